@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the headline measurement: DOF/s of one HPGMG-FV FMG F-cycle on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input: zero_vector(U) +
 one FMG F-cycle (reference bench_hpgmg, finite-volume/source/hpgmg-fv.c:50-99) on
@@ -17,7 +17,9 @@ limit per attempt; if the RCCL attempt fails or hangs on any rank, every child i
 children run the node-local hipIpc transport (`"transport": "ipc (fallback: <reason>)"`).  Every
 attempt begins with a transport self-test (a known pattern to and from every rank, a maximum, a
 rank-ordered sum), and the line carries `parity_ok`: the F-cycle norm equals the reference's string.
-One GPU, default workload: the line also carries `also` -- configs 3 (fv4, 27-pt), 4 and 1 with
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the outputs
+(--dump-outputs) and the line.  --full adds what takes runs of its own: on one GPU with the default
+workload the line then also carries `cpu_baseline` and `also` -- configs 3 (fv4, 27-pt), 4 and 1 with
 3 timed solves each, under the same clock, each in a fresh child process (a failure there cannot
 take the headline measurement with it; the headline line is also written to stderr first).
 Default series = north_star's STRONG scaling: the same 256^3 problem on 1, 2, 4, 8 GPUs
@@ -35,8 +37,14 @@ Extra objects on the JSON line:
                separate sweeps would have had to move in that time (a speed-up figure, not a bandwidth -- it may exceed the peak);
                traffic = HBM bytes per launch from the rocprofv3 PMC passes (traffic_source names the committed summary file),
                dram_GBs_from_pmc = traffic / launch time.  frac > 1 is refused.
-  cpu_baseline the REFERENCE binary (oracle/_ref, built from /root/reference by oracle/Makefile)
+  cpu_baseline (--full) the REFERENCE binary (oracle/_ref, built from the reference's sources by oracle/Makefile)
                run on this box's host cores; falls back to the CPU restatement ("port").
+
+--dump-outputs DIR: after the timed steps, what the last step left for its caller, as .npy files (rank 0's boxes):
+  fcycle_residual_norm.npy  float64 (1,)  the norm the F-cycle returns
+  u_sample.npy              float64 (<= 1048576,)  the fine-level solution u at a fixed, seeded sample of distinct cells (interior cells of
+                            rank 0's boxes, ordered by box position, then k, j, i)
+  u_box_sums.npy            float64 (boxes,)  the sum of u over the interior of each of those boxes, in the same order
 """
 import argparse
 import ctypes
@@ -121,12 +129,18 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own, on one GPU: the CPU baseline (`cpu_baseline`; config2, config5) and, for config2 fp64, the other "
+                         "BASELINE configurations (`also`).  A plain run leaves both out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (F-cycle norm, a seeded sample of the fine-level solution, its sum per box) "
+                         "to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--workload", choices=list(WORKLOADS), default="config2",
                     help="BASELINE.json configs; default config2 = the one the metric is quoted on.  config3 (`7 64`) and config4 (`8 8`) are the 8-GPU "
                          "configurations: with --gpus 1 they run their single-rank reading (512^3 on one GPU).  config5 = config2 with --precision fp32")
     ap.add_argument("--no-also", action="store_true",
-                    help="one GPU, config2: do NOT append the short runs of the other BASELINE configurations (`also` on the JSON line: config3-fv4, config3-27pt, "
+                    help="--full, one GPU, config2: do NOT append the short runs of the other BASELINE configurations (`also` on the JSON line: config3-fv4, config3-27pt, "
                          "config4, config1, 3 timed solves each).  The profiling scripts pass this so that a kernel trace holds config 2 only")
     ap.add_argument("--transport", choices=["rccl", "ipc"], default="rccl",
                     help="N > 1: rccl = grouped ncclSend / ncclRecv over xGMI (default, what the driver measures); ipc = the node-local peer-copy transport "
@@ -562,8 +576,46 @@ def run_workload(J, workload, steps, warmup, precision="fp64"):
         }
         if roof_error:
             line["error"] = roof_error
+        if args.dump_outputs:
+            dump_outputs(J, solver, norm, args.dump_outputs)
     lib.hpgmg_solver_destroy(solver)
     return line, roof_error
+
+
+DUMP_SAMPLE, DUMP_SEED = 1 << 20, 20240917
+
+
+def dump_outputs(J, solver, norm, out_dir):
+    """What the last timed step left for its caller: the F-cycle norm and the fine-level solution u (a fixed, seeded sample of the interior cells of this
+    rank's boxes, and the sum over each box), in float64.  Read after the clock has stopped."""
+    import numpy as np
+    H, lib = J.H, J.lib
+    level = lib.hpgmg_solver_level(solver, 0)
+    info = (ctypes.c_int * H.INFO_COUNT)()
+    lib.hpgmg_level_info(level, info)
+    d, g, n = info[H.INFO_BOX_DIM], info[H.INFO_GHOSTS], info[H.INFO_NUM_MY_BOXES]
+    j_stride, k_stride, volume = info[H.INFO_JSTRIDE], info[H.INFO_KSTRIDE], info[H.INFO_VOLUME]
+    w = d + 2 * g
+    lows = []
+    for b in range(n):
+        low = (ctypes.c_int * 3)()
+        lib.hpgmg_level_box_low(level, b, low)
+        lows.append((low[2], low[1], low[0], b))       # (k, j, i): boxes in the order of their position in the domain
+    cells = d ** 3
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n * cells, size=min(DUMP_SAMPLE, n * cells), replace=False))      # distinct cells of the boxes, in that order
+    sample, sums = np.empty(pick.size, dtype=np.float64), np.empty(n, dtype=np.float64)
+    buf = np.empty(volume, dtype=np.float64)
+    for pos, (_, _, _, b) in enumerate(sorted(lows)):
+        lib.hpgmg_level_read_vector(level, b, H.VECTOR_U, buf.ctypes.data)
+        box = buf[: w * k_stride].reshape(w, k_stride)[:, : w * j_stride].reshape(w, w, j_stride)
+        u = np.ascontiguousarray(box[g:g + d, g:g + d, g:g + d]).reshape(-1)
+        lo, hi = np.searchsorted(pick, [pos * cells, (pos + 1) * cells])
+        sample[lo:hi] = u[pick[lo:hi] - pos * cells]
+        sums[pos] = u.sum()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "fcycle_residual_norm.npy"), np.array([norm], dtype=np.float64))
+    np.save(os.path.join(out_dir, "u_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "u_box_sums.npy"), sums)
 
 
 def rank_main(args):
@@ -573,7 +625,7 @@ def rank_main(args):
     if J.dist is not None:
         J.dist.barrier()                       # every rank has flushed its C-level output before rank 0 prints the result
     if J.rank == 0:
-        if J.world == 1 and args.workload == "config2" and args.precision == "fp64" and not args.no_also:
+        if args.full and J.world == 1 and args.workload == "config2" and args.precision == "fp64" and not args.no_also:
             # the other BASELINE configurations under the same clock: 1 warm-up + 3 timed solves each (the 8-GPU ones in their single-rank reading), each in a FRESH
             # child process (a new process, not a re-exec) with its own time limit -- whatever ends one of them (an abort() from a failed allocation, its watchdog)
             # cannot take the headline measurement, which is already in hand, with it.  The headline line goes to stderr first, for the same reason.
@@ -597,7 +649,7 @@ def rank_main(args):
                 except Exception as exc:       # the headline measurement is done: report, never drop the line
                     also.append({"workload": w, "error": repr(exc)})
             line["also"] = also
-        if J.world == 1 and not args.no_cpu_baseline and args.workload in ("config2", "config5"):
+        if args.full and J.world == 1 and not args.no_cpu_baseline and args.workload in ("config2", "config5"):
             J.stage[0] = "cpu baseline (the reference binary on the host cores)"
             line["cpu_baseline"] = cpu_baseline()
         ctypes.CDLL(None).fflush(None)      # anything C code buffered on stdout goes first: the JSON line is the last line
