@@ -345,8 +345,9 @@ static const float *const *coef32_of(level_type *L) {
 }
 void hp_coef32_invalidate(level_type *L) { backend_t *B = hp_backend_of(L); B->coef32_valid = 0; if (B->halo) B->halo->coef_valid = 0; hp_images_invalidate_coefficients(B); hpgmg_hip_pair_packed_invalidate(&B->dev); }
 
-static long long pair_remote_smooths = 0;
+static long long pair_remote_smooths = 0, fp32_pair_smooths = 0;
 long long hpgmg_pair_remote_smooths(void) { return pair_remote_smooths; }   /* smooth() calls done as sweep pairs with remote faces (tests) */
+long long hpgmg_fp32_pair_smooths(void) { hp_lazy_flush(); return fp32_pair_smooths; }      /* smooth() calls whose sweep pairs read the fp32 coefficient copies (tests; a postponed smooth() is issued first) */
 
 /* the two plugin-private vectors per box that hold x1, x2 of the first sweep pair of a smooth() */
 void hp_ensure_pair_scratch(level_type *L, backend_t *B) {
@@ -365,7 +366,15 @@ void hp_ensure_pair_scratch(level_type *L, backend_t *B) {
 }
 void hpgmg_set_fused_sweeps(int on) { hp_switch_set(SW_FUSED_SWEEPS, on ? 1 : 0); }
 void hpgmg_set_pair_min_cells(long long cells) { hp_switch_set(SW_PAIR_MIN_CELLS, cells > 0 ? cells : 2000000); }
-/* common part: does the level qualify for the sweep-pair kernel, and are its two private vectors there? */
+/* common part: does the level qualify for the sweep-pair kernel, and are its two private vectors there?
+ * The CPU oracle's fp32 mode (its fp32_pair_smooth) restates which smooth() calls read the fp32 coefficient copies, from the
+ * level's geometry; keep the two in step.  With precision 32 on one rank they are exactly these:
+ *   Chebyshev smoother, 4 sweeps, 7-point operator (VC or CC); Dirichlet boundary; x_id and rhs_id both not VECTOR_TEMP;
+ *   dim.i * dim.j * dim.k >= HPGMG_PAIR_MIN_CELLS (default 2 000 000, hpgmg_set_pair_min_cells);
+ *   dim.i % 128 == 0; box side a multiple of 128, or 128 % box side == 0 with box side >= 16; at most 1024 boxes (kPairMaxBoxes);
+ *   boxes lexicographic and all on this rank (across ranks the coefficient streams stay fp64);
+ *   HPGMG_FUSED_SWEEPS and HPGMG_GHOST_FREE at their defaults (on); the storage conditions of pair_supported_dims (16-byte aligned boxes at
+ *   a constant distance) hold for every level the host layer creates. */
 static int pair_kernel_ready(level_type *L, int x_id, int rhs_id, int sweeps) {
   hpgmg_config cfg;
   hpgmg_get_config(&cfg);
@@ -407,6 +416,7 @@ static int smooth_cheby_pairs_fold(level_type *L, int x_id, int rhs_id, double a
   const int remote = !B->all_faces_local;
   const float *const *c32 = remote ? NULL : coef32_of(L);      /* across ranks the coefficient streams stay fp64 */
   int over = 0;
+  if (c32) fp32_pair_smooths++;
   if (remote) {
     pair_remote_smooths++;
     if (fold_Lc) { hpgmg_hip_pair_halo_fold_interpolation(fold_Lc, x_id, 1.0); interp_folded_remote++; }

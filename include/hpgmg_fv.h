@@ -103,6 +103,8 @@ long long   hpgmg_brick_capacity_refusals(void);      /* level visits left to th
 void        hpgmg_set_brick_wide(int on);      /* 0: the 27-point / fv4 plugins visit their launch-bound levels launch by launch (kernels/brick_wide.hip off; tests) */
 void        hpgmg_set_brick_chains(int on);    /* 0: one launch per level visit instead of one per V-cycle leg (tests) */
 long long   hpgmg_pair_remote_smooths(void);   /* smooth() calls executed as sweep pairs with faces owned by other ranks (tests) */
+long long   hpgmg_fp32_pair_smooths(void);     /* smooth() calls run on fp32-rounded coefficients (smoother precision 32): HIP, as sweep pairs reading the fp32
+                                                  copies; the CPU oracle, the same calls on rounded copies (tests) */
 long long   hpgmg_fused_residuals_remote(void); /* 7-point: fused residual passes (residual + restriction, residual + norm) run on levels with faces owned by other ranks (tests) */
 long long   hpgmg_fv4_rb_smooths(void);        /* fv4: smooth() calls run as one-pass red + black sweeps; hpgmg_rb27_passes(): such passes of the 27-point smoother (tests) */
 long long   hpgmg_rb27_passes(void);

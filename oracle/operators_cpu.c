@@ -68,8 +68,6 @@ int hpgmg_norm_scale_restrict_fused(level_type *l, int f, int r, level_type *c, 
 int hpgmg_residual_norm_fused(level_type *l, int res, int x, int r, double a, double b, double *o) { (void)l; (void)res; (void)x; (void)r; (void)a; (void)b; (void)o; return 0; }
 int hpgmg_interp_smooth_fused(level_type *f, int e, int R, level_type *c, double a, double b) { (void)f; (void)e; (void)R; (void)c; (void)a; (void)b; return 0; }
 void hpgmg_set_graphs(int on) { (void)on; }
-void hpgmg_set_smoother_precision(int bits) { (void)bits; }   /* the oracle is fp64 only */
-int hpgmg_get_smoother_precision(void) { return 64; }
 void hpgmg_segment_begin(long long key) { (void)key; }
 void hpgmg_segment_end(void) {}
 void hpgmg_solve_attempt_begin(void) {}      /* include/hpgmg_operators.h: no launch of this plugin can fail as a whole */
@@ -503,6 +501,78 @@ static void cheby_coefficients(const level_type *L, int degree, double *c1, doub
   }
 }
 
+/* ---------------------------------------------------------------- mixed-precision smoother (BASELINE config 5)
+ * Precision 32 (hpgmg_set_smoother_precision(32), HPGMG_SMOOTHER_PRECISION=32, `--fp32-smoother`): the smooth() calls that the HIP plugin runs
+ * as sweep pairs reading fp32 copies of Dinv, alpha and beta_i/j/k run here on copies of those five vectors rounded the same way,
+ * (double)(float)v over whole padded boxes.  Everything else -- the iterate, the right-hand side, all arithmetic, every other operator and
+ * every other level -- stays fp64, as there.  Default 64: nothing changes. */
+static int smoother_precision = 0;                 /* 0: not yet read from the environment */
+void hpgmg_set_smoother_precision(int bits) { smoother_precision = (bits == 32) ? 32 : 64; }
+int hpgmg_get_smoother_precision(void) {
+  if (!smoother_precision) { const char *e = getenv("HPGMG_SMOOTHER_PRECISION"); smoother_precision = (e && *e && atoll(e) == 32) ? 32 : 64; }
+  return smoother_precision;
+}
+static long long pair_min_cells = -1;              /* -1: not yet read from the environment */
+void hpgmg_set_pair_min_cells(long long cells) { pair_min_cells = cells > 0 ? cells : 2000000; }
+static long long get_pair_min_cells(void) {
+  if (pair_min_cells < 0) { const char *e = getenv("HPGMG_PAIR_MIN_CELLS"); pair_min_cells = (e && *e) ? atoll(e) : 2000000; }
+  return pair_min_cells;
+}
+static long long fp32_pair_smooths = 0;
+long long hpgmg_fp32_pair_smooths(void) { return fp32_pair_smooths; }     /* smooth() calls run on rounded coefficients (tests) */
+
+/* Does the HIP plugin run this smooth() as sweep pairs on fp32 coefficients?  The same rule as pair_kernel_ready
+ * (hpgmg_amd/csrc/host/plugin_smooth.c) and pair_supported_dims (kernels/pair.hip), derived from the level's geometry; the
+ * plugin's switches that could turn the pairs off (HPGMG_FUSED_SWEEPS, HPGMG_GHOST_FREE) are taken at their defaults, and its storage
+ * conditions (16-byte aligned boxes at a constant distance) hold for every level the host layer creates.  Keep the two in step. */
+static int fp32_pair_smooth(const level_type *L, const hpgmg_config *cfg, int x_id, int rhs_id, int sweeps) {
+  int bx;
+  if (hpgmg_get_smoother_precision() != 32) return 0;
+  if (cfg->smoother != HPGMG_SMOOTH_CHEBY || sweeps != 4 || cfg->op != HPGMG_OP_7PT) return 0;
+  if (L->boundary_condition.type != BC_DIRICHLET || x_id == VECTOR_TEMP || rhs_id == VECTOR_TEMP) return 0;
+  if ((long long)L->dim.i * L->dim.j * L->dim.k < get_pair_min_cells()) return 0;
+  if (L->dim.i % 128 != 0) return 0;                                            /* a wave owns a row of 128 cells ... */
+  if (L->box_dim % 128 != 0 && !(128 % L->box_dim == 0 && L->box_dim >= 16)) return 0;     /* ... of one box, or of several */
+  if (L->num_my_boxes < 1 || L->num_my_boxes > 1024) return 0;
+  if (L->num_my_boxes != L->boxes_in.i * L->boxes_in.j * L->boxes_in.k) return 0;          /* every box on this rank */
+  for (bx = 0; bx < L->num_my_boxes; bx++) {                                    /* local box b at lexicographic position b */
+    const box_type *X = &L->my_boxes[bx];
+    if (X->low.i != (bx % L->boxes_in.i) * L->box_dim || X->low.j != ((bx / L->boxes_in.i) % L->boxes_in.j) * L->box_dim ||
+        X->low.k != (bx / (L->boxes_in.i * L->boxes_in.j)) * L->box_dim) return 0;
+  }
+  return 1;
+}
+/* point the five coefficient vectors of every box at rounded copies; saved[] keeps the originals for coef32_restore() */
+enum { COEF32_COUNT = 5 };
+static const int coef32_ids[COEF32_COUNT] = { VECTOR_DINV, VECTOR_ALPHA, VECTOR_BETA_I, VECTOR_BETA_J, VECTOR_BETA_K };
+static double *coef32_buf = NULL;
+static size_t coef32_cap = 0;
+static double **coef32_swap_in(level_type *L) {
+  const size_t vol = (size_t)L->box_volume, n = (size_t)L->num_my_boxes * COEF32_COUNT;
+  double **saved = (double **)calloc(n, sizeof(double *));
+  int q;
+  if (!saved) { fprintf(stderr, "oracle: out of memory\n"); exit(1); }
+  if (n * vol > coef32_cap) { free(coef32_buf); coef32_buf = hpgmg_vector_alloc(n * vol); coef32_cap = n * vol; }
+  for (q = 0; q < (int)n; q++) {
+    box_type *B = &L->my_boxes[q / COEF32_COUNT];
+    const int id = coef32_ids[q % COEF32_COUNT];
+    if (id >= L->numVectors) continue;              /* Poisson / constant-coefficient builds carry no alpha vector */
+    const double *src = B->vectors[id];
+    double *dst = coef32_buf + (size_t)q * vol;
+    size_t n2;
+    _Pragma("omp parallel for")
+    for (n2 = 0; n2 < vol; n2++) dst[n2] = (double)(float)src[n2];
+    saved[q] = B->vectors[id];
+    B->vectors[id] = dst;
+  }
+  return saved;
+}
+static void coef32_restore(level_type *L, double **saved) {
+  int q;
+  for (q = 0; q < L->num_my_boxes * COEF32_COUNT; q++) if (saved[q]) L->my_boxes[q / COEF32_COUNT].vectors[coef32_ids[q % COEF32_COUNT]] = saved[q];
+  free(saved);
+}
+
 void smooth(level_type *L, int x_id, int rhs_id, double a, double b) {
   hpgmg_config cfg;
   hpgmg_get_config(&cfg);
@@ -510,8 +580,10 @@ void smooth(level_type *L, int x_id, int rhs_id, double a, double b) {
   int s;
   if (cfg.smoother == HPGMG_SMOOTH_CHEBY) {               /* operators/chebyshev.c:8-100 */
     double c1[16], c2[16];
+    double **coef64 = NULL;
     if (L->dominant_eigenvalue_of_DinvA <= 0.0 && L->my_rank == 0) fprintf(stderr, "dominant_eigenvalue_of_DinvA <= 0.0 !\n");
     cheby_coefficients(L, sweeps, c1, c2);
+    if (fp32_pair_smooth(L, &cfg, x_id, rhs_id, sweeps)) { coef64 = coef32_swap_in(L); fp32_pair_smooths++; }
     for (s = 0; s < sweeps; s++) {
       const int src = (s & 1) ? VECTOR_TEMP : x_id, dst = (s & 1) ? x_id : VECTOR_TEMP;
       exchange_boundary(L, src, shape);
@@ -520,6 +592,7 @@ void smooth(level_type *L, int x_id, int rhs_id, double a, double b) {
       DISPATCH(cheby_sweep, L, src, dst, rhs_id, a, b, c1[s % sweeps], c2[s % sweeps]);
       L->timers.smooth += now() - t0;
     }
+    if (coef64) coef32_restore(L, coef64);
   } else if (cfg.smoother == HPGMG_SMOOTH_GSRB) {         /* operators/gsrb.c:24-132 */
     const int oop = hpgmg_gsrb_out_of_place();
     for (s = 0; s < sweeps; s++) {
