@@ -28,6 +28,7 @@ STENCIL_SHAPE_BOX, STENCIL_SHAPE_STAR, STENCIL_SHAPE_NO_CORNERS = 0, 1, 2
 RESTRICT_CELL, RESTRICT_FACE_I, RESTRICT_FACE_J, RESTRICT_FACE_K = 0, 1, 2, 3
 OP_7PT, OP_27PT, OP_FV4, OP_FV2 = 0, 1, 2, 3
 SMOOTH_CHEBY, SMOOTH_GSRB, SMOOTH_JACOBI = 0, 1, 2
+BOTTOM_BICGSTAB, BOTTOM_CG, BOTTOM_CABICGSTAB, BOTTOM_CACG = 0, 1, 2, 3      # hpgmg_set_bottom_solver: -DUSE_BICGSTAB / CG / CABICGSTAB / CACG
 (INFO_DIM, INFO_BOX_DIM, INFO_GHOSTS, INFO_JSTRIDE, INFO_KSTRIDE, INFO_VOLUME, INFO_NUM_MY_BOXES,
  INFO_NUM_VECTORS, INFO_BOXES_IN_I, INFO_MY_RANK, INFO_NUM_RANKS, INFO_NUM_MY_BLOCKS, INFO_ACTIVE, INFO_COUNT) = range(14)
 
@@ -85,7 +86,7 @@ def _declare_driver_api(lib):
         "hpgmg_mg_num_levels": (c_int, [vp]),
         "hpgmg_set_transport": (None, [vp]),
         # the reference's compile-time choices of mg.c / solvers.c as run-time setters (call before hpgmg_solver_create / MGBuild) and its other drivers
-        "hpgmg_set_bottom_solver": (None, [c_int]), "hpgmg_get_bottom_solver": (c_int, []),      # 0 BiCGStab (-DUSE_BICGSTAB), 1 CG (-DUSE_CG)
+        "hpgmg_set_bottom_solver": (None, [c_int]), "hpgmg_get_bottom_solver": (c_int, []),      # BOTTOM_*: BiCGStab (-DUSE_BICGSTAB), CG, CABiCGStab, CACG
         "hpgmg_set_ucycles": (None, [c_int]),                                                   # -DUSE_UCYCLES
         "hpgmg_set_fmg_vcycles": (None, [c_int]),                                               # -DUNLIMIT_FMG_ITERATIONS: 20
         "MGSolve": (None, [vp, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl]),
@@ -105,6 +106,7 @@ def _declare_driver_api(lib):
         "apply_BCs": (None, [vp, c_int, c_int]),
         "apply_BCs_p1": (None, [vp, c_int, c_int]),
         "dot": (c_dbl, [vp, c_int, c_int]), "norm": (c_dbl, [vp, c_int]), "mean": (c_dbl, [vp, c_int]),
+        "matmul": (None, [vp, P(c_dbl), P(c_int), P(c_int), c_int, c_int, c_int]),      # solvers/matmul.c: the s-step solvers' Gram matrix
         "error": (c_dbl, [vp, c_int, c_int]),
         "add_vectors": (None, [vp, c_int, c_dbl, c_int, c_dbl, c_int]),
         "scale_vector": (None, [vp, c_int, c_dbl, c_int]),
@@ -151,6 +153,7 @@ def _declare_kernel_api(lib):
         "hpgmg_hip_norm_max": (c_int, [L, c_int, P(c_dbl)]),
         "hpgmg_hip_dot": (c_int, [L, c_int, c_int, P(c_dbl)]),
         "hpgmg_hip_sum": (c_int, [L, c_int, P(c_dbl)]),
+        "hpgmg_hip_gram": (c_int, [L, P(c_int), c_int, P(c_int), c_int, P(c_dbl)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -348,7 +348,8 @@ int hpgmg_solve_attempt_end(void) {
   }
   return 0;
 }
-double hp_allreduce_scalar(level_type *L, double v, int op) {
+double hp_allreduce_scalar(level_type *L, double v, int op) { hp_allreduce_values(L, &v, 1, op); return v; }
+void hp_allreduce_values(level_type *L, double *v, int n, int op) {
   const hpgmg_transport *T = hpgmg_get_transport();
   if (hpgmg_hip_brick_visit_error()) {
     if (!attempt_open) { fprintf(stderr, "%s  HPGMG_BRICK_VISITS=0 runs these levels launch by launch.\n", brick_failure_text); abort(); }
@@ -356,9 +357,8 @@ double hp_allreduce_scalar(level_type *L, double v, int op) {
   }
   if (T && T->size > 1) {
     hpgmg_level_ext *X = hpgmg_level_ext_get(L);
-    if (X->num_active_ranks > 1) { const double t0 = hp_now(); T->allreduce(T->ctx, &v, 1, op, X->active_ranks, X->num_active_ranks); L->timers.collectives += hp_now() - t0; }   /* host-synchronous by nature: host clock in every mode */
+    if (X->num_active_ranks > 1) { const double t0 = hp_now(); T->allreduce(T->ctx, v, n, op, X->active_ranks, X->num_active_ranks); L->timers.collectives += hp_now() - t0; }   /* host-synchronous by nature: host clock in every mode */
   }
-  return v;
 }
 double hp_do_dot(level_type *L, int a, int b) { double v; BLAS1(hpgmg_hip_dot(&hp_backend_of(L)->dev, a, b, &v)); return hp_allreduce_scalar(L, v, HPGMG_REDUCE_SUM); }
 double hp_do_norm(level_type *L, int a) {

@@ -183,6 +183,7 @@ HP_INTERNAL void hp_do_add_vectors(level_type *L, int c, double sa, int a, doubl
 HP_INTERNAL void hp_do_mul_vectors(level_type *L, int c, double s, int a, int b);
 HP_INTERNAL void hp_do_scale_vector(level_type *L, int c, double s, int a);
 HP_INTERNAL double hp_allreduce_scalar(level_type *L, double v, int op);
+HP_INTERNAL void hp_allreduce_values(level_type *L, double *v, int n, int op);      /* n values in place, one transport call (matmul's whole matrix) */
 HP_INTERNAL double hp_do_dot(level_type *L, int a, int b);
 HP_INTERNAL double hp_do_norm(level_type *L, int a);
 HP_INTERNAL void hp_small_ops_forget(void);

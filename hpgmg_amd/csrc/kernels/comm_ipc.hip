@@ -33,7 +33,7 @@
 #include "common.hpp"
 
 namespace hpgmg {
-constexpr int kIpcMaxRanks = 16, kIpcMaxVals = 16;
+constexpr int kIpcMaxRanks = 16, kIpcMaxVals = 1024;     // values per reduction: a scalar on the V-cycle path, matmul's whole Gram matrix (<= 32 x 32) for the s-step solvers
 struct IpcDesc { hipIpcMemHandle_t mem; long long offset, size; int tag, pad; unsigned long long gen; };      // gen: which export of the receiver's this handle is (a freed allocation's address may come back)
 struct IpcChannel {                                  // data flows sender -> receiver; lives at [receiver][sender]
   std::atomic<unsigned long long> posted, sent;
@@ -236,7 +236,7 @@ void hpgmg_hip_ipc_allreduce(void *ctx, double *vals, int n, int op, const int *
   (void)ctx;
   if (nranks <= 1) return;
   if (!g_seg) ipc_die("transport used before hpgmg_hip_ipc_init");
-  if (n < 1 || n > kIpcMaxVals) ipc_die("allreduce of more than 16 values");
+  if (n < 1 || n > kIpcMaxVals) ipc_die("allreduce of more than 1024 values");
   for (int q = 0; q < nranks; q++) {                    // my values into every member's copy of my channel, once it has consumed the previous ones
     const int p = ranks[q];
     if (p == g_irank) continue;

@@ -30,7 +30,7 @@
 namespace hpgmg {
 static ncclComm_t g_comm = nullptr;
 static int g_rank = 0, g_size = 1;
-constexpr int kRedMax = 16;           // values per reduction call (the path reduces one)
+constexpr int kRedMax = 1024;         // values per reduction call (the V-cycle path reduces one; matmul the whole Gram matrix, <= 32 x 32)
 static double *g_red_dev = nullptr;   // [(g_size + 1) * kRedMax] staging: every rank's partials, then my own
 static double *g_red_host = nullptr;  // pinned, same size
 static long long g_allgathers = 0;

@@ -341,6 +341,10 @@ int hpgmg_hip_norm_copy_restrict(const hpgmg_hip_level *L, int f_id, int r_id, c
 int  hpgmg_hip_norm_copy_restrict_deferred(const hpgmg_hip_level *L, int f_id, int r_id, const hpgmg_hip_level *Lc, int rc_id, const int *restrict_map);
 int  hpgmg_hip_deferred_fetch(double *out);
 int hpgmg_hip_sum(const hpgmg_hip_level *L, int id, double *out);                     /* mean :336 (before the divide) */
+/* the Gram matrix of the s-step bottom solvers (solvers/matmul.c:6-62, this rank's boxes only): C_host[mm * cols + nn] = sum over the interior of
+ * id_A[mm] * id_B[nn] for nn >= mm, mirrored to C_host[nn * cols + mm] where that entry exists.  Per box one chain in k, j, i order, products first;
+ * box partials added in box order (NOT the tile order above).  One launch; synchronises.  rows, cols <= 32; the ids must name vectors of the level. */
+int hpgmg_hip_gram(const hpgmg_hip_level *L, const int *id_A, int rows, const int *id_B, int cols, double *C_host);
 
 /* ---- operators/rebuild.c:47-208 black-box rebuild: accumulate one colouring (x = 0/1 pattern, ghosts
  *      already exchanged / BCs applied) into Aii and sum|Aij|, then turn them into Dinv, L1inv, lambda_max ---- */

@@ -53,8 +53,10 @@ typedef struct {
 int  hpgmg_configure(const hpgmg_config *cfg);
 void hpgmg_get_config(hpgmg_config *cfg);
 int  hpgmg_vectors_reserved(void); /* VECTORS_RESERVED: 9, or 11 for Helmholtz */
-enum { HPGMG_BOTTOM_BICGSTAB = 0, HPGMG_BOTTOM_CG = 1 };      /* the reference's -DUSE_BICGSTAB / -DUSE_CG (solvers.c:17-24): host loops over the operators */
-void hpgmg_set_bottom_solver(int which);   /* before MGBuild (the solver's work vectors are created there: 8 / 5) */
+/* the reference's -DUSE_BICGSTAB / -DUSE_CG / -DUSE_CABICGSTAB / -DUSE_CACG (solvers.c:17-24): host loops over the operators.  The two CA (s-step)
+ * solvers are the reference's defaults for them: CA_KRYLOV_S 4, telescoping CABiCGStab, no diagonal preconditioning.  Any other value selects BiCGStab. */
+enum { HPGMG_BOTTOM_BICGSTAB = 0, HPGMG_BOTTOM_CG = 1, HPGMG_BOTTOM_CABICGSTAB = 2, HPGMG_BOTTOM_CACG = 3 };
+void hpgmg_set_bottom_solver(int which);   /* before MGBuild (the solver's work vectors are created there: 8 / 5 / 20 / 12) */
 int  hpgmg_get_bottom_solver(void);
 
 /* ---- operators.h:14-15 ---- */
@@ -81,6 +83,12 @@ void apply_BCs_v4(level_type *level, int x_id, int shape);
 void extrapolate_betas(level_type *level);
 /* ---- operators.h:35-45 ---- */
 double dot(level_type *level, int id_a, int id_b);
+/* solvers/matmul.c:6-62: C[mm * cols + nn] = dot(id_A[mm], id_B[nn]) for nn >= mm, mirrored to C[nn * cols + mm] where that entry exists (the
+ * CA solvers pass id_A == id_B; A_equals_B_transpose is accepted and, as in the reference, not read), then ONE allreduce of the whole rows x cols
+ * matrix.  Order of each entry: per box one chain over its dim^3 interior cells in k, j, i order, products a * b formed first, starting from 0.0;
+ * the box partials added in box order 0 .. num_my_boxes - 1, starting from 0.0 -- NOT dot()'s per-tile order.  host/solvers.c defines a weak
+ * default (boxes downloaded through hpgmg_vector_download, summed on the host); the HIP plugin overrides it with one Gram launch. */
+void matmul(level_type *level, double *C, int *id_A, int *id_B, int rows, int cols, int A_equals_B_transpose);
 double norm(level_type *level, int id_a);
 double mean(level_type *level, int id_a);
 double error(level_type *level, int id_a, int id_b);
