@@ -38,6 +38,22 @@ class Config(ctypes.Structure):
     _fields_ = [("op", ctypes.c_int), ("smoother", ctypes.c_int), ("helmholtz", ctypes.c_int), ("variable_coeff", ctypes.c_int)]
 
 
+class UserInfo(ctypes.Structure):
+    """hpgmg_user_info of include/hpgmg_fv.h."""
+    _fields_ = [("norm_of_residual", ctypes.c_double), ("norm_of_f", ctypes.c_double), ("mean_shift", ctypes.c_double),
+                ("vcycles", ctypes.c_int), ("converged", ctypes.c_int)]
+
+
+# hpgmg_dense_pack layouts / checks / where, hpgmg_user_* statuses and methods (include/hpgmg_operators.h, include/hpgmg_fv.h)
+DENSE_CELL, DENSE_FACE_I, DENSE_FACE_J, DENSE_FACE_K = 0, 1, 2, 3
+DENSE_CHECK_FINITE, DENSE_CHECK_POSITIVE, DENSE_CHECK_NONNEGATIVE = 0, 1, 2
+DENSE_NOT_FINITE, DENSE_OUT_OF_RANGE = 1, 2
+WHERE_HOST, WHERE_PLUGIN = 0, 1
+(USER_OK, USER_BAD_ARGUMENT, USER_CONFLICT, USER_MULTI_RANK, USER_NOT_FINITE, USER_OUT_OF_RANGE,
+ USER_NOT_READY, USER_UNSUPPORTED) = 0, -1, -2, -3, -4, -5, -6, -7
+USER_FMG, USER_MG = 0, 1
+
+
 class HipLevel(ctypes.Structure):
     """hpgmg_hip_level of include/hpgmg_hip.h (kernel-side geometry record)."""
     _fields_ = [("box_base", ctypes.c_void_p), ("box_low", ctypes.c_void_p), ("num_boxes", ctypes.c_int),
@@ -119,6 +135,18 @@ def _declare_driver_api(lib):
         "random_vector": (None, [vp, c_int]),
         "initialize_problem": (None, [vp, c_dbl, c_dbl, c_dbl]),
         "IterativeSolver": (None, [vp, c_int, c_int, c_dbl, c_dbl, c_dbl]),
+        # dense N^3 arrays <-> a level's boxes, and the user-problem API on them (hpgmg_amd/problem.py)
+        "hpgmg_dense_pack": (c_int, [vp, c_int, vp, c_int, c_int, c_int]),
+        "hpgmg_dense_unpack": (c_int, [vp, c_int, vp, c_int]),
+        "hpgmg_user_create": (c_int, [c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, P(vp)]),
+        "hpgmg_user_destroy": (None, [vp]),
+        "hpgmg_user_set_verbose": (None, [vp, c_int]),
+        "hpgmg_user_solver_of": (vp, [vp]),
+        "hpgmg_user_set_coefficients": (c_int, [vp, vp, vp, vp, vp, c_int]),
+        "hpgmg_user_set_rhs": (c_int, [vp, vp, c_int, P(c_dbl)]),
+        "hpgmg_user_solve": (c_int, [vp, c_int, c_dbl, vp, c_int, P(UserInfo)]),
+        "hpgmg_user_get_solution": (c_int, [vp, vp, c_int]),
+        "hpgmg_user_apply": (c_int, [vp, vp, vp, c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -154,6 +182,7 @@ def _declare_kernel_api(lib):
         "hpgmg_hip_dot": (c_int, [L, c_int, c_int, P(c_dbl)]),
         "hpgmg_hip_sum": (c_int, [L, c_int, P(c_dbl)]),
         "hpgmg_hip_gram": (c_int, [L, P(c_int), c_int, P(c_int), c_int, P(c_dbl)]),
+        "hpgmg_hip_pair_launch_counts": (None, [P(ctypes.c_longlong)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

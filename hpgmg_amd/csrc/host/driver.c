@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <math.h>
 #include "hpgmg_fv.h"
 #ifdef _OPENMP
 #include <omp.h>
@@ -149,6 +150,246 @@ void hpgmg_solver_richardson(hpgmg_solver *s, double out[2]) {
   richardson_error(&s->mg, 0, VECTOR_U);
   out[0] = hpgmg_last_solve.richardson_error;
   out[1] = hpgmg_last_solve.richardson_order;
+}
+
+/* ------------------------------------------------------------------ dense arrays <-> boxes: host defaults
+ * (include/hpgmg_operators.h).  Box by box through the plugin's upload / download; weak, so that a plugin with kernels for it (the HIP plugin:
+ * host/plugin_dense.c) replaces them while one without (the CPU oracle, whose memory is host memory for either `where`) gets these. */
+static int dense_extent(const level_type *L, int layout, int axis) {
+  const int n = axis == 0 ? L->dim.i : axis == 1 ? L->dim.j : L->dim.k;
+  return n + (layout == HPGMG_DENSE_FACE_I + axis && L->boundary_condition.type == BC_DIRICHLET);
+}
+__attribute__((weak)) int hpgmg_dense_pack(level_type *L, int id, const double *src, int where, int layout, int check) {
+  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || layout < HPGMG_DENSE_CELL || layout > HPGMG_DENSE_FACE_K || !src) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  const size_t ni = (size_t)dense_extent(L, layout, 0), nj = (size_t)dense_extent(L, layout, 1);
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  double *box = (double *)malloc((size_t)L->box_volume * sizeof(double));
+  int b, i, j, k, status = 0;
+  for (b = 0; b < L->num_my_boxes; b++) {
+    const box_type *B = &L->my_boxes[b];
+    /* the high ghost layer along the array's axis belongs to it on the domain's high face (Dirichlet face arrays) */
+    const int ei = dim + (ni > (size_t)L->dim.i && B->low.i + dim == L->dim.i);
+    const int ej = dim + (nj > (size_t)L->dim.j && B->low.j + dim == L->dim.j);
+    const int ek = dim + (dense_extent(L, layout, 2) > L->dim.k && B->low.k + dim == L->dim.k);
+    memset(box, 0, (size_t)L->box_volume * sizeof(double));
+    for (k = 0; k < ek; k++) for (j = 0; j < ej; j++) for (i = 0; i < ei; i++) {
+      const double v = src[((size_t)(B->low.k + k) * nj + (size_t)(B->low.j + j)) * ni + (size_t)(B->low.i + i)];
+      if (!isfinite(v)) status |= HPGMG_DENSE_NOT_FINITE;
+      else if ((check == HPGMG_DENSE_CHECK_POSITIVE && !(v > 0.0)) || (check == HPGMG_DENSE_CHECK_NONNEGATIVE && !(v >= 0.0))) status |= HPGMG_DENSE_OUT_OF_RANGE;
+      box[(i + g) + (j + g) * jS + (k + g) * kS] = v;
+    }
+    hpgmg_vector_upload(B->vectors[id], box, (size_t)L->box_volume);
+  }
+  free(box);
+  return status;
+}
+__attribute__((weak)) int hpgmg_dense_unpack(level_type *L, int id, double *dst, int where) {
+  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || !dst) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  const size_t ni = (size_t)L->dim.i, nj = (size_t)L->dim.j;
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  double *box = (double *)malloc((size_t)L->box_volume * sizeof(double));
+  int b, i, j, k;
+  for (b = 0; b < L->num_my_boxes; b++) {
+    const box_type *B = &L->my_boxes[b];
+    hpgmg_vector_download(box, B->vectors[id], (size_t)L->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++)
+      dst[((size_t)(B->low.k + k) * nj + (size_t)(B->low.j + j)) * ni + (size_t)(B->low.i + i)] = box[(i + g) + (j + g) * jS + (k + g) * kS];
+  }
+  free(box);
+  return 0;
+}
+
+/* ------------------------------------------------------------------ user problems on dense arrays (include/hpgmg_fv.h) */
+struct hpgmg_user_solver {
+  hpgmg_solver s;              /* the finest level, the hierarchy, a, b, h */
+  int n, bc, verbose;
+  int x_id;                    /* the finest level's one extra vector: u0 of a warm start, the operand of apply */
+  int operator_ok, rhs_ok;     /* 0 after a set_coefficients / set_rhs that was refused part way */
+  double mean_shift;           /* what the last set_rhs subtracted from f */
+};
+static int user_live = 0;              /* user solvers alive: the process-wide configuration belongs to them */
+static hpgmg_config user_cfg;
+
+/* user calls print only when the solver's verbose flag is on (the library's default, hpgmg_verbose = 1, is the benchmark's) */
+#define USER_QUIET(us) const int verbose_saved_ = hpgmg_verbose; hpgmg_verbose = (us)->verbose
+#define USER_LOUD() hpgmg_verbose = verbose_saved_
+
+static int user_config_ok(void) {                 /* nobody has reconfigured the process under the live user solvers */
+  hpgmg_config cfg;
+  hpgmg_get_config(&cfg);
+  return cfg.op == user_cfg.op && cfg.smoother == user_cfg.smoother && cfg.helmholtz == user_cfg.helmholtz && cfg.variable_coeff == user_cfg.variable_coeff;
+}
+static int user_pack_status(int st) {
+  if (st < 0) return HPGMG_USER_BAD_ARGUMENT;
+  if (st & HPGMG_DENSE_NOT_FINITE) return HPGMG_USER_NOT_FINITE;
+  if (st & HPGMG_DENSE_OUT_OF_RANGE) return HPGMG_USER_OUT_OF_RANGE;
+  return HPGMG_USER_OK;
+}
+
+int hpgmg_user_create(int n, int box_dim, int bc, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out) {
+  const hpgmg_transport *T = hpgmg_get_transport();
+  if (!out) return HPGMG_USER_BAD_ARGUMENT;
+  *out = NULL;
+  if (op != HPGMG_OP_7PT) return HPGMG_USER_UNSUPPORTED;
+  if (T && T->size > 1) return HPGMG_USER_MULTI_RANK;
+  if (box_dim <= 0) for (box_dim = 128; box_dim > 1 && n % box_dim; box_dim /= 2) {}
+  if (n < 4 || box_dim < 4 || (box_dim & (box_dim - 1)) || box_dim > 512 || n % box_dim) return HPGMG_USER_BAD_ARGUMENT;
+  if (bc != BC_DIRICHLET && bc != BC_PERIODIC) return HPGMG_USER_BAD_ARGUMENT;
+  if (smoother < HPGMG_SMOOTH_CHEBY || smoother > HPGMG_SMOOTH_JACOBI) return HPGMG_USER_BAD_ARGUMENT;
+  if (!isfinite(a) || !isfinite(b) || a < 0.0 || !(b > 0.0)) return HPGMG_USER_BAD_ARGUMENT;
+  if (!(h > 0.0) || !isfinite(h)) h = 1.0 / (double)n;
+  const hpgmg_config cfg = { HPGMG_OP_7PT, smoother, a != 0.0, 1 };
+  if (user_live > 0 && (cfg.smoother != user_cfg.smoother || cfg.helmholtz != user_cfg.helmholtz)) return HPGMG_USER_CONFLICT;
+  if (hpgmg_configure(&cfg)) return HPGMG_USER_UNSUPPORTED;
+  user_cfg = cfg;
+  user_live++;
+
+  hpgmg_user_solver *us = (hpgmg_user_solver *)calloc(1, sizeof(*us));
+  hpgmg_solver *s = &us->s;
+  us->n = n; us->bc = bc; us->operator_ok = us->rhs_ok = 1;
+  USER_QUIET(us);
+  s->boxes_in_i = n / box_dim; s->box_dim = box_dim; s->my_rank = 0; s->num_ranks = 1;
+  s->a = a; s->b = b; s->h = h;
+  us->x_id = hpgmg_vectors_reserved();
+  create_level(&s->level_h, s->boxes_in_i, box_dim, stencil_get_radius(), us->x_id + 1, bc, 0, 1);
+  s->level_h.h = h;
+  { /* coefficients 1 (high domain faces included), f = 0: initialize_problem's layout with constant values */
+    const size_t big = (size_t)n * n * (n + 1);
+    double *ones = (double *)malloc(big * sizeof(double));
+    size_t q;
+    for (q = 0; q < big; q++) ones[q] = 1.0;
+    hpgmg_dense_pack(&s->level_h, VECTOR_BETA_I, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_FACE_I, HPGMG_DENSE_CHECK_POSITIVE);
+    hpgmg_dense_pack(&s->level_h, VECTOR_BETA_J, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_FACE_J, HPGMG_DENSE_CHECK_POSITIVE);
+    hpgmg_dense_pack(&s->level_h, VECTOR_BETA_K, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_FACE_K, HPGMG_DENSE_CHECK_POSITIVE);
+    if (cfg.helmholtz) hpgmg_dense_pack(&s->level_h, VECTOR_ALPHA, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_NONNEGATIVE);
+    free(ones);
+  }
+  rebuild_operator(&s->level_h, NULL, a, b);
+  MGBuild(&s->mg, &s->level_h, a, b, bc == BC_PERIODIC ? 2 : 1);
+  USER_LOUD();
+  *out = us;
+  return HPGMG_USER_OK;
+}
+
+void hpgmg_user_destroy(hpgmg_user_solver *us) {
+  if (!us) return;
+  USER_QUIET(us);
+  MGDestroy(&us->s.mg);
+  destroy_level(&us->s.level_h);     /* frees the plugin's staging buffer with the level */
+  USER_LOUD();
+  free(us);
+  user_live--;
+}
+
+void hpgmg_user_set_verbose(hpgmg_user_solver *us, int on) { us->verbose = on; }
+hpgmg_solver *hpgmg_user_solver_of(hpgmg_user_solver *us) { return &us->s; }
+
+int hpgmg_user_set_coefficients(hpgmg_user_solver *us, const double *alpha, const double *beta_i, const double *beta_j, const double *beta_k, int where) {
+  hpgmg_solver *s = &us->s;
+  level_type *L = &s->level_h;
+  const int helmholtz = s->a != 0.0;
+  if (!beta_i || !beta_j || !beta_k || (helmholtz && !alpha) || (!helmholtz && alpha)) return HPGMG_USER_BAD_ARGUMENT;
+  if (!user_config_ok()) return HPGMG_USER_CONFLICT;
+  int st = 0, e;
+  USER_QUIET(us);
+  us->operator_ok = 0;
+  if ((e = hpgmg_dense_pack(L, VECTOR_BETA_I, beta_i, where, HPGMG_DENSE_FACE_I, HPGMG_DENSE_CHECK_POSITIVE)) < 0) goto refused;
+  st |= e;
+  if ((e = hpgmg_dense_pack(L, VECTOR_BETA_J, beta_j, where, HPGMG_DENSE_FACE_J, HPGMG_DENSE_CHECK_POSITIVE)) < 0) goto refused;
+  st |= e;
+  if ((e = hpgmg_dense_pack(L, VECTOR_BETA_K, beta_k, where, HPGMG_DENSE_FACE_K, HPGMG_DENSE_CHECK_POSITIVE)) < 0) goto refused;
+  st |= e;
+  if (helmholtz && (e = hpgmg_dense_pack(L, VECTOR_ALPHA, alpha, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_NONNEGATIVE)) < 0) goto refused;
+  if (helmholtz) st |= e;
+  if (st) { USER_LOUD(); return user_pack_status(st); }
+  rebuild_operator(L, NULL, s->a, s->b);
+  MGRebuildCoarse(&s->mg, s->a, s->b);
+  us->operator_ok = 1;
+  USER_LOUD();
+  return HPGMG_USER_OK;
+refused:
+  USER_LOUD();
+  return HPGMG_USER_BAD_ARGUMENT;
+}
+
+int hpgmg_user_set_rhs(hpgmg_user_solver *us, const double *f, int where, double *mean_shift) {
+  level_type *L = &us->s.level_h;
+  if (!f) return HPGMG_USER_BAD_ARGUMENT;
+  USER_QUIET(us);
+  const int st = user_pack_status(hpgmg_dense_pack(L, VECTOR_F, f, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
+  us->rhs_ok = (st == HPGMG_USER_OK);
+  us->mean_shift = 0.0;
+  if (us->rhs_ok && L->must_subtract_mean) {     /* periodic without an a * alpha term: only a mean-free f has a solution (hpgmg_solver_create_explicit) */
+    const double avg = mean(L, VECTOR_F);
+    if (avg != 0.0) { shift_vector(L, VECTOR_F, VECTOR_F, -avg); us->mean_shift = avg; }
+  }
+  USER_LOUD();
+  if (mean_shift) *mean_shift = us->mean_shift;
+  return st;
+}
+
+int hpgmg_user_solve(hpgmg_user_solver *us, int method, double rtol, const double *u0, int where, hpgmg_user_info *info) {
+  hpgmg_solver *s = &us->s;
+  level_type *L = &s->level_h;
+  if ((method != HPGMG_USER_FMG && method != HPGMG_USER_MG) || !(rtol > 0.0)) return HPGMG_USER_BAD_ARGUMENT;
+  if (!us->operator_ok || !us->rhs_ok) return HPGMG_USER_NOT_READY;
+  if (!user_config_ok()) return HPGMG_USER_CONFLICT;
+  USER_QUIET(us);
+  const int v0 = L->vcycles_from_this_level;
+  double norm_of_F, r;
+  if (u0) {                     /* u = u0 + e with A e = f - A u0; the V-cycles stop when |f - A u| has dropped below rtol |f| */
+    const int st = user_pack_status(hpgmg_dense_pack(L, VECTOR_U, u0, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
+    if (st) { USER_LOUD(); return st; }
+    residual(L, us->x_id, VECTOR_U, VECTOR_F, s->a, s->b);
+    norm_of_F = norm(L, VECTOR_F);
+    const double norm_of_r0 = norm(L, us->x_id);
+    if (norm_of_r0 > 0.0) {
+      MGSolve(&s->mg, 0, VECTOR_U, us->x_id, s->a, s->b, rtol * norm_of_F / norm_of_r0);
+      hpgmg_dense_pack(L, us->x_id, u0, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE);
+      add_vectors(L, VECTOR_U, 1.0, VECTOR_U, 1.0, us->x_id);
+    }
+    residual(L, VECTOR_TEMP, VECTOR_U, VECTOR_F, s->a, s->b);
+    r = norm(L, VECTOR_TEMP);
+  } else if (method == HPGMG_USER_FMG) {           /* the benchmark's solve (hpgmg_solver_fmg) */
+    hpgmg_fmg_zero_u_first();
+    FMGSolve(&s->mg, 0, VECTOR_U, VECTOR_F, s->a, s->b, rtol);
+    norm_of_F = hpgmg_last_solve.norm_of_F; r = hpgmg_last_solve.norm_of_residual;
+  } else {
+    MGSolve(&s->mg, 0, VECTOR_U, VECTOR_F, s->a, s->b, rtol);
+    norm_of_F = hpgmg_last_solve.norm_of_F; r = hpgmg_last_solve.norm_of_residual;
+  }
+  USER_LOUD();
+  if (info) {
+    info->norm_of_residual = r; info->norm_of_f = norm_of_F; info->mean_shift = us->mean_shift;
+    info->vcycles = L->vcycles_from_this_level - v0;
+    info->converged = (r == 0.0) || (r < rtol * norm_of_F);
+  }
+  return HPGMG_USER_OK;
+}
+
+int hpgmg_user_get_solution(hpgmg_user_solver *us, double *u, int where) {
+  USER_QUIET(us);
+  const int st = hpgmg_dense_unpack(&us->s.level_h, VECTOR_U, u, where);
+  USER_LOUD();
+  return st < 0 ? HPGMG_USER_BAD_ARGUMENT : HPGMG_USER_OK;
+}
+
+int hpgmg_user_apply(hpgmg_user_solver *us, const double *x, double *y, int where) {
+  hpgmg_solver *s = &us->s;
+  level_type *L = &s->level_h;
+  if (!y) return HPGMG_USER_BAD_ARGUMENT;
+  if (!us->operator_ok) return HPGMG_USER_NOT_READY;
+  if (!user_config_ok()) return HPGMG_USER_CONFLICT;
+  USER_QUIET(us);
+  int st = user_pack_status(hpgmg_dense_pack(L, us->x_id, x, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
+  if (st == HPGMG_USER_OK) {
+    apply_op(L, VECTOR_R, us->x_id, s->a, s->b);      /* VECTOR_R: every solve sets it from f before reading it */
+    if (hpgmg_dense_unpack(L, VECTOR_R, y, where) < 0) st = HPGMG_USER_BAD_ARGUMENT;
+  }
+  USER_LOUD();
+  return st;
 }
 
 /* ------------------------------------------------------------------ CLI */

@@ -361,6 +361,12 @@ void MGBuild(mg_type *G, level_type *fine, double a, double b, int minCoarseGrid
       }
   }
   SAY(G->my_rank, "\n");
+  MGRebuildCoarse(G, a, b);
+  G->timers.MGBuild += now() - t0;
+}
+
+void MGRebuildCoarse(mg_type *G, double a, double b) {
+  int l;
   for (l = 1; l < G->num_levels; l++) rebuild_operator(G->levels[l], G->levels[l - 1], a, b);
   SAY(G->my_rank, "\n");
 
@@ -371,7 +377,6 @@ void MGBuild(mg_type *G, level_type *fine, double a, double b, int minCoarseGrid
     if (hpgmg_vectors_reserved() > VECTOR_ALPHA && L->active) alpha_is_zero = (dot(L, VECTOR_ALPHA, VECTOR_ALPHA) == 0.0);
     if (L->boundary_condition.type == BC_PERIODIC && (a == 0 || alpha_is_zero)) L->must_subtract_mean = 1;
   }
-  G->timers.MGBuild += now() - t0;
 }
 
 void MGDestroy(mg_type *G) {

@@ -1,0 +1,50 @@
+/*
+ * plugin_dense.c -- hpgmg_dense_pack / hpgmg_dense_unpack of the operator plugin (include/hpgmg_operators.h): one launch of
+ * kernels/dense_io.hip per array.  A device array is read / written in place; a host array is copied once into the level's staging buffer
+ * (allocated on first use, freed with the level) and packed from there, or unpacked into it and copied out once.  They replace the weak
+ * host defaults of host/driver.c, which go box by box through hpgmg_vector_upload / download.
+ */
+#include "plugin_internal.h"
+
+static size_t dense_extent(const level_type *L, int layout, int axis) {     /* axis 0 = i, 1 = j, 2 = k */
+  const int n = axis == 0 ? L->dim.i : axis == 1 ? L->dim.j : L->dim.k;
+  return (size_t)n + (layout == HPGMG_DENSE_FACE_I + axis && L->boundary_condition.type == BC_DIRICHLET);
+}
+
+static double *dense_stage(backend_t *B, size_t n) {
+  if (B->dense_stage_len < n) {
+    if (B->dense_stage) hpgmg_hip_free(B->dense_stage);
+    B->dense_stage = (double *)hpgmg_hip_malloc(n * sizeof(double));
+    B->dense_stage_len = B->dense_stage ? n : 0;
+    if (!B->dense_stage) { fprintf(stderr, "hpgmg: dense arrays: no device memory for a %zu-double staging buffer\n", n); abort(); }
+  }
+  return B->dense_stage;
+}
+
+int hpgmg_dense_pack(level_type *L, int id, const double *src, int where, int layout, int check) {
+  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || layout < HPGMG_DENSE_CELL || layout > HPGMG_DENSE_FACE_K || !src) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  backend_t *B = hp_backend_of(L);
+  const size_t ni = dense_extent(L, layout, 0), nj = dense_extent(L, layout, 1), nk = dense_extent(L, layout, 2);
+  const double *d_src = src;
+  int status = 0;
+  if (where == HPGMG_WHERE_HOST) {
+    double *stage = dense_stage(B, ni * nj * nk);
+    HIP_OK(hpgmg_hip_memcpy_h2d(stage, src, ni * nj * nk * sizeof(double)));
+    d_src = stage;
+  }
+  HIP_OK(hpgmg_hip_dense_pack(&B->dev, id, d_src, (int)ni, (int)nj, (int)nk, check, &status));
+  return status;
+}
+
+int hpgmg_dense_unpack(level_type *L, int id, double *dst, int where) {
+  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || !dst) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  backend_t *B = hp_backend_of(L);
+  const size_t n = (size_t)L->dim.i * L->dim.j * L->dim.k;
+  if (where == HPGMG_WHERE_PLUGIN) { HIP_OK(hpgmg_hip_dense_unpack(&B->dev, id, dst)); return 0; }
+  double *stage = dense_stage(B, n);
+  HIP_OK(hpgmg_hip_dense_unpack(&B->dev, id, stage));
+  HIP_OK(hpgmg_hip_memcpy_d2h(dst, stage, n * sizeof(double)));
+  return 0;
+}

@@ -207,6 +207,7 @@ void hpgmg_level_release(level_type *L) {
   if (B->d_box_low) hpgmg_hip_free(B->d_box_low);
   if (B->d_box_nbr) hpgmg_hip_free(B->d_box_nbr);
   if (B->krylov_pinned) hpgmg_hip_host_free(B->krylov_pinned);
+  if (B->dense_stage) hpgmg_hip_free(B->dense_stage);
   if (B->pair_scratch) hpgmg_hip_free(B->pair_scratch);
   if (B->coef32) hpgmg_hip_free(B->coef32);
   if (B->d_coef32_base) hpgmg_hip_free(B->d_coef32_base);

@@ -1,0 +1,242 @@
+"""User problems on dense arrays: the 7-point variable-coefficient operator  a alpha u - b div(beta grad u)  on an N^3 grid.
+
+    with Solver(256, bc="dirichlet", a=0.0, b=1.0) as s:
+        s.set_coefficients(None, beta_i, beta_j, beta_k)     # Poisson: no alpha
+        u, info = s.solve(f)                                  # one F-cycle, as the benchmark
+
+Arrays are C-contiguous float64 indexed [k][j][i]; cell (i,j,k) has its centre at ((i+1/2)h, (j+1/2)h, (k+1/2)h).  f, alpha, u, u0 and x
+are (N,N,N).  Dirichlet (homogeneous): beta_i is (N,N,N+1), beta_i[k][j][i] on the face between cells i-1 and i (i = 0 and i = N are the
+domain faces); beta_j is (N,N+1,N), beta_k (N+1,N,N).  Periodic: all three are (N,N,N), face N being face 0.
+
+NumPy arrays take the host path.  torch tensors on the library's GPU (float64, contiguous) are read and written in place, and results come
+back as tensors on that device.  torch must be imported before this package loads its libraries: both bring a HIP runtime
+(libamdhip64.so.7), and a device pointer is only valid inside the runtime that made it.  The C entry points are hpgmg_user_* of
+include/hpgmg_fv.h.
+"""
+import ctypes
+from dataclasses import dataclass
+
+import numpy as np
+
+import hpgmg_amd as H
+
+_BC = {"dirichlet": H.BC_DIRICHLET, "periodic": H.BC_PERIODIC}
+_SMOOTHER = {"cheby": H.SMOOTH_CHEBY, "chebyshev": H.SMOOTH_CHEBY, "gsrb": H.SMOOTH_GSRB, "jacobi": H.SMOOTH_JACOBI}
+_OPERATOR = {"7pt": H.OP_7PT, "27pt": H.OP_27PT, "fv4": H.OP_FV4, "fv2": H.OP_FV2}
+_METHOD = {"fmg": H.USER_FMG, "mg": H.USER_MG}
+_STATUS = {H.USER_BAD_ARGUMENT: "refused by the library", H.USER_CONFLICT: "the process is configured for another live solver",
+           H.USER_MULTI_RANK: "only one rank is supported", H.USER_NOT_FINITE: "holds a value that is not finite",
+           H.USER_OUT_OF_RANGE: "is out of range (beta must be > 0, alpha >= 0)",
+           H.USER_NOT_READY: "no valid coefficients / right-hand side (an earlier call was refused)",
+           H.USER_UNSUPPORTED: "only the 7-point operator is supported"}
+
+
+@dataclass
+class SolveInfo:
+    residual: float      # |f - A u|_inf (f after the mean shift)
+    norm_f: float        # |f|_inf
+    vcycles: int         # V-cycles run from the finest level (an F-cycle ends with one)
+    converged: bool      # residual < rtol * norm_f
+    mean_shift: float    # subtracted from f (periodic without an a alpha term), else 0.0
+
+
+def hip_runtimes_mapped():
+    """Paths of the libamdhip64 copies mapped into this process."""
+    paths = set()
+    with open("/proc/self/maps") as f:
+        for line in f:
+            parts = line.split()
+            if len(parts) >= 6 and "libamdhip64" in parts[-1]:
+                paths.add(parts[-1])
+    return sorted(paths)
+
+
+def check_single_hip_runtime():
+    """Raise unless at most one HIP runtime is mapped (torch's bundled copy and the system one have the same soname; which one the
+    project's libraries bind to depends on which was loaded first)."""
+    runtimes = hip_runtimes_mapped()
+    if len(runtimes) > 1:
+        raise RuntimeError("import torch before hpgmg_amd loads its libraries: this process has two HIP runtimes mapped "
+                           f"({', '.join(runtimes)}) and a device pointer of one is not valid in the other")
+
+
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+class Solver:
+    """One user problem.  `lib` is the driver library to run on (default: the HIP build, hpgmg_amd.load_driver())."""
+
+    def __init__(self, n, box_dim=None, bc="dirichlet", smoother="cheby", a=0.0, b=1.0, h=None, operator="7pt", lib=None, verbose=False):
+        if bc not in _BC:
+            raise ValueError(f"bc: {bc!r} is not one of {sorted(_BC)}")
+        if smoother not in _SMOOTHER:
+            raise ValueError(f"smoother: {smoother!r} is not one of {sorted(_SMOOTHER)}")
+        if operator not in _OPERATOR:
+            raise ValueError(f"operator: {operator!r} is not one of {sorted(_OPERATOR)}")
+        self.lib = lib if lib is not None else H.load_driver()
+        self.hip = self.lib.hpgmg_backend_name() == b"hip"
+        self.n, self.bc, self.a, self.b = int(n), bc, float(a), float(b)
+        self._ptr = None
+        out = ctypes.c_void_p()
+        st = self.lib.hpgmg_user_create(self.n, int(box_dim or 0), _BC[bc], _OPERATOR[operator], _SMOOTHER[smoother], self.a, self.b,
+                                        float(h or 0.0), ctypes.byref(out))
+        self._check(st, "operator" if st == H.USER_UNSUPPORTED else "n, box_dim, a, b or h")
+        self._ptr = out.value
+        if verbose:
+            self.lib.hpgmg_user_set_verbose(self._ptr, 1)
+
+    # ---- shapes
+    def _face_shape(self, axis):
+        n = self.n
+        shape = [n, n, n]
+        if self.bc == "dirichlet":
+            shape[2 - axis] += 1
+        return tuple(shape)
+
+    # ---- arguments
+    def _check(self, st, name):
+        if st != H.USER_OK:
+            raise ValueError(f"{name}: {_STATUS.get(st, f'status {st}')}")
+
+    def _device_ok(self, x, name):
+        import torch
+        check_single_hip_runtime()
+        if not self.hip:
+            raise ValueError(f"{name}: a tensor needs the HIP library (this solver runs on {self.lib.hpgmg_backend_name().decode()})")
+        if not x.is_cuda:
+            raise ValueError(f"{name}: a tensor must be on the GPU (pass a NumPy array for host data)")
+        if x.device.index not in (None, torch.cuda.current_device()):
+            raise ValueError(f"{name}: the tensor is on {x.device}, the library on cuda:{torch.cuda.current_device()}")
+
+    def _arg(self, x, shape, name, kind=None):
+        """(pointer, where, kind) of an input array; kind = 'numpy' / 'torch' must match the other arrays of the call."""
+        if _is_tensor(x):
+            import torch
+            if x.dtype != torch.float64:
+                raise ValueError(f"{name}: dtype {x.dtype}, expected torch.float64")
+            if tuple(x.shape) != shape:
+                raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {shape}")
+            if not x.is_contiguous():
+                raise ValueError(f"{name}: the tensor is not contiguous")
+            self._device_ok(x, name)
+            this = "torch"
+            ptr, where = x.data_ptr(), H.WHERE_PLUGIN
+        elif isinstance(x, np.ndarray):
+            if x.dtype != np.float64:
+                raise ValueError(f"{name}: dtype {x.dtype}, expected float64")
+            if x.shape != shape:
+                raise ValueError(f"{name}: shape {x.shape}, expected {shape}")
+            if not x.flags.c_contiguous:
+                raise ValueError(f"{name}: the array is not C-contiguous")
+            this = "numpy"
+            ptr, where = x.ctypes.data, H.WHERE_HOST
+        else:
+            raise ValueError(f"{name}: expected a NumPy array or a torch tensor, got {type(x).__name__}")
+        if kind is not None and kind != this:
+            raise ValueError(f"{name}: a {this} array among {kind} arrays (one call takes host or device arrays, not both)")
+        return ptr, where, this
+
+    @staticmethod
+    def _sync_torch(kind):
+        if kind == "torch":
+            import torch
+            torch.cuda.current_stream().synchronize()
+
+    def _first_bad(self, named, st):
+        """Which argument a refused pack was about (the library reports the status, not the array)."""
+        for name, x, low, strict in named:
+            v = x.detach().cpu().numpy() if _is_tensor(x) else x
+            if not np.isfinite(v).all():
+                return name
+            if st == H.USER_OUT_OF_RANGE and ((strict and not (v > low).all()) or (not strict and not (v >= low).all())):
+                return name
+        return ", ".join(nm for nm, *_ in named)
+
+    def _out(self, out, kind, like, name):
+        if out is None:
+            if kind == "torch":
+                import torch
+                return torch.empty((self.n,) * 3, dtype=torch.float64, device=like.device)
+            return np.empty((self.n,) * 3, dtype=np.float64)
+        self._arg(out, (self.n,) * 3, name, kind)
+        return out
+
+    # ---- the API
+    def set_coefficients(self, alpha, beta_i, beta_j, beta_k):
+        """alpha: (N,N,N) or None for Poisson (a = 0); beta_*: the face arrays described in the module docstring."""
+        if (alpha is None) != (self.a == 0.0):
+            raise ValueError("alpha: required when a != 0 (Helmholtz), must be None when a == 0 (Poisson)")
+        pi, where, kind = self._arg(beta_i, self._face_shape(0), "beta_i")
+        pj, _, _ = self._arg(beta_j, self._face_shape(1), "beta_j", kind)
+        pk, _, _ = self._arg(beta_k, self._face_shape(2), "beta_k", kind)
+        pa = self._arg(alpha, (self.n,) * 3, "alpha", kind)[0] if alpha is not None else None
+        self._sync_torch(kind)
+        st = self.lib.hpgmg_user_set_coefficients(self._ptr, pa, pi, pj, pk, where)
+        if st in (H.USER_NOT_FINITE, H.USER_OUT_OF_RANGE):
+            named = [("beta_i", beta_i, 0.0, True), ("beta_j", beta_j, 0.0, True), ("beta_k", beta_k, 0.0, True)]
+            if alpha is not None:
+                named.append(("alpha", alpha, 0.0, False))
+            self._check(st, self._first_bad(named, st))
+        self._check(st, "alpha, beta_i, beta_j, beta_k")
+
+    def set_rhs(self, f):
+        """Packs f; returns the mean subtracted from it (periodic without an a alpha term), else 0.0."""
+        p, where, kind = self._arg(f, (self.n,) * 3, "f")
+        self._sync_torch(kind)
+        shift = ctypes.c_double(0.0)
+        self._check(self.lib.hpgmg_user_set_rhs(self._ptr, p, where, ctypes.byref(shift)), "f")
+        return shift.value
+
+    def solve(self, f, method="fmg", rtol=1e-10, u0=None, out=None):
+        """u, SolveInfo.  method 'fmg': one F-cycle (the benchmark's solve); 'mg': V-cycles until |f - A u| < rtol |f|.
+        u0: start from it (u = u0 + e, the correction solved with V-cycles; method is then not used)."""
+        if method not in _METHOD:
+            raise ValueError(f"method: {method!r} is not one of {sorted(_METHOD)}")
+        if not rtol > 0.0:
+            raise ValueError(f"rtol: {rtol!r} must be > 0")
+        _, _, kind = self._arg(f, (self.n,) * 3, "f")
+        p0 = self._arg(u0, (self.n,) * 3, "u0", kind)[0] if u0 is not None else None
+        out = self._out(out, kind, f, "out")
+        self.set_rhs(f)
+        info = H.UserInfo()
+        self._sync_torch(kind)
+        self._check(self.lib.hpgmg_user_solve(self._ptr, _METHOD[method], float(rtol), p0,
+                                              H.WHERE_PLUGIN if kind == "torch" else H.WHERE_HOST, ctypes.byref(info)), "u0")
+        self.get_solution(out)
+        return out, SolveInfo(info.norm_of_residual, info.norm_of_f, info.vcycles, bool(info.converged), info.mean_shift)
+
+    def get_solution(self, out=None):
+        """The last solution into `out` (NumPy array or tensor), or a new NumPy array."""
+        if out is None:
+            out = np.empty((self.n,) * 3, dtype=np.float64)
+        p, where, kind = self._arg(out, (self.n,) * 3, "out")
+        self._sync_torch(kind)
+        self._check(self.lib.hpgmg_user_get_solution(self._ptr, p, where), "out")
+        return out
+
+    def apply(self, x, out=None):
+        """y = A x."""
+        px, where, kind = self._arg(x, (self.n,) * 3, "x")
+        out = self._out(out, kind, x, "out")
+        py = self._arg(out, (self.n,) * 3, "out", kind)[0]
+        self._sync_torch(kind)
+        self._check(self.lib.hpgmg_user_apply(self._ptr, px, py, where), "x")
+        return out
+
+    def close(self):
+        if self._ptr is not None:
+            self.lib.hpgmg_user_destroy(self._ptr)
+            self._ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

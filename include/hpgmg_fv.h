@@ -54,6 +54,40 @@ void   hpgmg_solver_richardson(hpgmg_solver *s, double out[2]);
 /* the reference's whole main(): prints the same report; returns 0 */
 int hpgmg_fv_main(int argc, char **argv);
 
+/* ---- user problems on dense arrays: the 7-point variable-coefficient operator  a alpha u - b div(beta grad u)  on an N^3 grid, one rank ----
+ * Cell (i,j,k) has its centre at ((i+1/2)h, (j+1/2)h, (k+1/2)h).  Arrays are C-contiguous float64 indexed [k][j][i] (i fastest).  f, alpha, u,
+ * u0, x, y: (N,N,N).  Dirichlet (homogeneous; the ghost rule of boundary_fd.c p1, as the plugin applies it): beta_i (N,N,N+1) with
+ * beta_i[k][j][i] on the face between cells i-1 and i, so i = 0 and i = N are the domain faces; beta_j (N,N+1,N), beta_k (N+1,N,N).
+ * Periodic: all three (N,N,N) (face N is face 0).  Poisson is a = 0 and has no alpha.  where: HPGMG_WHERE_HOST (host memory) or
+ * HPGMG_WHERE_PLUGIN (the plugin's memory: a device array in the HIP build, read and written in place).  Every call returns HPGMG_USER_*.
+ * The operator configuration is process-wide (hpgmg_configure): create refuses one that differs from a live user solver's. */
+enum { HPGMG_USER_OK = 0, HPGMG_USER_BAD_ARGUMENT = -1, HPGMG_USER_CONFLICT = -2, HPGMG_USER_MULTI_RANK = -3, HPGMG_USER_NOT_FINITE = -4,
+       HPGMG_USER_OUT_OF_RANGE = -5, HPGMG_USER_NOT_READY = -6, HPGMG_USER_UNSUPPORTED = -7 };
+enum { HPGMG_USER_FMG = 0, HPGMG_USER_MG = 1 };
+typedef struct hpgmg_user_solver hpgmg_user_solver;
+typedef struct {
+  double norm_of_residual;   /* |f - A u|_inf (f after the mean shift) */
+  double norm_of_f;          /* |f|_inf */
+  double mean_shift;         /* what set_rhs subtracted from f (periodic without an a alpha term), else 0 */
+  int    vcycles;            /* V-cycles run from the finest level (an F-cycle ends with one) */
+  int    converged;          /* norm_of_residual < rtol * norm_of_f */
+} hpgmg_user_info;
+/* op must be HPGMG_OP_7PT (others: HPGMG_USER_UNSUPPORTED); box_dim <= 0: the largest power of two <= 128 dividing n; h <= 0: 1/n.
+ * Configures {7pt, smoother, a != 0, variable coefficients}, sets every beta (and alpha) to 1 and f to 0, builds the hierarchy. */
+int  hpgmg_user_create(int n, int box_dim, int bc, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out);
+void hpgmg_user_destroy(hpgmg_user_solver *s);
+void hpgmg_user_set_verbose(hpgmg_user_solver *s, int on);      /* 1: print what the solver prints (default 0: nothing) */
+hpgmg_solver *hpgmg_user_solver_of(hpgmg_user_solver *s);       /* its levels and hierarchy (hpgmg_solver_level, hpgmg_solver_mg) */
+/* pack the coefficients (beta > 0, alpha >= 0, all finite), rebuild the operator on the finest level, then MGRebuildCoarse */
+int  hpgmg_user_set_coefficients(hpgmg_user_solver *s, const double *alpha, const double *beta_i, const double *beta_j, const double *beta_k, int where);
+/* pack f (finite); periodic without an a alpha term: subtract its mean, returned in *mean_shift */
+int  hpgmg_user_set_rhs(hpgmg_user_solver *s, const double *f, int where, double *mean_shift);
+/* HPGMG_USER_FMG: what the benchmark runs (zero u, FMGSolve); HPGMG_USER_MG: V-cycles until |f - A u| < rtol |f| (MGSolve).
+ * u0 != NULL: u = u0 + e, where V-cycles solve A e = f - A u0 until |f - A u| < rtol |f| (method is then not read). */
+int  hpgmg_user_solve(hpgmg_user_solver *s, int method, double rtol, const double *u0, int where, hpgmg_user_info *info);
+int  hpgmg_user_get_solution(hpgmg_user_solver *s, double *u, int where);
+int  hpgmg_user_apply(hpgmg_user_solver *s, const double *x, double *y, int where);   /* y = A x (apply_op) */
+
 /* ---- small accessors so a ctypes caller never needs the struct layouts ---- */
 enum { HPGMG_INFO_DIM = 0, HPGMG_INFO_BOX_DIM, HPGMG_INFO_GHOSTS, HPGMG_INFO_JSTRIDE, HPGMG_INFO_KSTRIDE,
        HPGMG_INFO_VOLUME, HPGMG_INFO_NUM_MY_BOXES, HPGMG_INFO_NUM_VECTORS, HPGMG_INFO_BOXES_IN_I,

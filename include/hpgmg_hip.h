@@ -345,6 +345,11 @@ int hpgmg_hip_sum(const hpgmg_hip_level *L, int id, double *out);               
  * id_A[mm] * id_B[nn] for nn >= mm, mirrored to C_host[nn * cols + mm] where that entry exists.  Per box one chain in k, j, i order, products first;
  * box partials added in box order (NOT the tile order above).  One launch; synchronises.  rows, cols <= 32; the ids must name vectors of the level. */
 int hpgmg_hip_gram(const hpgmg_hip_level *L, const int *id_A, int rows, const int *id_B, int cols, double *C_host);
+/* dense arrays <-> vector id (include/hpgmg_operators.h hpgmg_dense_pack / unpack; kernels/dense_io.hip).  src / dst are DEVICE arrays.
+ * pack: a (nk, nj, ni) array, each extent the level's global one or one more (a Dirichlet face array); writes every double of every box
+ * and returns the validation bits in *status (HPGMG_DENSE_*; check = HPGMG_DENSE_CHECK_*).  Both synchronise. */
+int hpgmg_hip_dense_pack(const hpgmg_hip_level *L, int id, const double *src, int ni, int nj, int nk, int check, int *status);
+int hpgmg_hip_dense_unpack(const hpgmg_hip_level *L, int id, double *dst);
 
 /* ---- operators/rebuild.c:47-208 black-box rebuild: accumulate one colouring (x = 0/1 pattern, ghosts
  *      already exchanged / BCs applied) into Aii and sum|Aij|, then turn them into Dinv, L1inv, lambda_max ---- */

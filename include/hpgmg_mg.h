@@ -28,6 +28,9 @@ typedef struct {
 
 void MGBuild(mg_type *all_grids, level_type *fine_grid, double a, double b, int minCoarseGridDim);
 void MGDestroy(mg_type *all_grids);
+/* MGBuild's last steps: rebuild_operator(level l, level l-1) for every coarser level, then must_subtract_mean of every level.  MGBuild runs it
+ * once; a caller that gives the finest level new coefficients runs rebuild_operator(level 0, NULL) and then this. */
+void MGRebuildCoarse(mg_type *all_grids, double a, double b);
 void MGVCycle(mg_type *all_grids, int e_id, int R_id, double a, double b, int level);
 void MGSolve(mg_type *all_grids, int onLevel, int u_id, int F_id, double a, double b, double rtol);
 void FMGSolve(mg_type *all_grids, int onLevel, int u_id, int F_id, double a, double b, double rtol);

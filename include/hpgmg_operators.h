@@ -115,6 +115,24 @@ void    hpgmg_vector_copy(double *dst, const double *src, size_t num_doubles);
 /* host<->plugin staging, used by tests and by initialize_problem */
 void    hpgmg_vector_upload(double *dst_plugin, const double *src_host, size_t num_doubles);
 void    hpgmg_vector_download(double *dst_host, const double *src_plugin, size_t num_doubles);
+/* Dense N^3 arrays <-> vector `id` of a level (one rank; the user-problem API of include/hpgmg_fv.h).  A dense array is C-contiguous
+ * float64 indexed [k][j][i] (i fastest); cell (i,j,k) is the cell whose global index is (i,j,k).  Layout HPGMG_DENSE_CELL: (N,N,N).
+ * HPGMG_DENSE_FACE_I/J/K: the LOW face of cell (i,j,k) along that axis (hpgmg_level.h); with Dirichlet boundaries the array is one longer along
+ * that axis (beta_i is (N,N,N+1)), its entry N being the high domain face; with periodic ones it is (N,N,N) (face N is face 0).
+ * pack: every padded cell of every box is written -- the array's value where the array determines it (interior cells; for a Dirichlet face
+ * array also the high ghost layer along its axis of the boxes on the domain's high face), 0.0 elsewhere; exchange_boundary fills the ghost
+ * zones afterwards.  Each value is checked while it is copied: the result is 0, or HPGMG_DENSE_NOT_FINITE | HPGMG_DENSE_OUT_OF_RANGE (check
+ * POSITIVE: v > 0, NONNEGATIVE: v >= 0) -- the vector is then written but not to be used -- or -1 for an argument the plugin refuses.
+ * unpack: the interior cells of the vector into a (N,N,N) array; nothing else of the array is written.  where: HPGMG_WHERE_HOST = the array
+ * is in host memory, HPGMG_WHERE_PLUGIN = in the plugin's memory (device memory in the HIP build; read and written in place).
+ * host/driver.c holds weak host defaults (box by box through hpgmg_vector_upload / download: the CPU oracle); the HIP plugin overrides them
+ * with one launch per array (kernels/dense_io.hip). */
+enum { HPGMG_DENSE_CELL = 0, HPGMG_DENSE_FACE_I = 1, HPGMG_DENSE_FACE_J = 2, HPGMG_DENSE_FACE_K = 3 };
+enum { HPGMG_DENSE_CHECK_FINITE = 0, HPGMG_DENSE_CHECK_POSITIVE = 1, HPGMG_DENSE_CHECK_NONNEGATIVE = 2 };
+enum { HPGMG_DENSE_NOT_FINITE = 1, HPGMG_DENSE_OUT_OF_RANGE = 2 };
+enum { HPGMG_WHERE_HOST = 0, HPGMG_WHERE_PLUGIN = 1 };
+int     hpgmg_dense_pack(level_type *level, int id, const double *src, int where, int layout, int check);
+int     hpgmg_dense_unpack(level_type *level, int id, double *dst, int where);
 /* Launch-bound stretches of a cycle (everything done on levels of <= 64^3 cells between two
  * bottom solves) are bracketed by the cycle driver as a SEGMENT with a key that repeats every
  * solve, so the HIP plugin can capture it once into a hipGraph and replay it.  Plugins without
