@@ -147,6 +147,17 @@ def _declare_driver_api(lib):
         "hpgmg_user_solve": (c_int, [vp, c_int, c_dbl, vp, c_int, P(UserInfo)]),
         "hpgmg_user_get_solution": (c_int, [vp, vp, c_int]),
         "hpgmg_user_apply": (c_int, [vp, vp, vp, c_int]),
+        "hpgmg_user_set_rhs_dirichlet": (c_int, [vp, vp, vp, c_int, P(c_dbl)]),
+        "hpgmg_user_apply_dirichlet": (c_int, [vp, vp, vp, vp, c_int]),
+        "hpgmg_dense_pack_lifted": (c_int, [vp, c_int, vp, c_int, vp, c_dbl]),
+        "hpgmg_boundary_flux": (c_int, [vp, vp, vp, c_dbl]),
+        "hpgmg_boundary_restrict": (None, [vp, vp, vp, vp]),
+        "hpgmg_boundary_lift": (None, [vp, c_int, vp, vp, c_dbl]),
+        "hpgmg_vector_alloc": (vp, [ctypes.c_size_t]),
+        "hpgmg_vector_free": (None, [vp]),
+        "hpgmg_vector_copy": (None, [vp, vp, ctypes.c_size_t]),
+        "hpgmg_vector_upload": (None, [vp, vp, ctypes.c_size_t]),
+        "hpgmg_vector_download": (None, [vp, vp, ctypes.c_size_t]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -11,6 +11,7 @@
 #include <string.h>
 #include <time.h>
 #include <math.h>
+#include <stdint.h>
 #include "hpgmg_fv.h"
 #ifdef _OPENMP
 #include <omp.h>
@@ -201,6 +202,209 @@ __attribute__((weak)) int hpgmg_dense_unpack(level_type *L, int id, double *dst,
   return 0;
 }
 
+/* ------------------------------------------------------------------ boundary values: host defaults (include/hpgmg_operators.h)
+ * Box by box through hpgmg_vector_upload / download, weak like the dense pair above (the HIP plugin: host/plugin_dense.c).  The domain is the
+ * user problems' cube of n = dim.i cells per side. */
+static int bnd_touches(int n, int face, int gi, int gj, int gk) {          /* cell (gi,gj,gk) lies on domain face `face` */
+  const int c = face < 2 ? gi : face < 4 ? gj : gk;
+  return (face & 1) ? c == n - 1 : c == 0;
+}
+static size_t bnd_entry(int n, int face, int gi, int gj, int gk) {         /* its entry in a 6 x n x n boundary array */
+  const int q = face < 4 ? gk : gj, p = face < 2 ? gj : gi;
+  return ((size_t)face * n + q) * n + p;
+}
+static int bnd_box_on_domain_face(const level_type *L, const box_type *B) {
+  const int n = L->dim.i, d = L->box_dim;
+  return B->low.i == 0 || B->low.j == 0 || B->low.k == 0 || B->low.i + d == n || B->low.j + d == n || B->low.k + d == n;
+}
+/* beta of domain face `face` of the box cell at padded offset ijk */
+static double bnd_beta(const double *bi, const double *bj, const double *bk, int face, int ijk, int jS, int kS) {
+  switch (face) {
+    case 0: return bi[ijk];  case 1: return bi[ijk + 1];
+    case 2: return bj[ijk];  case 3: return bj[ijk + jS];
+    case 4: return bk[ijk];  default: return bk[ijk + kS];
+  }
+}
+static double bnd_weight(const level_type *L, double b) { return (2.0 * b) * (1.0 / (L->h * L->h)); }
+/* S(c) of hpgmg_boundary_lift: the four finer entries under each face entry of coarse cell (gi,gj,gk), faces in order */
+static double bnd_fine_sum(int n, const double *phi_f, int gi, int gj, int gk) {
+  double S = 0.0;
+  int face;
+  for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
+    const int q = face < 4 ? gk : gj, p = face < 2 ? gj : gi;
+    const double *e = phi_f + ((size_t)face * 2 * n + 2 * q) * 2 * n + 2 * p;
+    S = S + (((e[0] + e[1]) + e[2 * n]) + e[2 * n + 1]);
+  }
+  return S;
+}
+static double *bnd_download(const double *src, size_t n) {
+  double *h = (double *)malloc(n * sizeof(double));
+  hpgmg_vector_download(h, src, n);
+  return h;
+}
+
+__attribute__((weak)) int hpgmg_dense_pack_lifted(level_type *L, int id, const double *f, int where, const double *g, double b) {
+  if (!g || L->boundary_condition.type != BC_DIRICHLET) return -1;
+  const int st = hpgmg_dense_pack(L, id, f, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE);
+  if (st < 0) return st;
+  const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const double w = bnd_weight(L, b);
+  double *gh = bnd_download(g, (size_t)6 * n * n);
+  double *v = (double *)malloc((size_t)L->box_volume * 4 * sizeof(double));
+  double *bi = v + L->box_volume, *bj = bi + L->box_volume, *bk = bj + L->box_volume;
+  int box, i, j, k, face, bad = 0;
+  for (box = 0; box < L->num_my_boxes; box++) {
+    const box_type *B = &L->my_boxes[box];
+    if (!bnd_box_on_domain_face(L, B)) continue;
+    hpgmg_vector_download(v, B->vectors[id], (size_t)L->box_volume);
+    hpgmg_vector_download(bi, B->vectors[VECTOR_BETA_I], (size_t)L->box_volume);
+    hpgmg_vector_download(bj, B->vectors[VECTOR_BETA_J], (size_t)L->box_volume);
+    hpgmg_vector_download(bk, B->vectors[VECTOR_BETA_K], (size_t)L->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      double T = 0.0;
+      int on = 0;
+      for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
+        const double gv = gh[bnd_entry(n, face, gi, gj, gk)];
+        if (!isfinite(gv)) bad = 1;
+        T = T + (w * bnd_beta(bi, bj, bk, face, ijk, jS, kS)) * gv;
+        on = 1;
+      }
+      if (on) v[ijk] = v[ijk] + T;
+    }
+    hpgmg_vector_upload(B->vectors[id], v, (size_t)L->box_volume);
+  }
+  free(v); free(gh);
+  return st | (bad ? HPGMG_DENSE_NOT_FINITE : 0);
+}
+
+__attribute__((weak)) int hpgmg_boundary_flux(level_type *L, double *phi, const double *g, double b) {
+  const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t len = (size_t)6 * n * n;
+  const double w = bnd_weight(L, b);
+  double *gh = bnd_download(g, len), *ph = (double *)calloc(len, sizeof(double));
+  double *bi = (double *)malloc((size_t)L->box_volume * 3 * sizeof(double)), *bj = bi + L->box_volume, *bk = bj + L->box_volume;
+  int box, i, j, k, face, bad = 0;
+  size_t e;
+  for (e = 0; e < len; e++) if (!isfinite(gh[e])) bad = 1;
+  for (box = 0; box < L->num_my_boxes; box++) {
+    const box_type *B = &L->my_boxes[box];
+    if (!bnd_box_on_domain_face(L, B)) continue;
+    hpgmg_vector_download(bi, B->vectors[VECTOR_BETA_I], (size_t)L->box_volume);
+    hpgmg_vector_download(bj, B->vectors[VECTOR_BETA_J], (size_t)L->box_volume);
+    hpgmg_vector_download(bk, B->vectors[VECTOR_BETA_K], (size_t)L->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
+        e = bnd_entry(n, face, gi, gj, gk);
+        ph[e] = (w * bnd_beta(bi, bj, bk, face, ijk, jS, kS)) * gh[e];
+      }
+    }
+  }
+  hpgmg_vector_upload(phi, ph, len);
+  free(bi); free(ph); free(gh);
+  return bad ? HPGMG_DENSE_NOT_FINITE : 0;
+}
+
+__attribute__((weak)) void hpgmg_boundary_restrict(level_type *Lc, double *g_c, level_type *Lf, const double *g_f) {
+  const int nc = Lc->dim.i, nf = Lf->dim.i;
+  double *gf = bnd_download(g_f, (size_t)6 * nf * nf), *gc = (double *)malloc((size_t)6 * nc * nc * sizeof(double));
+  int face, q, p;
+  for (face = 0; face < 6; face++) for (q = 0; q < nc; q++) for (p = 0; p < nc; p++) {
+    const double *e = gf + ((size_t)face * nf + 2 * q) * nf + 2 * p;
+    gc[((size_t)face * nc + q) * nc + p] = (e[0] + e[1] + e[nf] + e[nf + 1]) * 0.25;
+  }
+  hpgmg_vector_upload(g_c, gc, (size_t)6 * nc * nc);
+  free(gc); free(gf);
+}
+
+__attribute__((weak)) void hpgmg_boundary_lift(level_type *L, int id, const double *phi, const double *phi_fine, double sign) {
+  const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  double *ph = bnd_download(phi, (size_t)6 * n * n), *pf = phi_fine ? bnd_download(phi_fine, (size_t)24 * n * n) : NULL;
+  double *v = (double *)malloc((size_t)L->box_volume * sizeof(double));
+  int box, i, j, k, face;
+  for (box = 0; box < L->num_my_boxes; box++) {
+    const box_type *B = &L->my_boxes[box];
+    if (!bnd_box_on_domain_face(L, B)) continue;
+    hpgmg_vector_download(v, B->vectors[id], (size_t)L->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      double T = 0.0;
+      int on = 0;
+      for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) { T = T + ph[bnd_entry(n, face, gi, gj, gk)]; on = 1; }
+      if (!on) continue;
+      if (pf) T = T - 0.125 * bnd_fine_sum(n, pf, gi, gj, gk);
+      v[ijk] = v[ijk] + sign * T;
+    }
+    hpgmg_vector_upload(B->vectors[id], v, (size_t)L->box_volume);
+  }
+  free(v); free(pf); free(ph);
+}
+
+/* delta of the ghost at coarse (ci,cj,ck) (hpgmg_boundary_interp): 2 g on a face, the wall-by-wall linear rule on an edge
+ * or corner (exact for u linear near them).  BND_AT(face, i, j, k): the entry of `face` at the in-range cell (i, j, k) (its own axis not read). */
+#define BND_AT(f, i, j, k) g[((size_t)(f) * n + ((f) < 4 ? (k) : (j))) * n + ((f) < 2 ? (j) : (i))]
+static double bnd_ghost_delta(int n, const double *g, int ci, int cj, int ck) {
+  const int q[3] = { ci, cj, ck };
+  int out[3], P[3], step[3], face[3], a, m = 0;
+  for (a = 0; a < 3; a++) {
+    out[a] = q[a] < 0 || q[a] >= n;
+    P[a] = q[a] < 0 ? 0 : q[a] >= n ? n - 1 : q[a];
+    step[a] = q[a] < 0 ? 1 : -1;                               /* one cell inward */
+    face[a] = 2 * a + (q[a] >= n);
+    m += out[a];
+  }
+  if (m == 1) { a = out[0] ? 0 : out[1] ? 1 : 2; return 2.0 * BND_AT(face[a], P[0], P[1], P[2]); }
+  if (n < 2) return m == 3 ? ((BND_AT(face[0], P[0], P[1], P[2]) + BND_AT(face[1], P[0], P[1], P[2])) + BND_AT(face[2], P[0], P[1], P[2])) * (2.0 / 3.0) : 0.0;
+  if (m == 2) {                      /* the outside axes x < y: each wall's entry next to the edge minus the one a cell further along the other wall */
+    const int x = out[0] ? 0 : 1, y = out[2] ? 2 : 1;
+    const int yi = P[0] + (y == 0) * step[0], yj = P[1] + (y == 1) * step[1], yk = P[2] + (y == 2) * step[2];
+    const int xi = P[0] + (x == 0) * step[0], xj = P[1] + (x == 1) * step[1], xk = P[2] + (x == 2) * step[2];
+    return (BND_AT(face[x], P[0], P[1], P[2]) - BND_AT(face[x], yi, yj, yk)) + (BND_AT(face[y], P[0], P[1], P[2]) - BND_AT(face[y], xi, xj, xk));
+  }
+  double c[3];                       /* corner: each wall's linear extrapolation to the corner point */
+  for (a = 0; a < 3; a++) {
+    const int b = a == 0 ? 1 : 0, d = a == 2 ? 1 : 2;          /* the wall's in-face axes, b < d */
+    const double g00 = BND_AT(face[a], P[0], P[1], P[2]);
+    const double g10 = BND_AT(face[a], P[0] + (b == 0) * step[0], P[1] + (b == 1) * step[1], P[2]);
+    const double g01 = BND_AT(face[a], P[0], P[1] + (d == 1) * step[1], P[2] + (d == 2) * step[2]);
+    c[a] = (2.0 * g00 - 0.5 * g10) - 0.5 * g01;
+  }
+  return ((c[0] + c[1]) + c[2]) * (2.0 / 3.0);
+}
+#undef BND_AT
+/* D(c) of hpgmg_boundary_interp for fine cell (gi,gj,gk): the p1 weights of its ghost reads times their deltas, in interpolation_p1's order */
+static double bnd_interp_delta(int nc, const double *g, int gi, int gj, int gk) {
+  const int ci = gi >> 1, cj = gj >> 1, ck = gk >> 1, di = (gi & 1) ? 1 : -1, dj = (gj & 1) ? 1 : -1, dk = (gk & 1) ? 1 : -1;
+  static const double w[8] = { 0.421875, 0.140625, 0.140625, 0.046875, 0.140625, 0.046875, 0.046875, 0.015625 };
+  static const int si[8] = { 0, 0, 0, 0, 1, 1, 1, 1 }, sj[8] = { 0, 0, 1, 1, 0, 0, 1, 1 }, sk[8] = { 0, 1, 0, 1, 0, 1, 0, 1 };
+  double D = 0.0;
+  int t;
+  for (t = 1; t < 8; t++) {
+    const int qi = ci + si[t] * di, qj = cj + sj[t] * dj, qk = ck + sk[t] * dk;
+    if (qi < 0 || qi >= nc || qj < 0 || qj >= nc || qk < 0 || qk >= nc) D = D + w[t] * bnd_ghost_delta(nc, g, qi, qj, qk);
+  }
+  return D;
+}
+
+__attribute__((weak)) void hpgmg_boundary_interp(level_type *Lf, int id, level_type *Lc, const double *g_c) {
+  const int n = Lf->dim.i, nc = Lc->dim.i, g0 = Lf->box_ghosts, dim = Lf->box_dim, jS = Lf->box_jStride, kS = Lf->box_kStride;
+  double *gc = bnd_download(g_c, (size_t)6 * nc * nc), *v = (double *)malloc((size_t)Lf->box_volume * sizeof(double));
+  int box, i, j, k;
+  for (box = 0; box < Lf->num_my_boxes; box++) {
+    const box_type *B = &Lf->my_boxes[box];
+    if (!bnd_box_on_domain_face(Lf, B)) continue;
+    hpgmg_vector_download(v, B->vectors[id], (size_t)Lf->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      if (gi > 0 && gj > 0 && gk > 0 && gi < n - 1 && gj < n - 1 && gk < n - 1) continue;
+      v[ijk] = v[ijk] + bnd_interp_delta(nc, gc, gi, gj, gk);
+    }
+    hpgmg_vector_upload(B->vectors[id], v, (size_t)Lf->box_volume);
+  }
+  free(v); free(gc);
+}
+
 /* ------------------------------------------------------------------ user problems on dense arrays (include/hpgmg_fv.h) */
 struct hpgmg_user_solver {
   hpgmg_solver s;              /* the finest level, the hierarchy, a, b, h */
@@ -208,6 +412,9 @@ struct hpgmg_user_solver {
   int x_id;                    /* the finest level's one extra vector: u0 of a warm start, the operand of apply */
   int operator_ok, rhs_ok;     /* 0 after a set_coefficients / set_rhs that was refused part way */
   double mean_shift;           /* what the last set_rhs subtracted from f */
+  int bnd;                     /* 1: f was set with boundary values (set_rhs_dirichlet): an F-cycle runs with the hook below */
+  double **bnd_g, **bnd_phi;   /* per level: the boundary values g_l and their lift flux phi_l (plugin memory; allocated on first use) */
+  double *app_g, *app_phi;     /* apply_dirichlet's g and phi on the finest level */
 };
 static int user_live = 0;              /* user solvers alive: the process-wide configuration belongs to them */
 static hpgmg_config user_cfg;
@@ -276,6 +483,12 @@ int hpgmg_user_create(int n, int box_dim, int bc, int op, int smoother, double a
 void hpgmg_user_destroy(hpgmg_user_solver *us) {
   if (!us) return;
   USER_QUIET(us);
+  if (us->bnd_g) {
+    int l;
+    for (l = 0; l < us->s.mg.num_levels; l++) { hpgmg_vector_free(us->bnd_g[l]); hpgmg_vector_free(us->bnd_phi[l]); }
+    hpgmg_vector_free(us->app_g); hpgmg_vector_free(us->app_phi);
+    free(us->bnd_g); free(us->bnd_phi);
+  }
   MGDestroy(&us->s.mg);
   destroy_level(&us->s.level_h);     /* frees the plugin's staging buffer with the level */
   USER_LOUD();
@@ -295,6 +508,7 @@ int hpgmg_user_set_coefficients(hpgmg_user_solver *us, const double *alpha, cons
   int st = 0, e;
   USER_QUIET(us);
   us->operator_ok = 0;
+  if (us->bnd) us->rhs_ok = 0;           /* the lifted f and every phi_l were made with the old beta: a new set_rhs_dirichlet is needed */
   if ((e = hpgmg_dense_pack(L, VECTOR_BETA_I, beta_i, where, HPGMG_DENSE_FACE_I, HPGMG_DENSE_CHECK_POSITIVE)) < 0) goto refused;
   st |= e;
   if ((e = hpgmg_dense_pack(L, VECTOR_BETA_J, beta_j, where, HPGMG_DENSE_FACE_J, HPGMG_DENSE_CHECK_POSITIVE)) < 0) goto refused;
@@ -321,6 +535,7 @@ int hpgmg_user_set_rhs(hpgmg_user_solver *us, const double *f, int where, double
   const int st = user_pack_status(hpgmg_dense_pack(L, VECTOR_F, f, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
   us->rhs_ok = (st == HPGMG_USER_OK);
   us->mean_shift = 0.0;
+  us->bnd = 0;
   if (us->rhs_ok && L->must_subtract_mean) {     /* periodic without an a * alpha term: only a mean-free f has a solution (hpgmg_solver_create_explicit) */
     const double avg = mean(L, VECTOR_F);
     if (avg != 0.0) { shift_vector(L, VECTOR_F, VECTOR_F, -avg); us->mean_shift = avg; }
@@ -328,6 +543,62 @@ int hpgmg_user_set_rhs(hpgmg_user_solver *us, const double *f, int where, double
   USER_LOUD();
   if (mean_shift) *mean_shift = us->mean_shift;
   return st;
+}
+
+/* boundary values: g_l and phi_l of every level, g and phi of apply_dirichlet -- 6 n_l^2 doubles each, allocated once */
+static void user_bnd_alloc(hpgmg_user_solver *us) {
+  const mg_type *G = &us->s.mg;
+  int l;
+  if (us->bnd_g) return;
+  us->bnd_g = (double **)calloc((size_t)G->num_levels, sizeof(double *));
+  us->bnd_phi = (double **)calloc((size_t)G->num_levels, sizeof(double *));
+  for (l = 0; l < G->num_levels; l++) {
+    const size_t n = (size_t)G->levels[l]->dim.i;
+    us->bnd_g[l] = hpgmg_vector_alloc(6 * n * n);
+    us->bnd_phi[l] = hpgmg_vector_alloc(6 * n * n);
+  }
+  us->app_g = hpgmg_vector_alloc((size_t)6 * us->n * us->n);
+  us->app_phi = hpgmg_vector_alloc((size_t)6 * us->n * us->n);
+}
+static void user_bnd_take(hpgmg_user_solver *us, double *dst, const double *g, int where) {     /* the caller's g into plugin memory */
+  const size_t len = (size_t)6 * us->n * us->n;
+  if (where == HPGMG_WHERE_HOST) hpgmg_vector_upload(dst, g, len);
+  else hpgmg_vector_copy(dst, g, len);
+}
+
+int hpgmg_user_set_rhs_dirichlet(hpgmg_user_solver *us, const double *f, const double *g, int where, double *mean_shift) {
+  hpgmg_solver *s = &us->s;
+  level_type *L = &s->level_h;
+  int l;
+  if (mean_shift) *mean_shift = 0.0;
+  if (!f || !g || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
+  if (us->bc != BC_DIRICHLET) return HPGMG_USER_UNSUPPORTED;
+  USER_QUIET(us);
+  user_bnd_alloc(us);
+  us->bnd = 0; us->mean_shift = 0.0;
+  user_bnd_take(us, us->bnd_g[0], g, where);
+  const int st = user_pack_status(hpgmg_dense_pack_lifted(L, VECTOR_F, f, where, us->bnd_g[0], s->b));     /* F = f + T(g) */
+  us->rhs_ok = (st == HPGMG_USER_OK);
+  if (us->rhs_ok) {                  /* g_l and phi_l of every level, for the F-cycle's right-hand-side correction */
+    for (l = 0; l < s->mg.num_levels; l++) {
+      if (l > 0) hpgmg_boundary_restrict(s->mg.levels[l], us->bnd_g[l], s->mg.levels[l - 1], us->bnd_g[l - 1]);
+      hpgmg_boundary_flux(s->mg.levels[l], us->bnd_phi[l], us->bnd_g[l], s->b);
+    }
+    us->bnd = 1;
+  }
+  USER_LOUD();
+  return st;
+}
+
+/* the F-cycle hook: R_l += T_l(g_l) - R_cell(T_{l-1}(g_{l-1})), so that R_l is the restricted f plus level l's own lift */
+static void user_bnd_restricted(const hpgmg_fmg_hook *hook, mg_type *G, int l, int R_id) {
+  const hpgmg_user_solver *us = (const hpgmg_user_solver *)hook->ctx;
+  hpgmg_boundary_lift(G->levels[l], R_id, us->bnd_phi[l], us->bnd_phi[l - 1], 1.0);
+}
+/* after interpolation_fcycle onto level l: the fine cells that read a coarse ghost get what the inhomogeneous ghost adds */
+static void user_bnd_interpolated(const hpgmg_fmg_hook *hook, mg_type *G, int l, int e_id) {
+  const hpgmg_user_solver *us = (const hpgmg_user_solver *)hook->ctx;
+  hpgmg_boundary_interp(G->levels[l], e_id, G->levels[l + 1], us->bnd_g[l + 1]);
 }
 
 int hpgmg_user_solve(hpgmg_user_solver *us, int method, double rtol, const double *u0, int where, hpgmg_user_info *info) {
@@ -353,8 +624,12 @@ int hpgmg_user_solve(hpgmg_user_solver *us, int method, double rtol, const doubl
     residual(L, VECTOR_TEMP, VECTOR_U, VECTOR_F, s->a, s->b);
     r = norm(L, VECTOR_TEMP);
   } else if (method == HPGMG_USER_FMG) {           /* the benchmark's solve (hpgmg_solver_fmg) */
+    hpgmg_fmg_hook hook = { user_bnd_restricted, user_bnd_interpolated, us, 0 };
+    hook.key = 1 + (long long)(uintptr_t)us->bnd_phi;
+    if (us->bnd) hpgmg_fmg_set_hook(&hook);
     hpgmg_fmg_zero_u_first();
     FMGSolve(&s->mg, 0, VECTOR_U, VECTOR_F, s->a, s->b, rtol);
+    hpgmg_fmg_set_hook(NULL);
     norm_of_F = hpgmg_last_solve.norm_of_F; r = hpgmg_last_solve.norm_of_residual;
   } else {
     MGSolve(&s->mg, 0, VECTOR_U, VECTOR_F, s->a, s->b, rtol);
@@ -386,6 +661,27 @@ int hpgmg_user_apply(hpgmg_user_solver *us, const double *x, double *y, int wher
   int st = user_pack_status(hpgmg_dense_pack(L, us->x_id, x, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
   if (st == HPGMG_USER_OK) {
     apply_op(L, VECTOR_R, us->x_id, s->a, s->b);      /* VECTOR_R: every solve sets it from f before reading it */
+    if (hpgmg_dense_unpack(L, VECTOR_R, y, where) < 0) st = HPGMG_USER_BAD_ARGUMENT;
+  }
+  USER_LOUD();
+  return st;
+}
+
+int hpgmg_user_apply_dirichlet(hpgmg_user_solver *us, const double *x, const double *g, double *y, int where) {
+  hpgmg_solver *s = &us->s;
+  level_type *L = &s->level_h;
+  if (!x || !g || !y || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
+  if (us->bc != BC_DIRICHLET) return HPGMG_USER_UNSUPPORTED;
+  if (!us->operator_ok) return HPGMG_USER_NOT_READY;
+  if (!user_config_ok()) return HPGMG_USER_CONFLICT;
+  USER_QUIET(us);
+  user_bnd_alloc(us);
+  user_bnd_take(us, us->app_g, g, where);
+  int st = user_pack_status(hpgmg_boundary_flux(L, us->app_phi, us->app_g, s->b));
+  if (st == HPGMG_USER_OK) st = user_pack_status(hpgmg_dense_pack(L, us->x_id, x, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
+  if (st == HPGMG_USER_OK) {
+    apply_op(L, VECTOR_R, us->x_id, s->a, s->b);
+    hpgmg_boundary_lift(L, VECTOR_R, us->app_phi, NULL, -1.0);    /* y = A0 x - T(g) */
     if (hpgmg_dense_unpack(L, VECTOR_R, y, where) < 0) st = HPGMG_USER_BAD_ARGUMENT;
   }
   USER_LOUD();

@@ -407,6 +407,8 @@ void MGResetTimers(mg_type *G) {
 #define SEGMENT_MAX_DIM 64
 static long long seg_base = 0;   /* identifies (hierarchy, start level) of the running solve */
 static int seg_counter = 0, seg_open_now = 0;
+static const hpgmg_fmg_hook *fmg_hook = NULL;     /* hpgmg_fmg_set_hook: set only during a boundary-value F-cycle */
+void hpgmg_fmg_set_hook(const hpgmg_fmg_hook *hook) { fmg_hook = hook; }
 static int is_small(const mg_type *G, int l) { return G->levels[l]->dim.i <= SEGMENT_MAX_DIM; }
 /* A captured segment bakes in the vector ids, a, b and (through the Chebyshev coefficients) every level's eigenvalue bound: all of them
  * are part of the key, so another solve on the same hierarchy with other vectors or a rebuilt operator never replays a stale graph. */
@@ -418,6 +420,7 @@ static void seg_reset(const mg_type *G, int onLevel, int u_id, int F_id, double 
 #define MIX(v) do { unsigned long long t_; double d_ = (double)(v); memcpy(&t_, &d_, sizeof t_); h ^= t_; \
     h ^= h >> 30; h *= 0xbf58476d1ce4e5b9ULL; h ^= h >> 27; h *= 0x94d049bb133111ebULL; h ^= h >> 31; } while (0)
   MIX(u_id); MIX(F_id); MIX(a); MIX(b); MIX(onLevel);
+  if (fmg_hook) MIX(fmg_hook->key);
   for (l = 0; l < G->num_levels; l++) MIX(G->levels[l]->dominant_eigenvalue_of_DinvA);
 #undef MIX
   seg_base = (long long)(((((unsigned long long)(uintptr_t)G) << 20) ^ (h << 12)) & ~0xfffULL);   /* low 12 bits: the segment counter */
@@ -652,8 +655,9 @@ static void fmg_solve_once(mg_type *G, int onLevel, int u_id, int F_id, double a
   double norm_of_F = 0.0;
   int first_restriction = onLevel;               /* the plugin may do norm, copy and the first restriction in one pass over F */
   int norm_deferred = 0;                         /* norm(F) is used only by the check at the end: the plugin may let the host run on and hand it over there */
-  if (onLevel < bottom && hpgmg_norm_scale_restrict_fused_deferred(L, F_id, R_id, G->levels[onLevel + 1])) { first_restriction = onLevel + 1; norm_deferred = 1; }
-  else if (onLevel < bottom && hpgmg_norm_scale_restrict_fused(L, F_id, R_id, G->levels[onLevel + 1], &norm_of_F)) first_restriction = onLevel + 1;
+  const hpgmg_fmg_hook *hook = fmg_hook;         /* a boundary-value F-cycle: every restriction of R is followed by the hook's correction */
+  if (!hook && onLevel < bottom && hpgmg_norm_scale_restrict_fused_deferred(L, F_id, R_id, G->levels[onLevel + 1])) { first_restriction = onLevel + 1; norm_deferred = 1; }
+  else if (!hook && onLevel < bottom && hpgmg_norm_scale_restrict_fused(L, F_id, R_id, G->levels[onLevel + 1], &norm_of_F)) first_restriction = onLevel + 1;
   else {
     norm_of_F = norm(L, F_id);
     scale_vector(L, R_id, 1.0, F_id);
@@ -663,13 +667,14 @@ static void fmg_solve_once(mg_type *G, int onLevel, int u_id, int F_id, double a
   /* the plugin may run everything below some small level -- the rest of the restrictions, the bottom solve and the climb back up to
    * that level, interpolation_fcycle + V-cycle per level -- as one fused operation */
   int ftail = bottom;
-  for (l = onLevel; l < bottom; l++) if (is_small(G, l) && hpgmg_vcycle_legs_fused(&G->levels[l], G->num_levels - l, e_id, R_id, a, b, HPGMG_LEG_FCYCLE_TAIL_ASK)) { ftail = l; break; }
+  for (l = onLevel; l < bottom && !hook; l++) if (is_small(G, l) && hpgmg_vcycle_legs_fused(&G->levels[l], G->num_levels - l, e_id, R_id, a, b, HPGMG_LEG_FCYCLE_TAIL_ASK)) { ftail = l; break; }
 
   if (u_to_zero && ftail <= onLevel) { zero_vector(L, u_id); u_to_zero = 0; }      /* no interpolation onto this level will come: zero it now, as the caller would have */
   for (l = first_restriction; l < ftail; l++) {           /* carry the right-hand side down */
     if (is_small(G, l)) seg_open();
     t = hpgmg_tick_begin(G->levels[l], &G->levels[l]->timers.Total, "restrict R");
     restriction(G->levels[l + 1], R_id, G->levels[l], R_id, RESTRICT_CELL);
+    if (hook) hook->rhs_restricted(hook, G, l + 1, R_id);
     hpgmg_tick_end(t);
   }
 
@@ -690,14 +695,15 @@ static void fmg_solve_once(mg_type *G, int onLevel, int u_id, int F_id, double a
     if (is_small(G, l)) seg_open();
     t = hpgmg_tick_begin(G->levels[l], &G->levels[l]->timers.Total, "interpolation_fcycle");
     if (l == onLevel && u_to_zero) {
-      if (!hpgmg_zero_interpolation_fcycle_fused(G->levels[l], e_id, G->levels[l + 1], e_id)) { zero_vector(G->levels[l], e_id); interpolation_fcycle(G->levels[l], e_id, 0.0, G->levels[l + 1], e_id); }
+      if (hook || !hpgmg_zero_interpolation_fcycle_fused(G->levels[l], e_id, G->levels[l + 1], e_id)) { zero_vector(G->levels[l], e_id); interpolation_fcycle(G->levels[l], e_id, 0.0, G->levels[l + 1], e_id); }
       u_to_zero = 0;
-    } else if (is_small(G, l) && hpgmg_vcycle_legs_fused(&G->levels[l], G->num_levels - l, e_id, R_id, a, b, HPGMG_LEG_FCYCLE_STEP)) {      /* the plugin ran this step whole: interpolation + V-cycle */
+    } else if (!hook && is_small(G, l) && hpgmg_vcycle_legs_fused(&G->levels[l], G->num_levels - l, e_id, R_id, a, b, HPGMG_LEG_FCYCLE_STEP)) {      /* the plugin ran this step whole: interpolation + V-cycle */
       hpgmg_tick_end(t);
       G->levels[l]->vcycles_from_this_level++;
       seg_close();
       continue;
     } else interpolation_fcycle(G->levels[l], e_id, 0.0, G->levels[l + 1], e_id);
+    if (hook && hook->interpolated) hook->interpolated(hook, G, l, e_id);
     hpgmg_tick_end(t);
     G->levels[l]->vcycles_from_this_level++;
     MGVCycle(G, e_id, R_id, a, b, l);

@@ -2,7 +2,7 @@
  * plugin_dense.c -- hpgmg_dense_pack / hpgmg_dense_unpack of the operator plugin (include/hpgmg_operators.h): one launch of
  * kernels/dense_io.hip per array.  A device array is read / written in place; a host array is copied once into the level's staging buffer
  * (allocated on first use, freed with the level) and packed from there, or unpacked into it and copied out once.  They replace the weak
- * host defaults of host/driver.c, which go box by box through hpgmg_vector_upload / download.
+ * host defaults of host/driver.c, which go box by box through hpgmg_vector_upload / download.  The boundary-value hooks below likewise.
  */
 #include "plugin_internal.h"
 
@@ -47,4 +47,43 @@ int hpgmg_dense_unpack(level_type *L, int id, double *dst, int where) {
   HIP_OK(hpgmg_hip_dense_unpack(&B->dev, id, stage));
   HIP_OK(hpgmg_hip_memcpy_d2h(dst, stage, n * sizeof(double)));
   return 0;
+}
+
+/* boundary values (include/hpgmg_operators.h): one launch of kernels/dense_boundary.hip each.  g, phi are device arrays (hpgmg_vector_alloc);
+ * f is staged as hpgmg_dense_pack stages it. */
+static double bnd_weight(const level_type *L, double b) { return (2.0 * b) * (1.0 / (L->h * L->h)); }
+
+int hpgmg_dense_pack_lifted(level_type *L, int id, const double *f, int where, const double *g, double b) {
+  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || !f || !g || L->boundary_condition.type != BC_DIRICHLET) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  backend_t *B = hp_backend_of(L);
+  const size_t n = (size_t)L->dim.i * L->dim.j * L->dim.k;
+  const double *d_src = f;
+  int status = 0;
+  if (where == HPGMG_WHERE_HOST) {
+    double *stage = dense_stage(B, n);
+    HIP_OK(hpgmg_hip_memcpy_h2d(stage, f, n * sizeof(double)));
+    d_src = stage;
+  }
+  HIP_OK(hpgmg_hip_dense_pack_lifted(&B->dev, id, d_src, g, bnd_weight(L, b), &status));
+  return status;
+}
+
+int hpgmg_boundary_flux(level_type *L, double *phi, const double *g, double b) {
+  int status = 0;
+  HIP_OK(hpgmg_hip_boundary_flux(&hp_backend_of(L)->dev, phi, g, bnd_weight(L, b), &status));
+  return status;
+}
+
+void hpgmg_boundary_restrict(level_type *Lc, double *g_c, level_type *Lf, const double *g_f) {
+  (void)Lf;
+  HIP_OK(hpgmg_hip_boundary_restrict(g_c, g_f, Lc->dim.i));
+}
+
+void hpgmg_boundary_lift(level_type *L, int id, const double *phi, const double *phi_fine, double sign) {
+  HIP_OK(hpgmg_hip_boundary_lift(&hp_backend_of(L)->dev, id, phi, phi_fine, sign));
+}
+
+void hpgmg_boundary_interp(level_type *Lf, int id, level_type *Lc, const double *g_c) {
+  HIP_OK(hpgmg_hip_boundary_interp(&hp_backend_of(Lf)->dev, id, g_c, Lc->dim.i));
 }

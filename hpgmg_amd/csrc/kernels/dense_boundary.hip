@@ -1,0 +1,266 @@
+// dense_boundary.hip -- inhomogeneous Dirichlet values of the dense-array API (include/hpgmg_operators.h hpgmg_dense_pack_lifted,
+// hpgmg_boundary_flux / _restrict / _lift / _interp; the formulas and their order are written there and in DESIGN.md §11).
+//
+// A boundary array is 6 x n x n doubles (n = the level's cells per side, a cube): [0], [1] i-low / i-high indexed [k][j], [2], [3] j-low /
+// j-high [k][i], [4], [5] k-low / k-high [j][i].  w = (2.0 * b) * (1.0 / (h * h)) comes from the host, so every term (w * beta) * g has the
+// host default's bits (-ffp-contract=off).
+//
+// Lifted pack: dense_pack_kernel's single pass over every double of every padded box (grid row y = box, 32-bit offsets inside it,
+// consecutive lanes on consecutive doubles), plus T(c) on the interior cells that lie on a domain face, read from the box's own beta
+// vectors and g; f and the g values read are validated into the same device word.
+// Face kernels (flux, lift, interp): grid row y = box, x over the 6 dim^2 face positions of the box; a position on a box face that is not
+// a domain face does nothing.  A cell on several domain faces (edge, corner) is handled once, by the position of the first face it touches
+// in the order i-low .. k-high, so no two lanes write one cell.  One launch per level and operation; they are launch bound (6 n^2 cells).
+#include "common.hpp"
+
+namespace hpgmg {
+
+constexpr int kBndThreads = 256;
+static int *g_bnd_flag = nullptr;               // validation bits of the last lifted pack / flux (device word)
+
+__device__ __forceinline__ bool bnd_touches(int n, int face, int gi, int gj, int gk) {
+  const int c = face < 2 ? gi : face < 4 ? gj : gk;
+  return (face & 1) ? c == n - 1 : c == 0;
+}
+__device__ __forceinline__ int bnd_entry(int n, int face, int gi, int gj, int gk) {     // 6 n^2 < 2^31 for any level that fits a device
+  const int q = face < 4 ? gk : gj, p = face < 2 ? gj : gi;
+  return (face * n + q) * n + p;
+}
+// offset, from a cell's padded offset, of its beta on face `face`, and the vector holding it
+__device__ __forceinline__ int bnd_beta_vec(int face) { return face < 2 ? VECTOR_BETA_I : face < 4 ? VECTOR_BETA_J : VECTOR_BETA_K; }
+__device__ __forceinline__ int bnd_beta_step(const hpgmg_hip_level &L, int face) {
+  return !(face & 1) ? 0 : face == 1 ? 1 : face == 3 ? L.jStride : L.kStride;
+}
+
+// the face position t of a box: local cell (i, j, k) and whether it is on a domain face and owned (first face it touches)
+struct FacePos { int face, i, j, k; bool on; };
+__device__ __forceinline__ FacePos bnd_face_pos(const hpgmg_hip_level &L, int li, int lj, int lk, int t) {
+  const int dim = L.dim, n = L.dim_i, plane = dim * dim;
+  FacePos P;
+  P.face = t / plane;
+  const int r = t - P.face * plane, q = r / dim, p = r - q * dim, side = (P.face & 1) ? dim - 1 : 0;
+  if (P.face < 2) { P.i = side; P.j = p; P.k = q; }
+  else if (P.face < 4) { P.i = p; P.j = side; P.k = q; }
+  else { P.i = p; P.j = q; P.k = side; }
+  const int gi = li + P.i, gj = lj + P.j, gk = lk + P.k;
+  P.on = bnd_touches(n, P.face, gi, gj, gk);
+  for (int f = 0; f < P.face; f++) P.on = P.on && !bnd_touches(n, f, gi, gj, gk);
+  return P;
+}
+
+__global__ __launch_bounds__(kBndThreads) void dense_pack_lifted_kernel(const hpgmg_hip_level L, int id, const double *__restrict__ src,
+                                                                        const double *__restrict__ g, double w, int *flag) {
+  const int gh = L.ghosts, dim = L.dim, n = L.dim_i;
+  int bits = 0;
+  for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
+    const int li = L.box_low[3 * box], lj = L.box_low[3 * box + 1], lk = L.box_low[3 * box + 2];
+    double *dst = L.box_base[box] + (size_t)id * L.volume;
+    const double *bi = L.box_base[box] + (size_t)VECTOR_BETA_I * L.volume, *bj = L.box_base[box] + (size_t)VECTOR_BETA_J * L.volume;
+    const double *bk = L.box_base[box] + (size_t)VECTOR_BETA_K * L.volume;
+    for (int ofs = (int)(blockIdx.x * kBndThreads + threadIdx.x); ofs < L.volume; ofs += (int)(gridDim.x * kBndThreads)) {
+      const int pk = ofs / L.kStride, pj = (ofs - pk * L.kStride) / L.jStride, pi = ofs - pk * L.kStride - pj * L.jStride;
+      const int i = pi - gh, j = pj - gh, k = pk - gh;
+      double v = 0.0;
+      if (i >= 0 && i < dim && j >= 0 && j < dim && k >= 0 && k < dim) {
+        const int gi = li + i, gj = lj + j, gk = lk + k;
+        v = src[((size_t)gk * n + gj) * n + gi];
+        if (!isfinite(v)) bits |= HPGMG_DENSE_NOT_FINITE;
+        if (gi == 0 || gj == 0 || gk == 0 || gi == n - 1 || gj == n - 1 || gk == n - 1) {
+          double T = 0.0;
+          for (int face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
+            const double gv = g[bnd_entry(n, face, gi, gj, gk)];
+            if (!isfinite(gv)) bits |= HPGMG_DENSE_NOT_FINITE;
+            const double *beta = face < 2 ? bi : face < 4 ? bj : bk;
+            T = T + (w * beta[ofs + bnd_beta_step(L, face)]) * gv;
+          }
+          v = v + T;
+        }
+      }
+      dst[ofs] = v;
+    }
+  }
+  if (bits) atomicOr(flag, bits);
+}
+
+__global__ __launch_bounds__(kBndThreads) void boundary_flux_kernel(const hpgmg_hip_level L, double *__restrict__ phi,
+                                                                    const double *__restrict__ g, double w, int *flag) {
+  const int n = L.dim_i, positions = 6 * L.dim * L.dim;
+  int bits = 0;
+  for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
+    const int li = L.box_low[3 * box], lj = L.box_low[3 * box + 1], lk = L.box_low[3 * box + 2];
+    for (int t = (int)(blockIdx.x * kBndThreads + threadIdx.x); t < positions; t += (int)(gridDim.x * kBndThreads)) {
+      const int face = t / (L.dim * L.dim);
+      const int r = t - face * L.dim * L.dim, q = r / L.dim, p = r - q * L.dim, side = (face & 1) ? L.dim - 1 : 0;
+      const int i = face < 2 ? side : p, j = face < 2 ? p : face < 4 ? side : q, k = face < 4 ? q : side;
+      const int gi = li + i, gj = lj + j, gk = lk + k;
+      if (!bnd_touches(n, face, gi, gj, gk)) continue;          // this box face is not a domain face: every entry has one box face that is
+      const int e = bnd_entry(n, face, gi, gj, gk);
+      const double gv = g[e];
+      if (!isfinite(gv)) bits |= HPGMG_DENSE_NOT_FINITE;
+      const double beta = vec_origin(L, box, bnd_beta_vec(face))[i + j * L.jStride + k * L.kStride + bnd_beta_step(L, face)];
+      phi[e] = (w * beta) * gv;
+    }
+  }
+  if (bits) atomicOr(flag, bits);
+}
+
+__global__ __launch_bounds__(kBndThreads) void boundary_restrict_kernel(double *__restrict__ gc, const double *__restrict__ gf, int nc) {
+  const int nf = 2 * nc, total = 6 * nc * nc;
+  for (int e = (int)(blockIdx.x * kBndThreads + threadIdx.x); e < total; e += (int)(gridDim.x * kBndThreads)) {
+    const int face = e / (nc * nc), r = e - face * nc * nc, q = r / nc, p = r - q * nc;
+    const double *s = gf + (face * nf + 2 * q) * nf + 2 * p;
+    gc[e] = (s[0] + s[1] + s[nf] + s[nf + 1]) * 0.25;
+  }
+}
+
+__global__ __launch_bounds__(kBndThreads) void boundary_lift_kernel(const hpgmg_hip_level L, int id, const double *__restrict__ phi,
+                                                                    const double *__restrict__ phi_fine, double sign) {
+  const int n = L.dim_i, positions = 6 * L.dim * L.dim;
+  for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
+    const int li = L.box_low[3 * box], lj = L.box_low[3 * box + 1], lk = L.box_low[3 * box + 2];
+    double *v = vec_origin(L, box, id);
+    for (int t = (int)(blockIdx.x * kBndThreads + threadIdx.x); t < positions; t += (int)(gridDim.x * kBndThreads)) {
+      const FacePos P = bnd_face_pos(L, li, lj, lk, t);
+      if (!P.on) continue;
+      const int gi = li + P.i, gj = lj + P.j, gk = lk + P.k;
+      double T = 0.0;
+      for (int face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) T = T + phi[bnd_entry(n, face, gi, gj, gk)];
+      if (phi_fine) {                      // S: the four finer entries under each face entry, faces in order
+        const int nf = 2 * n;
+        double S = 0.0;
+        for (int face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
+          const int q = face < 4 ? gk : gj, p = face < 2 ? gj : gi;
+          const double *e = phi_fine + (face * nf + 2 * q) * nf + 2 * p;
+          S = S + (((e[0] + e[1]) + e[nf]) + e[nf + 1]);
+        }
+        T = T - 0.125 * S;
+      }
+      const int c = P.i + P.j * L.jStride + P.k * L.kStride;
+      v[c] = v[c] + sign * T;
+    }
+  }
+}
+
+// the delta of the coarse ghost at (ci, cj, ck): host/driver.c bnd_ghost_delta, expression for expression
+#define BND_AT(f, i, j, k) g[((f) * n + ((f) < 4 ? (k) : (j))) * n + ((f) < 2 ? (j) : (i))]
+__device__ __forceinline__ double bnd_ghost_delta(int n, const double *g, int ci, int cj, int ck) {
+  const int q[3] = { ci, cj, ck };
+  int out[3], P[3], step[3], face[3], a, m = 0;
+  for (a = 0; a < 3; a++) {
+    out[a] = q[a] < 0 || q[a] >= n;
+    P[a] = q[a] < 0 ? 0 : q[a] >= n ? n - 1 : q[a];
+    step[a] = q[a] < 0 ? 1 : -1;                               // one cell inward
+    face[a] = 2 * a + (q[a] >= n);
+    m += out[a];
+  }
+  if (m == 1) { a = out[0] ? 0 : out[1] ? 1 : 2; return 2.0 * BND_AT(face[a], P[0], P[1], P[2]); }
+  if (n < 2) return m == 3 ? ((BND_AT(face[0], P[0], P[1], P[2]) + BND_AT(face[1], P[0], P[1], P[2])) + BND_AT(face[2], P[0], P[1], P[2])) * (2.0 / 3.0) : 0.0;
+  if (m == 2) {                      // the outside axes x < y
+    const int x = out[0] ? 0 : 1, y = out[2] ? 2 : 1;
+    const int yi = P[0] + (y == 0) * step[0], yj = P[1] + (y == 1) * step[1], yk = P[2] + (y == 2) * step[2];
+    const int xi = P[0] + (x == 0) * step[0], xj = P[1] + (x == 1) * step[1], xk = P[2] + (x == 2) * step[2];
+    return (BND_AT(face[x], P[0], P[1], P[2]) - BND_AT(face[x], yi, yj, yk)) + (BND_AT(face[y], P[0], P[1], P[2]) - BND_AT(face[y], xi, xj, xk));
+  }
+  double c[3];                       // corner: each wall's extrapolation
+  for (a = 0; a < 3; a++) {
+    const int b = a == 0 ? 1 : 0, d = a == 2 ? 1 : 2;          // the wall's in-face axes, b < d
+    const double g00 = BND_AT(face[a], P[0], P[1], P[2]);
+    const double g10 = BND_AT(face[a], P[0] + (b == 0) * step[0], P[1] + (b == 1) * step[1], P[2]);
+    const double g01 = BND_AT(face[a], P[0], P[1] + (d == 1) * step[1], P[2] + (d == 2) * step[2]);
+    c[a] = (2.0 * g00 - 0.5 * g10) - 0.5 * g01;
+  }
+  return ((c[0] + c[1]) + c[2]) * (2.0 / 3.0);
+}
+#undef BND_AT
+
+__global__ __launch_bounds__(kBndThreads) void boundary_interp_kernel(const hpgmg_hip_level L, int id, const double *__restrict__ gc, int nc) {
+  const int positions = 6 * L.dim * L.dim;
+  const double wt[8] = { 0.421875, 0.140625, 0.140625, 0.046875, 0.140625, 0.046875, 0.046875, 0.015625 };
+  for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
+    const int li = L.box_low[3 * box], lj = L.box_low[3 * box + 1], lk = L.box_low[3 * box + 2];
+    double *v = vec_origin(L, box, id);
+    for (int t = (int)(blockIdx.x * kBndThreads + threadIdx.x); t < positions; t += (int)(gridDim.x * kBndThreads)) {
+      const FacePos P = bnd_face_pos(L, li, lj, lk, t);
+      if (!P.on) continue;
+      const int gi = li + P.i, gj = lj + P.j, gk = lk + P.k;
+      const int ci = gi >> 1, cj = gj >> 1, ck = gk >> 1, di = (gi & 1) ? 1 : -1, dj = (gj & 1) ? 1 : -1, dk = (gk & 1) ? 1 : -1;
+      double D = 0.0;
+#pragma unroll
+      for (int s = 1; s < 8; s++) {       // interpolation_p1's reads after the centre: dk, dj, dj+dk, di, di+dk, di+dj, di+dj+dk
+        const int qi = ci + ((s >> 2) & 1) * di, qj = cj + ((s >> 1) & 1) * dj, qk = ck + (s & 1) * dk;
+        if (qi < 0 || qi >= nc || qj < 0 || qj >= nc || qk < 0 || qk >= nc) D = D + wt[s] * bnd_ghost_delta(nc, gc, qi, qj, qk);
+      }
+      const int c = P.i + P.j * L.jStride + P.k * L.kStride;
+      v[c] = v[c] + D;
+    }
+  }
+}
+
+static dim3 bnd_grid(int per_box, int boxes) {       // x: the positions of one box, y: the boxes (the rest of either by grid stride)
+  const int blocks = (per_box + kBndThreads - 1) / kBndThreads;
+  return dim3(blocks < 16384 ? (blocks > 0 ? blocks : 1) : 16384, boxes < 65535 ? boxes : 65535);
+}
+static int bnd_cube(const hpgmg_hip_level *L) { return L->dim_i == L->dim_j && L->dim_i == L->dim_k && L->periodic == 0; }
+
+}  // namespace hpgmg
+
+using namespace hpgmg;
+
+extern "C" {
+int hpgmg_hip_graph_flush(void);
+
+int hpgmg_hip_dense_pack_lifted(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int *status) {
+  *status = 0;
+  if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "dense_pack_lifted: the level is not a Dirichlet cube");
+  if (int e = hpgmg_hip_graph_flush()) return e;
+  if (L->num_boxes <= 0) return 0;
+  if (!g_bnd_flag) HPGMG_CHECK(hipMalloc((void **)&g_bnd_flag, sizeof(int)));
+  HPGMG_CHECK(hipMemsetAsync(g_bnd_flag, 0, sizeof(int), g_stream));
+  hipLaunchKernelGGL(dense_pack_lifted_kernel, bnd_grid(L->volume, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, src, g, w, g_bnd_flag);
+  HPGMG_LAUNCH_CHECK("dense_pack_lifted_kernel");
+  HPGMG_CHECK(hipMemcpyAsync(status, g_bnd_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
+  HPGMG_CHECK(hipStreamSynchronize(g_stream));
+  return 0;
+}
+
+int hpgmg_hip_boundary_flux(const hpgmg_hip_level *L, double *phi, const double *g, double w, int *status) {
+  *status = 0;
+  if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "boundary_flux: the level is not a Dirichlet cube");
+  if (int e = hpgmg_hip_graph_flush()) return e;
+  if (L->num_boxes <= 0) return 0;
+  if (!g_bnd_flag) HPGMG_CHECK(hipMalloc((void **)&g_bnd_flag, sizeof(int)));
+  HPGMG_CHECK(hipMemsetAsync(g_bnd_flag, 0, sizeof(int), g_stream));
+  hipLaunchKernelGGL(boundary_flux_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, phi, g, w, g_bnd_flag);
+  HPGMG_LAUNCH_CHECK("boundary_flux_kernel");
+  HPGMG_CHECK(hipMemcpyAsync(status, g_bnd_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
+  HPGMG_CHECK(hipStreamSynchronize(g_stream));
+  return 0;
+}
+
+int hpgmg_hip_boundary_restrict(double *g_c, const double *g_f, int n_c) {
+  HPGMG_SKIP_IF_REPLAY();
+  if (n_c <= 0) return 0;
+  hipLaunchKernelGGL(boundary_restrict_kernel, bnd_grid(6 * n_c * n_c, 1), dim3(kBndThreads), 0, g_stream, g_c, g_f, n_c);
+  HPGMG_LAUNCH_CHECK("boundary_restrict_kernel");
+  return 0;
+}
+
+int hpgmg_hip_boundary_lift(const hpgmg_hip_level *L, int id, const double *phi, const double *phi_fine, double sign) {
+  HPGMG_SKIP_IF_REPLAY();
+  if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "boundary_lift: the level is not a Dirichlet cube");
+  if (L->num_boxes <= 0) return 0;
+  hipLaunchKernelGGL(boundary_lift_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, phi, phi_fine, sign);
+  HPGMG_LAUNCH_CHECK("boundary_lift_kernel");
+  return 0;
+}
+
+int hpgmg_hip_boundary_interp(const hpgmg_hip_level *L, int id, const double *g_c, int n_c) {
+  HPGMG_SKIP_IF_REPLAY();
+  if (!bnd_cube(L) || 2 * n_c != L->dim_i) return record_error(hipErrorInvalidValue, "boundary_interp: the levels are not a Dirichlet cube and its coarsening");
+  if (L->num_boxes <= 0) return 0;
+  hipLaunchKernelGGL(boundary_interp_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, g_c, n_c);
+  HPGMG_LAUNCH_CHECK("boundary_interp_kernel");
+  return 0;
+}
+
+}  // extern "C"

@@ -8,6 +8,11 @@ Arrays are C-contiguous float64 indexed [k][j][i]; cell (i,j,k) has its centre a
 are (N,N,N).  Dirichlet (homogeneous): beta_i is (N,N,N+1), beta_i[k][j][i] on the face between cells i-1 and i (i = 0 and i = N are the
 domain faces); beta_j is (N,N+1,N), beta_k (N+1,N,N).  Periodic: all three are (N,N,N), face N being face 0.
 
+Inhomogeneous Dirichlet values: `boundary=` of set_rhs / solve / apply, a (6,N,N) float64 array of face-centre values (the same kind of
+array as the call's others): boundary[0], [1] the i-low / i-high faces indexed [k][j]; [2], [3] j-low / j-high indexed [k][i]; [4], [5]
+k-low / k-high indexed [j][i].  A boundary cell's ghost is 2 g - u instead of -u, so the solve is A0 u = f + T(g), and
+apply(x, boundary=g) is A0 x - T(g).  Solver.boundary_from(fn) samples fn(x, y, z) at the face centres.
+
 NumPy arrays take the host path.  torch tensors on the library's GPU (float64, contiguous) are read and written in place, and results come
 back as tensors on that device.  torch must be imported before this package loads its libraries: both bring a HIP runtime
 (libamdhip64.so.7), and a device pointer is only valid inside the runtime that made it.  The C entry points are hpgmg_user_* of
@@ -34,7 +39,7 @@ _STATUS = {H.USER_BAD_ARGUMENT: "refused by the library", H.USER_CONFLICT: "the 
 @dataclass
 class SolveInfo:
     residual: float      # |f - A u|_inf (f after the mean shift)
-    norm_f: float        # |f|_inf
+    norm_f: float        # |f|_inf; with boundary values |f + T(g)|_inf, the right-hand side actually solved
     vcycles: int         # V-cycles run from the finest level (an F-cycle ends with one)
     converged: bool      # residual < rtol * norm_f
     mean_shift: float    # subtracted from f (periodic without an a alpha term), else 0.0
@@ -77,6 +82,7 @@ class Solver:
         self.lib = lib if lib is not None else H.load_driver()
         self.hip = self.lib.hpgmg_backend_name() == b"hip"
         self.n, self.bc, self.a, self.b = int(n), bc, float(a), float(b)
+        self.h = float(h) if h is not None and h > 0 else 1.0 / self.n
         self._ptr = None
         out = ctypes.c_void_p()
         st = self.lib.hpgmg_user_create(self.n, int(box_dim or 0), _BC[bc], _OPERATOR[operator], _SMOOTHER[smoother], self.a, self.b,
@@ -180,25 +186,60 @@ class Solver:
             self._check(st, self._first_bad(named, st))
         self._check(st, "alpha, beta_i, beta_j, beta_k")
 
-    def set_rhs(self, f):
-        """Packs f; returns the mean subtracted from it (periodic without an a alpha term), else 0.0."""
+    def _boundary(self, g, kind):
+        """(pointer of) the boundary values g: (6,N,N), of the same kind as the call's other arrays; Dirichlet only."""
+        if self.bc != "dirichlet":
+            raise ValueError(f"boundary: boundary values need a Dirichlet domain (this solver is {self.bc})")
+        return self._arg(g, (6, self.n, self.n), "boundary", kind)[0]
+
+    def boundary_from(self, fn):
+        """Boundary values sampled from fn(x, y, z) (NumPy arrays in, an array of their shape out) at the 6 N^2 face centres: cell (i,j,k) is
+        centred at ((i+1/2)h, (j+1/2)h, (k+1/2)h), so the faces lie at 0 and N h.  Returns the (6,N,N) NumPy array that boundary= takes."""
+        n, h = self.n, self.h
+        c = (np.arange(n) + 0.5) * h
+        slow, fast = np.meshgrid(c, c, indexing="ij")          # entry [q][p]: p the faster index
+        g = np.empty((6, n, n))
+        for face in range(6):
+            wall = np.full((n, n), n * h if face & 1 else 0.0)
+            if face < 2:
+                x, y, z = wall, fast, slow                       # [k][j]
+            elif face < 4:
+                x, y, z = fast, wall, slow                       # [k][i]
+            else:
+                x, y, z = fast, slow, wall                       # [j][i]
+            g[face] = np.broadcast_to(np.asarray(fn(x, y, z), dtype=np.float64), (n, n))
+        return g
+
+    def set_rhs(self, f, boundary=None):
+        """Packs f (with boundary values: f + T(boundary)); returns the mean subtracted from f (periodic without an a alpha term), else 0.0."""
         p, where, kind = self._arg(f, (self.n,) * 3, "f")
-        self._sync_torch(kind)
         shift = ctypes.c_double(0.0)
-        self._check(self.lib.hpgmg_user_set_rhs(self._ptr, p, where, ctypes.byref(shift)), "f")
+        if boundary is None:
+            self._sync_torch(kind)
+            self._check(self.lib.hpgmg_user_set_rhs(self._ptr, p, where, ctypes.byref(shift)), "f")
+            return shift.value
+        pg = self._boundary(boundary, kind)
+        self._sync_torch(kind)
+        st = self.lib.hpgmg_user_set_rhs_dirichlet(self._ptr, p, pg, where, ctypes.byref(shift))
+        if st == H.USER_NOT_FINITE:
+            self._check(st, self._first_bad([("f", f, 0.0, False), ("boundary", boundary, 0.0, False)], st))
+        self._check(st, "f, boundary")
         return shift.value
 
-    def solve(self, f, method="fmg", rtol=1e-10, u0=None, out=None):
+    def solve(self, f, method="fmg", rtol=1e-10, u0=None, out=None, boundary=None):
         """u, SolveInfo.  method 'fmg': one F-cycle (the benchmark's solve); 'mg': V-cycles until |f - A u| < rtol |f|.
-        u0: start from it (u = u0 + e, the correction solved with V-cycles; method is then not used)."""
+        u0: start from it (u = u0 + e, the correction solved with V-cycles; method is then not used).
+        boundary: Dirichlet values (module docstring); f then stands for f + T(boundary) throughout."""
         if method not in _METHOD:
             raise ValueError(f"method: {method!r} is not one of {sorted(_METHOD)}")
         if not rtol > 0.0:
             raise ValueError(f"rtol: {rtol!r} must be > 0")
         _, _, kind = self._arg(f, (self.n,) * 3, "f")
         p0 = self._arg(u0, (self.n,) * 3, "u0", kind)[0] if u0 is not None else None
+        if boundary is not None:
+            self._boundary(boundary, kind)
         out = self._out(out, kind, f, "out")
-        self.set_rhs(f)
+        self.set_rhs(f, boundary)
         info = H.UserInfo()
         self._sync_torch(kind)
         self._check(self.lib.hpgmg_user_solve(self._ptr, _METHOD[method], float(rtol), p0,
@@ -215,13 +256,20 @@ class Solver:
         self._check(self.lib.hpgmg_user_get_solution(self._ptr, p, where), "out")
         return out
 
-    def apply(self, x, out=None):
-        """y = A x."""
+    def apply(self, x, out=None, boundary=None):
+        """y = A x; with boundary values y = A0 x - T(boundary), so that apply(u, boundary=g) - f is the residual of a solution."""
         px, where, kind = self._arg(x, (self.n,) * 3, "x")
+        pg = self._boundary(boundary, kind) if boundary is not None else None
         out = self._out(out, kind, x, "out")
         py = self._arg(out, (self.n,) * 3, "out", kind)[0]
         self._sync_torch(kind)
-        self._check(self.lib.hpgmg_user_apply(self._ptr, px, py, where), "x")
+        if pg is None:
+            self._check(self.lib.hpgmg_user_apply(self._ptr, px, py, where), "x")
+            return out
+        st = self.lib.hpgmg_user_apply_dirichlet(self._ptr, px, pg, py, where)
+        if st == H.USER_NOT_FINITE:
+            self._check(st, self._first_bad([("boundary", boundary, 0.0, False), ("x", x, 0.0, False)], st))
+        self._check(st, "x, boundary")
         return out
 
     def close(self):

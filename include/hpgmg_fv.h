@@ -87,6 +87,15 @@ int  hpgmg_user_set_rhs(hpgmg_user_solver *s, const double *f, int where, double
 int  hpgmg_user_solve(hpgmg_user_solver *s, int method, double rtol, const double *u0, int where, hpgmg_user_info *info);
 int  hpgmg_user_get_solution(hpgmg_user_solver *s, double *u, int where);
 int  hpgmg_user_apply(hpgmg_user_solver *s, const double *x, double *y, int where);   /* y = A x (apply_op) */
+/* Inhomogeneous Dirichlet values.  g: (6,N,N) float64 of face-centre values, in the same memory as f / x (where): g[0], g[1]
+ * the i-low / i-high faces indexed [k][j], g[2], g[3] j-low / j-high [k][i], g[4], g[5] k-low / k-high [j][i].  A boundary cell's ghost is
+ * 2 g - u; the equations are A0 u = f + T(g), A0 the operator above (homogeneous ghosts), T of include/hpgmg_operators.h.
+ * set_rhs_dirichlet: packs F = f + T(g) (f and g finite: else HPGMG_USER_NOT_FINITE) and the per-level g_l; the next HPGMG_USER_FMG solve runs an
+ * F-cycle whose coarse right-hand sides carry each level's own T_l(g_l); HPGMG_USER_MG and u0 solve A0 u = F as they are.  set_rhs clears the
+ * boundary values; set_coefficients after set_rhs_dirichlet leaves no right-hand side (solve: HPGMG_USER_NOT_READY).  info.norm_of_f is |F|.
+ * apply_dirichlet: y = A0 x - T(g), the residual operator of the boundary-value problem.  A periodic solver: HPGMG_USER_UNSUPPORTED. */
+int  hpgmg_user_set_rhs_dirichlet(hpgmg_user_solver *s, const double *f, const double *g, int where, double *mean_shift);
+int  hpgmg_user_apply_dirichlet(hpgmg_user_solver *s, const double *x, const double *g, double *y, int where);
 
 /* ---- small accessors so a ctypes caller never needs the struct layouts ---- */
 enum { HPGMG_INFO_DIM = 0, HPGMG_INFO_BOX_DIM, HPGMG_INFO_GHOSTS, HPGMG_INFO_JSTRIDE, HPGMG_INFO_KSTRIDE,

@@ -350,6 +350,16 @@ int hpgmg_hip_gram(const hpgmg_hip_level *L, const int *id_A, int rows, const in
  * and returns the validation bits in *status (HPGMG_DENSE_*; check = HPGMG_DENSE_CHECK_*).  Both synchronise. */
 int hpgmg_hip_dense_pack(const hpgmg_hip_level *L, int id, const double *src, int ni, int nj, int nk, int check, int *status);
 int hpgmg_hip_dense_unpack(const hpgmg_hip_level *L, int id, double *dst);
+/* boundary values of the dense-array API (include/hpgmg_operators.h hpgmg_dense_pack_lifted / hpgmg_boundary_*; kernels/dense_boundary.hip).
+ * All arrays are DEVICE arrays; the level must be a Dirichlet cube; w = (2.0 * b) * (1.0 / (h * h)) of the level.  pack_lifted: hpgmg_hip_dense_pack
+ * of a CELL array plus T(c) from g and the box's betas; flux: phi = (w * beta) * g.  Both validate (HPGMG_DENSE_NOT_FINITE in *status) and
+ * synchronise.  restrict (g_c of a level of n_c cells per side from the finer level's g_f), lift and interp (fine level L, coarse boundary
+ * values g_c of n_c = L's n / 2) only enqueue: one launch each, which a captured segment may hold. */
+int hpgmg_hip_dense_pack_lifted(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int *status);
+int hpgmg_hip_boundary_flux(const hpgmg_hip_level *L, double *phi, const double *g, double w, int *status);
+int hpgmg_hip_boundary_restrict(double *g_c, const double *g_f, int n_c);
+int hpgmg_hip_boundary_lift(const hpgmg_hip_level *L, int id, const double *phi, const double *phi_fine, double sign);
+int hpgmg_hip_boundary_interp(const hpgmg_hip_level *L, int id, const double *g_c, int n_c);
 
 /* ---- operators/rebuild.c:47-208 black-box rebuild: accumulate one colouring (x = 0/1 pattern, ghosts
  *      already exchanged / BCs applied) into Aii and sum|Aij|, then turn them into Dinv, L1inv, lambda_max ---- */

@@ -37,6 +37,17 @@ void FMGSolve(mg_type *all_grids, int onLevel, int u_id, int F_id, double a, dou
 void hpgmg_set_ucycles(int on);        /* before MGBuild: 1 = the reference's -DUSE_UCYCLES ladder (boxes halved, never merged; mg.c:878-893) */
 void hpgmg_fmg_zero_u_first(void);  /* the NEXT FMGSolve starts from u = 0: it zeroes u itself, where it first touches it (the benchmark step's zero_vector(u), hpgmg-fv.c:77-85) */
 void hpgmg_set_fmg_vcycles(int n);     /* V-cycles FMGSolve may add after its F-cycle: 0 (default) or 20 = -DUNLIMIT_FMG_ITERATIONS (mg.c:1239-1247) */
+/* F-cycle hook of the boundary-value solves (hpgmg_user_set_rhs_dirichlet); NULL (the default) leaves FMGSolve as it is.
+ * While one is set, FMGSolve calls rhs_restricted(hook, G, l, R_id) after each restriction of the right-hand side onto level l >= 1, and its
+ * own restriction chain and climb take the launch-by-launch forms (the V-cycles it runs keep every fused form).  key goes into the keys of
+ * the captured segments, so a hooked and an unhooked F-cycle never share one. */
+typedef struct hpgmg_fmg_hook {
+  void (*rhs_restricted)(const struct hpgmg_fmg_hook *hook, mg_type *G, int level, int R_id);
+  void (*interpolated)(const struct hpgmg_fmg_hook *hook, mg_type *G, int level, int e_id);
+  void *ctx;
+  long long key;
+} hpgmg_fmg_hook;
+void hpgmg_fmg_set_hook(const hpgmg_fmg_hook *hook);
 void MGPCG(mg_type *all_grids, int onLevel, int x_id, int F_id, double a, double b, double rtol);   /* mg.c:1500-1605: CG preconditioned with one V-cycle per iteration; grows every level by three vectors */
 void MGPrintTiming(mg_type *all_grids, int fromLevel);
 void MGResetTimers(mg_type *all_grids);

@@ -133,6 +133,28 @@ enum { HPGMG_DENSE_NOT_FINITE = 1, HPGMG_DENSE_OUT_OF_RANGE = 2 };
 enum { HPGMG_WHERE_HOST = 0, HPGMG_WHERE_PLUGIN = 1 };
 int     hpgmg_dense_pack(level_type *level, int id, const double *src, int where, int layout, int check);
 int     hpgmg_dense_unpack(level_type *level, int id, double *dst, int where);
+/* Inhomogeneous Dirichlet values (the boundary-value solves of include/hpgmg_fv.h).  A level's boundary array is 6 x n x n
+ * doubles in the plugin's memory, n the level's cells per side: [0], [1] the i-low / i-high domain faces indexed [k][j]; [2], [3] j-low / j-high
+ * indexed [k][i]; [4], [5] k-low / k-high indexed [j][i] (entry [q][p]: p the faster index).  The ghost of a boundary cell is 2 g - u instead of
+ * -u, which moves  phi = ((2.0 * b) * (1.0 / (h * h))) * beta_face) * g  per face to the right-hand side: beta_face is the level's beta of that
+ * face (beta_i at i = 0 of a box on the i-low face, at its high ghost layer i = dim on the i-high face; j, k alike), h the level's.  For a cell c
+ * T(c) = 0.0 + phi of each domain face c touches, added in the order i-low, i-high, j-low, j-high, k-low, k-high.  Cells on no face: T = 0.
+ *   pack_lifted:       vector id := f + T(c) from g (hpgmg_dense_pack's CELL layout and one pass; f and g are checked: HPGMG_DENSE_NOT_FINITE)
+ *   boundary_flux:     phi of every entry of g (the level's beta, h; b) into phi; returns HPGMG_DENSE_NOT_FINITE if g holds a non-finite value
+ *   boundary_restrict: g_c[f][q][p] = (g_f[f][2q][2p] + g_f[f][2q][2p+1] + g_f[f][2q+1][2p] + g_f[f][2q+1][2p+1]) * 0.25, left to right
+ *   boundary_lift:     every boundary cell c of the level: v(c) := v(c) + sign * T(c), T from phi; with phi_fine (the next finer level's phi) instead
+ *                      v(c) := v(c) + sign * (T(c) - 0.125 * S(c)), S(c) = 0.0 + per face c touches (same order) the sum of the four finer
+ *                      entries under its entry, summed as boundary_restrict sums them.  S is the cell restriction of the finer level's T.
+ *   boundary_interp:   after interpolation_fcycle (p1) of coarse onto fine: every fine boundary cell adds D = 0.0 + weight * delta over its p1 reads
+ *                      that land on a coarse ghost, in interpolation_p1's order; delta = the inhomogeneous minus the homogeneous ghost, from g_c
+ *                      (the coarse level's boundary array): 2 g on a face, the linear rules of DESIGN.md §11.1 on an edge or corner.
+ * g, g_c, g_f, phi, phi_fine live in the plugin's memory (hpgmg_vector_alloc).  host/driver.c holds weak host defaults (the CPU oracle); the HIP
+ * plugin overrides them (kernels/dense_boundary.hip), one launch each. */
+int     hpgmg_dense_pack_lifted(level_type *level, int id, const double *f, int where, const double *g, double b);
+int     hpgmg_boundary_flux(level_type *level, double *phi, const double *g, double b);
+void    hpgmg_boundary_restrict(level_type *coarse, double *g_c, level_type *fine, const double *g_f);
+void    hpgmg_boundary_lift(level_type *level, int id, const double *phi, const double *phi_fine, double sign);
+void    hpgmg_boundary_interp(level_type *fine, int id, level_type *coarse, const double *g_c);
 /* Launch-bound stretches of a cycle (everything done on levels of <= 64^3 cells between two
  * bottom solves) are bracketed by the cycle driver as a SEGMENT with a key that repeats every
  * solve, so the HIP plugin can capture it once into a hipGraph and replay it.  Plugins without
