@@ -52,6 +52,7 @@ WHERE_HOST, WHERE_PLUGIN = 0, 1
 (USER_OK, USER_BAD_ARGUMENT, USER_CONFLICT, USER_MULTI_RANK, USER_NOT_FINITE, USER_OUT_OF_RANGE,
  USER_NOT_READY, USER_UNSUPPORTED) = 0, -1, -2, -3, -4, -5, -6, -7
 USER_FMG, USER_MG = 0, 1
+FACE_DIRICHLET, FACE_NEUMANN = 0, 1
 
 
 class HipLevel(ctypes.Structure):
@@ -153,6 +154,13 @@ def _declare_driver_api(lib):
         "hpgmg_boundary_flux": (c_int, [vp, vp, vp, c_dbl]),
         "hpgmg_boundary_restrict": (None, [vp, vp, vp, vp]),
         "hpgmg_boundary_lift": (None, [vp, c_int, vp, vp, c_dbl]),
+        "hpgmg_boundary_interp": (None, [vp, c_int, vp, vp]),
+        # Neumann and mixed walls
+        "hpgmg_user_create_faces": (c_int, [c_int, c_int, P(c_int), c_int, c_int, c_dbl, c_dbl, c_dbl, P(vp)]),
+        "hpgmg_dense_pack_walls": (c_int, [vp, c_int, vp, c_int, c_int, c_int, c_int, vp]),
+        "hpgmg_dense_pack_lifted_faces": (c_int, [vp, c_int, vp, c_int, vp, c_dbl, c_int, vp]),
+        "hpgmg_boundary_flux_faces": (c_int, [vp, vp, vp, c_dbl, c_int, vp]),
+        "hpgmg_boundary_interp_faces": (None, [vp, c_int, vp, vp, c_int]),
         "hpgmg_vector_alloc": (vp, [ctypes.c_size_t]),
         "hpgmg_vector_free": (None, [vp]),
         "hpgmg_vector_copy": (None, [vp, vp, ctypes.c_size_t]),

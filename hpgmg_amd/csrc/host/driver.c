@@ -160,9 +160,14 @@ static int dense_extent(const level_type *L, int layout, int axis) {
   const int n = axis == 0 ? L->dim.i : axis == 1 ? L->dim.j : L->dim.k;
   return n + (layout == HPGMG_DENSE_FACE_I + axis && L->boundary_condition.type == BC_DIRICHLET);
 }
-__attribute__((weak)) int hpgmg_dense_pack(level_type *L, int id, const double *src, int where, int layout, int check) {
+/* mask, wall: hpgmg_dense_pack_walls (0, NULL: hpgmg_dense_pack) */
+static int dense_pack_host(level_type *L, int id, const double *src, int where, int layout, int check, int mask, double *wall) {
   if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || layout < HPGMG_DENSE_CELL || layout > HPGMG_DENSE_FACE_K || !src) return -1;
   if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  const int axis = layout - HPGMG_DENSE_FACE_I, n = L->dim.i;
+  const int lo = mask ? (mask >> (2 * axis)) & 1 : 0, hi = mask ? (mask >> (2 * axis + 1)) & 1 : 0;
+  double *wh = NULL;
+  if (lo || hi) { wh = (double *)malloc((size_t)6 * n * n * sizeof(double)); hpgmg_vector_download(wh, wall, (size_t)6 * n * n); }
   const size_t ni = (size_t)dense_extent(L, layout, 0), nj = (size_t)dense_extent(L, layout, 1);
   const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
   double *box = (double *)malloc((size_t)L->box_volume * sizeof(double));
@@ -178,12 +183,26 @@ __attribute__((weak)) int hpgmg_dense_pack(level_type *L, int id, const double *
       const double v = src[((size_t)(B->low.k + k) * nj + (size_t)(B->low.j + j)) * ni + (size_t)(B->low.i + i)];
       if (!isfinite(v)) status |= HPGMG_DENSE_NOT_FINITE;
       else if ((check == HPGMG_DENSE_CHECK_POSITIVE && !(v > 0.0)) || (check == HPGMG_DENSE_CHECK_NONNEGATIVE && !(v >= 0.0))) status |= HPGMG_DENSE_OUT_OF_RANGE;
+      const int c = axis == 0 ? i : axis == 1 ? j : k, gc = (axis == 0 ? B->low.i : axis == 1 ? B->low.j : B->low.k) + c;
+      if ((lo && gc == 0) || (hi && gc == n)) {               /* a masked domain wall: its beta goes to the wall array, the vector takes 0.0 */
+        const int q = axis == 2 ? B->low.j + j : B->low.k + k, p = axis == 0 ? B->low.j + j : B->low.i + i;
+        wh[((size_t)(2 * axis + (gc == n)) * n + q) * n + p] = v;
+        box[(i + g) + (j + g) * jS + (k + g) * kS] = 0.0;
+      } else
       box[(i + g) + (j + g) * jS + (k + g) * kS] = v;
     }
     hpgmg_vector_upload(B->vectors[id], box, (size_t)L->box_volume);
   }
   free(box);
+  if (wh) { hpgmg_vector_upload(wall, wh, (size_t)6 * n * n); free(wh); }
   return status;
+}
+__attribute__((weak)) int hpgmg_dense_pack(level_type *L, int id, const double *src, int where, int layout, int check) {
+  return dense_pack_host(L, id, src, where, layout, check, 0, NULL);
+}
+__attribute__((weak)) int hpgmg_dense_pack_walls(level_type *L, int id, const double *src, int where, int layout, int check, int mask, double *wall) {
+  if (layout < HPGMG_DENSE_FACE_I || !wall || mask < 0 || mask > 63 || L->boundary_condition.type != BC_DIRICHLET || L->dim.i != L->dim.j || L->dim.i != L->dim.k) return -1;
+  return dense_pack_host(L, id, src, where, layout, check, mask, wall);
 }
 __attribute__((weak)) int hpgmg_dense_unpack(level_type *L, int id, double *dst, int where) {
   if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || !dst) return -1;
@@ -243,13 +262,15 @@ static double *bnd_download(const double *src, size_t n) {
   return h;
 }
 
-__attribute__((weak)) int hpgmg_dense_pack_lifted(level_type *L, int id, const double *f, int where, const double *g, double b) {
+static double bnd_weight_neumann(const level_type *L, double b) { return b * (1.0 / L->h); }
+/* mask, wall: hpgmg_dense_pack_lifted_faces (0, NULL: hpgmg_dense_pack_lifted) */
+static int dense_pack_lifted_host(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
   if (!g || L->boundary_condition.type != BC_DIRICHLET) return -1;
   const int st = hpgmg_dense_pack(L, id, f, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE);
   if (st < 0) return st;
   const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
-  const double w = bnd_weight(L, b);
-  double *gh = bnd_download(g, (size_t)6 * n * n);
+  const double w = bnd_weight(L, b), wn = bnd_weight_neumann(L, b);
+  double *gh = bnd_download(g, (size_t)6 * n * n), *wh = mask ? bnd_download(wall, (size_t)6 * n * n) : NULL;
   double *v = (double *)malloc((size_t)L->box_volume * 4 * sizeof(double));
   double *bi = v + L->box_volume, *bj = bi + L->box_volume, *bk = bj + L->box_volume;
   int box, i, j, k, face, bad = 0;
@@ -267,22 +288,30 @@ __attribute__((weak)) int hpgmg_dense_pack_lifted(level_type *L, int id, const d
       for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
         const double gv = gh[bnd_entry(n, face, gi, gj, gk)];
         if (!isfinite(gv)) bad = 1;
-        T = T + (w * bnd_beta(bi, bj, bk, face, ijk, jS, kS)) * gv;
+        if ((mask >> face) & 1) T = T + (wn * wh[bnd_entry(n, face, gi, gj, gk)]) * gv;
+        else T = T + (w * bnd_beta(bi, bj, bk, face, ijk, jS, kS)) * gv;
         on = 1;
       }
       if (on) v[ijk] = v[ijk] + T;
     }
     hpgmg_vector_upload(B->vectors[id], v, (size_t)L->box_volume);
   }
-  free(v); free(gh);
+  free(v); free(gh); free(wh);
   return st | (bad ? HPGMG_DENSE_NOT_FINITE : 0);
 }
+__attribute__((weak)) int hpgmg_dense_pack_lifted(level_type *L, int id, const double *f, int where, const double *g, double b) {
+  return dense_pack_lifted_host(L, id, f, where, g, b, 0, NULL);
+}
+__attribute__((weak)) int hpgmg_dense_pack_lifted_faces(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
+  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
+  return dense_pack_lifted_host(L, id, f, where, g, b, mask, wall);
+}
 
-__attribute__((weak)) int hpgmg_boundary_flux(level_type *L, double *phi, const double *g, double b) {
+static int boundary_flux_host(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
   const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
   const size_t len = (size_t)6 * n * n;
-  const double w = bnd_weight(L, b);
-  double *gh = bnd_download(g, len), *ph = (double *)calloc(len, sizeof(double));
+  const double w = bnd_weight(L, b), wn = bnd_weight_neumann(L, b);
+  double *gh = bnd_download(g, len), *ph = (double *)calloc(len, sizeof(double)), *wh = mask ? bnd_download(wall, len) : NULL;
   double *bi = (double *)malloc((size_t)L->box_volume * 3 * sizeof(double)), *bj = bi + L->box_volume, *bk = bj + L->box_volume;
   int box, i, j, k, face, bad = 0;
   size_t e;
@@ -297,13 +326,19 @@ __attribute__((weak)) int hpgmg_boundary_flux(level_type *L, double *phi, const 
       const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
       for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
         e = bnd_entry(n, face, gi, gj, gk);
-        ph[e] = (w * bnd_beta(bi, bj, bk, face, ijk, jS, kS)) * gh[e];
+        if ((mask >> face) & 1) ph[e] = (wn * wh[e]) * gh[e];
+        else ph[e] = (w * bnd_beta(bi, bj, bk, face, ijk, jS, kS)) * gh[e];
       }
     }
   }
   hpgmg_vector_upload(phi, ph, len);
-  free(bi); free(ph); free(gh);
+  free(bi); free(ph); free(gh); free(wh);
   return bad ? HPGMG_DENSE_NOT_FINITE : 0;
+}
+__attribute__((weak)) int hpgmg_boundary_flux(level_type *L, double *phi, const double *g, double b) { return boundary_flux_host(L, phi, g, b, 0, NULL); }
+__attribute__((weak)) int hpgmg_boundary_flux_faces(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
+  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
+  return boundary_flux_host(L, phi, g, b, mask, wall);
 }
 
 __attribute__((weak)) void hpgmg_boundary_restrict(level_type *Lc, double *g_c, level_type *Lf, const double *g_f) {
@@ -387,6 +422,61 @@ static double bnd_interp_delta(int nc, const double *g, int gi, int gj, int gk) 
   return D;
 }
 
+/* hpgmg_boundary_interp_faces' delta (include/hpgmg_operators.h): u the coarse iterate as a dense (n,n,n) array, hc the coarse h */
+#define BND_AT(f, i, j, k) g[((size_t)(f) * n + ((f) < 4 ? (k) : (j))) * n + ((f) < 2 ? (j) : (i))]
+static double bnd_ghost_delta_faces(int n, const double *g, const double *u, double hc, int mask, int ci, int cj, int ck) {
+  const int q[3] = { ci, cj, ck };
+  int out[3], P[3], face[3], a, m = 0, dirichlet = 0;
+  for (a = 0; a < 3; a++) {
+    out[a] = q[a] < 0 || q[a] >= n;
+    P[a] = q[a] < 0 ? 0 : q[a] >= n ? n - 1 : q[a];
+    face[a] = 2 * a + (q[a] >= n);
+    m += out[a];
+    dirichlet += out[a] && !((mask >> face[a]) & 1);
+  }
+  if (dirichlet == m) return bnd_ghost_delta(n, g, ci, cj, ck);
+  double s = 0.0;
+  for (a = 0; a < 3; a++) if (out[a]) {
+    const double ga = BND_AT(face[a], P[0], P[1], P[2]);
+    s = s + (((mask >> face[a]) & 1) ? hc * ga : 2.0 * ga);
+  }
+  const double c = (double)(1 - 2 * dirichlet + ((m & 1) ? 1 : -1));
+  return c * u[((size_t)P[2] * n + P[1]) * n + P[0]] + s;
+}
+#undef BND_AT
+static double bnd_interp_delta_faces(int nc, const double *g, const double *u, double hc, int mask, int gi, int gj, int gk) {
+  const int ci = gi >> 1, cj = gj >> 1, ck = gk >> 1, di = (gi & 1) ? 1 : -1, dj = (gj & 1) ? 1 : -1, dk = (gk & 1) ? 1 : -1;
+  static const double w[8] = { 0.421875, 0.140625, 0.140625, 0.046875, 0.140625, 0.046875, 0.046875, 0.015625 };
+  static const int si[8] = { 0, 0, 0, 0, 1, 1, 1, 1 }, sj[8] = { 0, 0, 1, 1, 0, 0, 1, 1 }, sk[8] = { 0, 1, 0, 1, 0, 1, 0, 1 };
+  double D = 0.0;
+  int t;
+  for (t = 1; t < 8; t++) {
+    const int qi = ci + si[t] * di, qj = cj + sj[t] * dj, qk = ck + sk[t] * dk;
+    if (qi < 0 || qi >= nc || qj < 0 || qj >= nc || qk < 0 || qk >= nc) D = D + w[t] * bnd_ghost_delta_faces(nc, g, u, hc, mask, qi, qj, qk);
+  }
+  return D;
+}
+
+__attribute__((weak)) void hpgmg_boundary_interp_faces(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) {
+  const int n = Lf->dim.i, nc = Lc->dim.i, g0 = Lf->box_ghosts, dim = Lf->box_dim, jS = Lf->box_jStride, kS = Lf->box_kStride;
+  double *gc = bnd_download(g_c, (size_t)6 * nc * nc), *v = (double *)malloc((size_t)Lf->box_volume * sizeof(double));
+  double *uc = (double *)malloc((size_t)nc * nc * nc * sizeof(double));
+  int box, i, j, k;
+  hpgmg_dense_unpack(Lc, id, uc, HPGMG_WHERE_HOST);
+  for (box = 0; box < Lf->num_my_boxes; box++) {
+    const box_type *B = &Lf->my_boxes[box];
+    if (!bnd_box_on_domain_face(Lf, B)) continue;
+    hpgmg_vector_download(v, B->vectors[id], (size_t)Lf->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      if (gi > 0 && gj > 0 && gk > 0 && gi < n - 1 && gj < n - 1 && gk < n - 1) continue;
+      v[ijk] = v[ijk] + bnd_interp_delta_faces(nc, gc, uc, Lc->h, mask, gi, gj, gk);
+    }
+    hpgmg_vector_upload(B->vectors[id], v, (size_t)Lf->box_volume);
+  }
+  free(uc); free(v); free(gc);
+}
+
 __attribute__((weak)) void hpgmg_boundary_interp(level_type *Lf, int id, level_type *Lc, const double *g_c) {
   const int n = Lf->dim.i, nc = Lc->dim.i, g0 = Lf->box_ghosts, dim = Lf->box_dim, jS = Lf->box_jStride, kS = Lf->box_kStride;
   double *gc = bnd_download(g_c, (size_t)6 * nc * nc), *v = (double *)malloc((size_t)Lf->box_volume * sizeof(double));
@@ -415,6 +505,8 @@ struct hpgmg_user_solver {
   int bnd;                     /* 1: f was set with boundary values (set_rhs_dirichlet): an F-cycle runs with the hook below */
   double **bnd_g, **bnd_phi;   /* per level: the boundary values g_l and their lift flux phi_l (plugin memory; allocated on first use) */
   double *app_g, *app_phi;     /* apply_dirichlet's g and phi on the finest level */
+  int mask;                    /* bit f: domain face f is a Neumann wall (hpgmg_user_create_faces); 0: every wall Dirichlet, or periodic */
+  double *wall0, **wall;       /* mask != 0: wall0 = wall[0]; per level, the wall beta of the Neumann faces (a boundary array; the level's own beta is 0 there) */
 };
 static int user_live = 0;              /* user solvers alive: the process-wide configuration belongs to them */
 static hpgmg_config user_cfg;
@@ -435,7 +527,45 @@ static int user_pack_status(int st) {
   return HPGMG_USER_OK;
 }
 
+static void user_bnd_alloc(hpgmg_user_solver *us);
+/* a face array of the coefficients into the finest level: with Neumann walls through the masked pack, which keeps their beta in wall[0] */
+static int user_pack_beta(hpgmg_user_solver *us, int id, const double *src, int where, int layout) {
+  level_type *L = &us->s.level_h;
+  if (!us->mask) return hpgmg_dense_pack(L, id, src, where, layout, HPGMG_DENSE_CHECK_POSITIVE);
+  return hpgmg_dense_pack_walls(L, id, src, where, layout, HPGMG_DENSE_CHECK_POSITIVE, us->mask, us->wall0);
+}
+/* after rebuild_operator + MGRebuildCoarse of a solver with Neumann walls: every level's wall beta, and the singular case.  Six Neumann walls
+ * without an a * alpha term leave the constants in the null space, as periodic Poisson does: the same path (MGRebuildCoarse has just reset it) */
+static void user_walls_rebuilt(hpgmg_user_solver *us) {
+  mg_type *G = &us->s.mg;
+  int l;
+  if (!us->mask) return;
+  for (l = 1; l < G->num_levels; l++) hpgmg_boundary_restrict(G->levels[l], us->wall[l], G->levels[l - 1], us->wall[l - 1]);
+  if (us->mask != 63) return;
+  for (l = 0; l < G->num_levels; l++) {
+    level_type *L = G->levels[l];
+    int alpha_is_zero = 1;
+    if (hpgmg_vectors_reserved() > VECTOR_ALPHA && L->active) alpha_is_zero = (dot(L, VECTOR_ALPHA, VECTOR_ALPHA) == 0.0);
+    if (us->s.a == 0 || alpha_is_zero) L->must_subtract_mean = 1;
+  }
+}
+
+static int user_create(int n, int box_dim, int bc, int mask, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out);
 int hpgmg_user_create(int n, int box_dim, int bc, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out) {
+  return user_create(n, box_dim, bc, 0, op, smoother, a, b, h, out);
+}
+int hpgmg_user_create_faces(int n, int box_dim, const int face_bc[6], int op, int smoother, double a, double b, double h, hpgmg_user_solver **out) {
+  int f, mask = 0;
+  if (out) *out = NULL;
+  if (!face_bc) return HPGMG_USER_BAD_ARGUMENT;
+  for (f = 0; f < 6; f++) {
+    if (face_bc[f] != HPGMG_FACE_DIRICHLET && face_bc[f] != HPGMG_FACE_NEUMANN) return HPGMG_USER_BAD_ARGUMENT;
+    if (face_bc[f] == HPGMG_FACE_NEUMANN) mask |= 1 << f;
+  }
+  return user_create(n, box_dim, BC_DIRICHLET, mask, op, smoother, a, b, h, out);       /* mask 0 is hpgmg_user_create's solver */
+}
+
+static int user_create(int n, int box_dim, int bc, int mask, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out) {
   const hpgmg_transport *T = hpgmg_get_transport();
   if (!out) return HPGMG_USER_BAD_ARGUMENT;
   *out = NULL;
@@ -456,6 +586,7 @@ int hpgmg_user_create(int n, int box_dim, int bc, int op, int smoother, double a
   hpgmg_user_solver *us = (hpgmg_user_solver *)calloc(1, sizeof(*us));
   hpgmg_solver *s = &us->s;
   us->n = n; us->bc = bc; us->operator_ok = us->rhs_ok = 1;
+  us->mask = mask;
   USER_QUIET(us);
   s->boxes_in_i = n / box_dim; s->box_dim = box_dim; s->my_rank = 0; s->num_ranks = 1;
   s->a = a; s->b = b; s->h = h;
@@ -467,14 +598,17 @@ int hpgmg_user_create(int n, int box_dim, int bc, int op, int smoother, double a
     double *ones = (double *)malloc(big * sizeof(double));
     size_t q;
     for (q = 0; q < big; q++) ones[q] = 1.0;
-    hpgmg_dense_pack(&s->level_h, VECTOR_BETA_I, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_FACE_I, HPGMG_DENSE_CHECK_POSITIVE);
-    hpgmg_dense_pack(&s->level_h, VECTOR_BETA_J, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_FACE_J, HPGMG_DENSE_CHECK_POSITIVE);
-    hpgmg_dense_pack(&s->level_h, VECTOR_BETA_K, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_FACE_K, HPGMG_DENSE_CHECK_POSITIVE);
+    if (mask) us->wall0 = hpgmg_vector_alloc((size_t)6 * n * n);
+    user_pack_beta(us, VECTOR_BETA_I, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_FACE_I);
+    user_pack_beta(us, VECTOR_BETA_J, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_FACE_J);
+    user_pack_beta(us, VECTOR_BETA_K, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_FACE_K);
     if (cfg.helmholtz) hpgmg_dense_pack(&s->level_h, VECTOR_ALPHA, ones, HPGMG_WHERE_HOST, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_NONNEGATIVE);
     free(ones);
   }
   rebuild_operator(&s->level_h, NULL, a, b);
-  MGBuild(&s->mg, &s->level_h, a, b, bc == BC_PERIODIC ? 2 : 1);
+  /* six Neumann walls: a level of one cell would have Aii = 0 for Poisson, so stop at 2^3 as the periodic case does */
+  MGBuild(&s->mg, &s->level_h, a, b, (bc == BC_PERIODIC || mask == 63) ? 2 : 1);
+  if (mask) { user_bnd_alloc(us); user_walls_rebuilt(us); }
   USER_LOUD();
   *out = us;
   return HPGMG_USER_OK;
@@ -485,9 +619,9 @@ void hpgmg_user_destroy(hpgmg_user_solver *us) {
   USER_QUIET(us);
   if (us->bnd_g) {
     int l;
-    for (l = 0; l < us->s.mg.num_levels; l++) { hpgmg_vector_free(us->bnd_g[l]); hpgmg_vector_free(us->bnd_phi[l]); }
+    for (l = 0; l < us->s.mg.num_levels; l++) { hpgmg_vector_free(us->bnd_g[l]); hpgmg_vector_free(us->bnd_phi[l]); if (us->wall) hpgmg_vector_free(us->wall[l]); }
     hpgmg_vector_free(us->app_g); hpgmg_vector_free(us->app_phi);
-    free(us->bnd_g); free(us->bnd_phi);
+    free(us->bnd_g); free(us->bnd_phi); free(us->wall);
   }
   MGDestroy(&us->s.mg);
   destroy_level(&us->s.level_h);     /* frees the plugin's staging buffer with the level */
@@ -509,17 +643,18 @@ int hpgmg_user_set_coefficients(hpgmg_user_solver *us, const double *alpha, cons
   USER_QUIET(us);
   us->operator_ok = 0;
   if (us->bnd) us->rhs_ok = 0;           /* the lifted f and every phi_l were made with the old beta: a new set_rhs_dirichlet is needed */
-  if ((e = hpgmg_dense_pack(L, VECTOR_BETA_I, beta_i, where, HPGMG_DENSE_FACE_I, HPGMG_DENSE_CHECK_POSITIVE)) < 0) goto refused;
+  if ((e = user_pack_beta(us, VECTOR_BETA_I, beta_i, where, HPGMG_DENSE_FACE_I)) < 0) goto refused;
   st |= e;
-  if ((e = hpgmg_dense_pack(L, VECTOR_BETA_J, beta_j, where, HPGMG_DENSE_FACE_J, HPGMG_DENSE_CHECK_POSITIVE)) < 0) goto refused;
+  if ((e = user_pack_beta(us, VECTOR_BETA_J, beta_j, where, HPGMG_DENSE_FACE_J)) < 0) goto refused;
   st |= e;
-  if ((e = hpgmg_dense_pack(L, VECTOR_BETA_K, beta_k, where, HPGMG_DENSE_FACE_K, HPGMG_DENSE_CHECK_POSITIVE)) < 0) goto refused;
+  if ((e = user_pack_beta(us, VECTOR_BETA_K, beta_k, where, HPGMG_DENSE_FACE_K)) < 0) goto refused;
   st |= e;
   if (helmholtz && (e = hpgmg_dense_pack(L, VECTOR_ALPHA, alpha, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_NONNEGATIVE)) < 0) goto refused;
   if (helmholtz) st |= e;
   if (st) { USER_LOUD(); return user_pack_status(st); }
   rebuild_operator(L, NULL, s->a, s->b);
   MGRebuildCoarse(&s->mg, s->a, s->b);
+  user_walls_rebuilt(us);
   us->operator_ok = 1;
   USER_LOUD();
   return HPGMG_USER_OK;
@@ -531,6 +666,7 @@ refused:
 int hpgmg_user_set_rhs(hpgmg_user_solver *us, const double *f, int where, double *mean_shift) {
   level_type *L = &us->s.level_h;
   if (!f) return HPGMG_USER_BAD_ARGUMENT;
+  if (us->mask) return hpgmg_user_set_rhs_dirichlet(us, f, NULL, where, mean_shift);     /* Neumann walls: zero data on every face, the F-cycle keeps its hook */
   USER_QUIET(us);
   const int st = user_pack_status(hpgmg_dense_pack(L, VECTOR_F, f, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
   us->rhs_ok = (st == HPGMG_USER_OK);
@@ -552,10 +688,12 @@ static void user_bnd_alloc(hpgmg_user_solver *us) {
   if (us->bnd_g) return;
   us->bnd_g = (double **)calloc((size_t)G->num_levels, sizeof(double *));
   us->bnd_phi = (double **)calloc((size_t)G->num_levels, sizeof(double *));
+  if (us->mask) us->wall = (double **)calloc((size_t)G->num_levels, sizeof(double *));
   for (l = 0; l < G->num_levels; l++) {
     const size_t n = (size_t)G->levels[l]->dim.i;
     us->bnd_g[l] = hpgmg_vector_alloc(6 * n * n);
     us->bnd_phi[l] = hpgmg_vector_alloc(6 * n * n);
+    if (us->mask) us->wall[l] = l ? hpgmg_vector_alloc(6 * n * n) : us->wall0;
   }
   us->app_g = hpgmg_vector_alloc((size_t)6 * us->n * us->n);
   us->app_phi = hpgmg_vector_alloc((size_t)6 * us->n * us->n);
@@ -571,20 +709,32 @@ int hpgmg_user_set_rhs_dirichlet(hpgmg_user_solver *us, const double *f, const d
   level_type *L = &s->level_h;
   int l;
   if (mean_shift) *mean_shift = 0.0;
-  if (!f || !g || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
+  if (!f || (!g && !us->mask) || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
   if (us->bc != BC_DIRICHLET) return HPGMG_USER_UNSUPPORTED;
   USER_QUIET(us);
   user_bnd_alloc(us);
   us->bnd = 0; us->mean_shift = 0.0;
-  user_bnd_take(us, us->bnd_g[0], g, where);
-  const int st = user_pack_status(hpgmg_dense_pack_lifted(L, VECTOR_F, f, where, us->bnd_g[0], s->b));     /* F = f + T(g) */
+  if (g) user_bnd_take(us, us->bnd_g[0], g, where);
+  else {                             /* a solver with Neumann walls and no data: zero on every face */
+    double *zero = (double *)calloc((size_t)6 * us->n * us->n, sizeof(double));
+    hpgmg_vector_upload(us->bnd_g[0], zero, (size_t)6 * us->n * us->n);
+    free(zero);
+  }
+  const int st = user_pack_status(us->mask ? hpgmg_dense_pack_lifted_faces(L, VECTOR_F, f, where, us->bnd_g[0], s->b, us->mask, us->wall[0])
+                                           : hpgmg_dense_pack_lifted(L, VECTOR_F, f, where, us->bnd_g[0], s->b));     /* F = f + T(g) */
   us->rhs_ok = (st == HPGMG_USER_OK);
   if (us->rhs_ok) {                  /* g_l and phi_l of every level, for the F-cycle's right-hand-side correction */
     for (l = 0; l < s->mg.num_levels; l++) {
       if (l > 0) hpgmg_boundary_restrict(s->mg.levels[l], us->bnd_g[l], s->mg.levels[l - 1], us->bnd_g[l - 1]);
-      hpgmg_boundary_flux(s->mg.levels[l], us->bnd_phi[l], us->bnd_g[l], s->b);
+      if (us->mask) hpgmg_boundary_flux_faces(s->mg.levels[l], us->bnd_phi[l], us->bnd_g[l], s->b, us->mask, us->wall[l]);
+      else hpgmg_boundary_flux(s->mg.levels[l], us->bnd_phi[l], us->bnd_g[l], s->b);
     }
     us->bnd = 1;
+    if (L->must_subtract_mean) {     /* six Neumann walls without an a * alpha term: only a mean-free f + T(g) has a solution */
+      const double avg = mean(L, VECTOR_F);
+      if (avg != 0.0) { shift_vector(L, VECTOR_F, VECTOR_F, -avg); us->mean_shift = avg; }
+      if (mean_shift) *mean_shift = us->mean_shift;
+    }
   }
   USER_LOUD();
   return st;
@@ -598,7 +748,8 @@ static void user_bnd_restricted(const hpgmg_fmg_hook *hook, mg_type *G, int l, i
 /* after interpolation_fcycle onto level l: the fine cells that read a coarse ghost get what the inhomogeneous ghost adds */
 static void user_bnd_interpolated(const hpgmg_fmg_hook *hook, mg_type *G, int l, int e_id) {
   const hpgmg_user_solver *us = (const hpgmg_user_solver *)hook->ctx;
-  hpgmg_boundary_interp(G->levels[l], e_id, G->levels[l + 1], us->bnd_g[l + 1]);
+  if (us->mask) hpgmg_boundary_interp_faces(G->levels[l], e_id, G->levels[l + 1], us->bnd_g[l + 1], us->mask);
+  else hpgmg_boundary_interp(G->levels[l], e_id, G->levels[l + 1], us->bnd_g[l + 1]);
 }
 
 int hpgmg_user_solve(hpgmg_user_solver *us, int method, double rtol, const double *u0, int where, hpgmg_user_info *info) {
@@ -677,7 +828,8 @@ int hpgmg_user_apply_dirichlet(hpgmg_user_solver *us, const double *x, const dou
   USER_QUIET(us);
   user_bnd_alloc(us);
   user_bnd_take(us, us->app_g, g, where);
-  int st = user_pack_status(hpgmg_boundary_flux(L, us->app_phi, us->app_g, s->b));
+  int st = user_pack_status(us->mask ? hpgmg_boundary_flux_faces(L, us->app_phi, us->app_g, s->b, us->mask, us->wall[0])
+                                     : hpgmg_boundary_flux(L, us->app_phi, us->app_g, s->b));
   if (st == HPGMG_USER_OK) st = user_pack_status(hpgmg_dense_pack(L, us->x_id, x, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
   if (st == HPGMG_USER_OK) {
     apply_op(L, VECTOR_R, us->x_id, s->a, s->b);

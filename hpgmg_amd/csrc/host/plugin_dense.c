@@ -87,3 +87,57 @@ void hpgmg_boundary_lift(level_type *L, int id, const double *phi, const double 
 void hpgmg_boundary_interp(level_type *Lf, int id, level_type *Lc, const double *g_c) {
   HIP_OK(hpgmg_hip_boundary_interp(&hp_backend_of(Lf)->dev, id, g_c, Lc->dim.i));
 }
+
+/* Neumann walls (include/hpgmg_operators.h): the same launches with per-face kinds */
+static double bnd_weight_neumann(const level_type *L, double b) { return b * (1.0 / L->h); }
+
+int hpgmg_dense_pack_walls(level_type *L, int id, const double *src, int where, int layout, int check, int mask, double *wall) {
+  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || layout < HPGMG_DENSE_FACE_I || layout > HPGMG_DENSE_FACE_K || !src || !wall) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  if (mask < 0 || mask > 63 || L->boundary_condition.type != BC_DIRICHLET || L->dim.i != L->dim.j || L->dim.i != L->dim.k) return -1;
+  backend_t *B = hp_backend_of(L);
+  const size_t ni = dense_extent(L, layout, 0), nj = dense_extent(L, layout, 1), nk = dense_extent(L, layout, 2);
+  const double *d_src = src;
+  int status = 0;
+  if (where == HPGMG_WHERE_HOST) {
+    double *stage = dense_stage(B, ni * nj * nk);
+    HIP_OK(hpgmg_hip_memcpy_h2d(stage, src, ni * nj * nk * sizeof(double)));
+    d_src = stage;
+  }
+  HIP_OK(hpgmg_hip_dense_pack_walls(&B->dev, id, d_src, layout - HPGMG_DENSE_FACE_I, check, mask, wall, &status));
+  return status;
+}
+
+int hpgmg_dense_pack_lifted_faces(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
+  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || !f || !g || L->boundary_condition.type != BC_DIRICHLET) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
+  backend_t *B = hp_backend_of(L);
+  const size_t n = (size_t)L->dim.i * L->dim.j * L->dim.k;
+  const double *d_src = f;
+  int status = 0;
+  if (where == HPGMG_WHERE_HOST) {
+    double *stage = dense_stage(B, n);
+    HIP_OK(hpgmg_hip_memcpy_h2d(stage, f, n * sizeof(double)));
+    d_src = stage;
+  }
+  HIP_OK(hpgmg_hip_dense_pack_lifted_faces(&B->dev, id, d_src, g, bnd_weight(L, b), mask, wall, bnd_weight_neumann(L, b), &status));
+  return status;
+}
+
+int hpgmg_boundary_flux_faces(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
+  int status = 0;
+  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
+  HIP_OK(hpgmg_hip_boundary_flux_faces(&hp_backend_of(L)->dev, phi, g, bnd_weight(L, b), mask, wall, bnd_weight_neumann(L, b), &status));
+  return status;
+}
+
+void hpgmg_boundary_interp_faces(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) {
+  int nb = Lc->dim.i / Lc->box_dim, bx;          /* the kernel's box formula holds when the coarse boxes are in i-fastest order */
+  if (Lc->num_my_boxes != nb * nb * nb) nb = 0;
+  for (bx = 0; nb && bx < Lc->num_my_boxes; bx++) {
+    const box_type *X = &Lc->my_boxes[bx];
+    if (X->low.i != (bx % nb) * Lc->box_dim || X->low.j != ((bx / nb) % nb) * Lc->box_dim || X->low.k != (bx / (nb * nb)) * Lc->box_dim) nb = 0;
+  }
+  HIP_OK(hpgmg_hip_boundary_interp_faces(&hp_backend_of(Lf)->dev, id, &hp_backend_of(Lc)->dev, nb, g_c, Lc->h, mask));
+}

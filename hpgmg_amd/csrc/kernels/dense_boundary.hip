@@ -1,5 +1,6 @@
 // dense_boundary.hip -- inhomogeneous Dirichlet values of the dense-array API (include/hpgmg_operators.h hpgmg_dense_pack_lifted,
-// hpgmg_boundary_flux / _restrict / _lift / _interp; the formulas and their order are written there and in DESIGN.md §11).
+// hpgmg_boundary_flux / _restrict / _lift / _interp and their per-face-kind forms for Neumann walls; the formulas and their order are written
+// there and in DESIGN.md §11.1, §11.2).
 //
 // A boundary array is 6 x n x n doubles (n = the level's cells per side, a cube): [0], [1] i-low / i-high indexed [k][j], [2], [3] j-low /
 // j-high [k][i], [4], [5] k-low / k-high [j][i].  w = (2.0 * b) * (1.0 / (h * h)) comes from the host, so every term (w * beta) * g has the
@@ -48,8 +49,11 @@ __device__ __forceinline__ FacePos bnd_face_pos(const hpgmg_hip_level &L, int li
   return P;
 }
 
+// mask, wall, wn (lifted pack and flux): bit f of mask set = face f is a Neumann wall, whose entry is (wn * wall[e]) * gn with
+// wn = b * (1.0 / h) from the host and wall the level's wall-beta array; mask 0 leaves every expression as it was.
 __global__ __launch_bounds__(kBndThreads) void dense_pack_lifted_kernel(const hpgmg_hip_level L, int id, const double *__restrict__ src,
-                                                                        const double *__restrict__ g, double w, int *flag) {
+                                                                        const double *__restrict__ g, double w, int mask,
+                                                                        const double *__restrict__ wall, double wn, int *flag) {
   const int gh = L.ghosts, dim = L.dim, n = L.dim_i;
   int bits = 0;
   for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
@@ -68,10 +72,12 @@ __global__ __launch_bounds__(kBndThreads) void dense_pack_lifted_kernel(const hp
         if (gi == 0 || gj == 0 || gk == 0 || gi == n - 1 || gj == n - 1 || gk == n - 1) {
           double T = 0.0;
           for (int face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
-            const double gv = g[bnd_entry(n, face, gi, gj, gk)];
+            const int e = bnd_entry(n, face, gi, gj, gk);
+            const double gv = g[e];
             if (!isfinite(gv)) bits |= HPGMG_DENSE_NOT_FINITE;
             const double *beta = face < 2 ? bi : face < 4 ? bj : bk;
-            T = T + (w * beta[ofs + bnd_beta_step(L, face)]) * gv;
+            if ((mask >> face) & 1) T = T + (wn * wall[e]) * gv;
+            else T = T + (w * beta[ofs + bnd_beta_step(L, face)]) * gv;
           }
           v = v + T;
         }
@@ -83,7 +89,8 @@ __global__ __launch_bounds__(kBndThreads) void dense_pack_lifted_kernel(const hp
 }
 
 __global__ __launch_bounds__(kBndThreads) void boundary_flux_kernel(const hpgmg_hip_level L, double *__restrict__ phi,
-                                                                    const double *__restrict__ g, double w, int *flag) {
+                                                                    const double *__restrict__ g, double w, int mask,
+                                                                    const double *__restrict__ wall, double wn, int *flag) {
   const int n = L.dim_i, positions = 6 * L.dim * L.dim;
   int bits = 0;
   for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
@@ -97,6 +104,7 @@ __global__ __launch_bounds__(kBndThreads) void boundary_flux_kernel(const hpgmg_
       const int e = bnd_entry(n, face, gi, gj, gk);
       const double gv = g[e];
       if (!isfinite(gv)) bits |= HPGMG_DENSE_NOT_FINITE;
+      if ((mask >> face) & 1) { phi[e] = (wn * wall[e]) * gv; continue; }
       const double beta = vec_origin(L, box, bnd_beta_vec(face))[i + j * L.jStride + k * L.kStride + bnd_beta_step(L, face)];
       phi[e] = (w * beta) * gv;
     }
@@ -196,6 +204,69 @@ __global__ __launch_bounds__(kBndThreads) void boundary_interp_kernel(const hpgm
   }
 }
 
+// the coarse iterate at the in-range cell (i, j, k): read in the box that owns it.  nb > 0: the boxes are in i-fastest order, nb per side
+// (checked by the host); else the owner is searched for.
+__device__ __forceinline__ double bnd_coarse_cell(const hpgmg_hip_level &Lc, int id, int nb, int i, int j, int k) {
+  int box = 0;
+  if (nb > 0) box = i / Lc.dim + nb * (j / Lc.dim + nb * (k / Lc.dim));
+  else for (; box < Lc.num_boxes - 1; box++) {
+    const int li = Lc.box_low[3 * box], lj = Lc.box_low[3 * box + 1], lk = Lc.box_low[3 * box + 2];
+    if (i >= li && i < li + Lc.dim && j >= lj && j < lj + Lc.dim && k >= lk && k < lk + Lc.dim) break;
+  }
+  const int li = Lc.box_low[3 * box], lj = Lc.box_low[3 * box + 1], lk = Lc.box_low[3 * box + 2];
+  return vec_origin(Lc, box, id)[(i - li) + (j - lj) * Lc.jStride + (k - lk) * Lc.kStride];
+}
+
+// host/driver.c bnd_ghost_delta_faces, expression for expression
+#define BND_AT(f, i, j, k) g[((f) * n + ((f) < 4 ? (k) : (j))) * n + ((f) < 2 ? (j) : (i))]
+__device__ __forceinline__ double bnd_ghost_delta_faces(const hpgmg_hip_level &Lc, int id, int nb, const double *g, double hc, int mask,
+                                                        int ci, int cj, int ck) {
+  const int n = Lc.dim_i;
+  const int q[3] = { ci, cj, ck };
+  int out[3], P[3], face[3], a, m = 0, dirichlet = 0;
+  for (a = 0; a < 3; a++) {
+    out[a] = q[a] < 0 || q[a] >= n;
+    P[a] = q[a] < 0 ? 0 : q[a] >= n ? n - 1 : q[a];
+    face[a] = 2 * a + (q[a] >= n);
+    m += out[a];
+    dirichlet += out[a] && !((mask >> face[a]) & 1);
+  }
+  if (dirichlet == m) return bnd_ghost_delta(n, g, ci, cj, ck);
+  double s = 0.0;
+  for (a = 0; a < 3; a++) if (out[a]) {
+    const double ga = BND_AT(face[a], P[0], P[1], P[2]);
+    s = s + (((mask >> face[a]) & 1) ? hc * ga : 2.0 * ga);
+  }
+  const double c = (double)(1 - 2 * dirichlet + ((m & 1) ? 1 : -1));
+  return c * bnd_coarse_cell(Lc, id, nb, P[0], P[1], P[2]) + s;
+}
+#undef BND_AT
+
+// boundary_interp_kernel with per-face kinds: Lc, nb locate the coarse iterate (vector id of the coarse level), hc is the coarse h
+__global__ __launch_bounds__(kBndThreads) void boundary_interp_faces_kernel(const hpgmg_hip_level L, int id, const hpgmg_hip_level Lc, int nb,
+                                                                            const double *__restrict__ gc, double hc, int mask) {
+  const int positions = 6 * L.dim * L.dim, nc = Lc.dim_i;
+  const double wt[8] = { 0.421875, 0.140625, 0.140625, 0.046875, 0.140625, 0.046875, 0.046875, 0.015625 };
+  for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
+    const int li = L.box_low[3 * box], lj = L.box_low[3 * box + 1], lk = L.box_low[3 * box + 2];
+    double *v = vec_origin(L, box, id);
+    for (int t = (int)(blockIdx.x * kBndThreads + threadIdx.x); t < positions; t += (int)(gridDim.x * kBndThreads)) {
+      const FacePos P = bnd_face_pos(L, li, lj, lk, t);
+      if (!P.on) continue;
+      const int gi = li + P.i, gj = lj + P.j, gk = lk + P.k;
+      const int ci = gi >> 1, cj = gj >> 1, ck = gk >> 1, di = (gi & 1) ? 1 : -1, dj = (gj & 1) ? 1 : -1, dk = (gk & 1) ? 1 : -1;
+      double D = 0.0;
+#pragma unroll
+      for (int s = 1; s < 8; s++) {       // interpolation_p1's reads after the centre
+        const int qi = ci + ((s >> 2) & 1) * di, qj = cj + ((s >> 1) & 1) * dj, qk = ck + (s & 1) * dk;
+        if (qi < 0 || qi >= nc || qj < 0 || qj >= nc || qk < 0 || qk >= nc) D = D + wt[s] * bnd_ghost_delta_faces(Lc, id, nb, gc, hc, mask, qi, qj, qk);
+      }
+      const int c = P.i + P.j * L.jStride + P.k * L.kStride;
+      v[c] = v[c] + D;
+    }
+  }
+}
+
 static dim3 bnd_grid(int per_box, int boxes) {       // x: the positions of one box, y: the boxes (the rest of either by grid stride)
   const int blocks = (per_box + kBndThreads - 1) / kBndThreads;
   return dim3(blocks < 16384 ? (blocks > 0 ? blocks : 1) : 16384, boxes < 65535 ? boxes : 65535);
@@ -209,28 +280,41 @@ using namespace hpgmg;
 extern "C" {
 int hpgmg_hip_graph_flush(void);
 
+int hpgmg_hip_dense_pack_lifted_faces(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int mask, const double *wall,
+                                      double wn, int *status);
+int hpgmg_hip_boundary_flux_faces(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn, int *status);
 int hpgmg_hip_dense_pack_lifted(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int *status) {
+  return hpgmg_hip_dense_pack_lifted_faces(L, id, src, g, w, 0, nullptr, 0.0, status);
+}
+int hpgmg_hip_boundary_flux(const hpgmg_hip_level *L, double *phi, const double *g, double w, int *status) {
+  return hpgmg_hip_boundary_flux_faces(L, phi, g, w, 0, nullptr, 0.0, status);
+}
+
+int hpgmg_hip_dense_pack_lifted_faces(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int mask, const double *wall,
+                                      double wn, int *status) {
   *status = 0;
+  if (mask < 0 || mask > 63 || (mask && !wall)) return record_error(hipErrorInvalidValue, "dense_pack_lifted: a wall mask without the wall betas");
   if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "dense_pack_lifted: the level is not a Dirichlet cube");
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
   if (!g_bnd_flag) HPGMG_CHECK(hipMalloc((void **)&g_bnd_flag, sizeof(int)));
   HPGMG_CHECK(hipMemsetAsync(g_bnd_flag, 0, sizeof(int), g_stream));
-  hipLaunchKernelGGL(dense_pack_lifted_kernel, bnd_grid(L->volume, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, src, g, w, g_bnd_flag);
+  hipLaunchKernelGGL(dense_pack_lifted_kernel, bnd_grid(L->volume, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, src, g, w, mask, wall, wn, g_bnd_flag);
   HPGMG_LAUNCH_CHECK("dense_pack_lifted_kernel");
   HPGMG_CHECK(hipMemcpyAsync(status, g_bnd_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
   HPGMG_CHECK(hipStreamSynchronize(g_stream));
   return 0;
 }
 
-int hpgmg_hip_boundary_flux(const hpgmg_hip_level *L, double *phi, const double *g, double w, int *status) {
+int hpgmg_hip_boundary_flux_faces(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn, int *status) {
   *status = 0;
+  if (mask < 0 || mask > 63 || (mask && !wall)) return record_error(hipErrorInvalidValue, "boundary_flux: a wall mask without the wall betas");
   if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "boundary_flux: the level is not a Dirichlet cube");
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
   if (!g_bnd_flag) HPGMG_CHECK(hipMalloc((void **)&g_bnd_flag, sizeof(int)));
   HPGMG_CHECK(hipMemsetAsync(g_bnd_flag, 0, sizeof(int), g_stream));
-  hipLaunchKernelGGL(boundary_flux_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, phi, g, w, g_bnd_flag);
+  hipLaunchKernelGGL(boundary_flux_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, phi, g, w, mask, wall, wn, g_bnd_flag);
   HPGMG_LAUNCH_CHECK("boundary_flux_kernel");
   HPGMG_CHECK(hipMemcpyAsync(status, g_bnd_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
   HPGMG_CHECK(hipStreamSynchronize(g_stream));
@@ -260,6 +344,19 @@ int hpgmg_hip_boundary_interp(const hpgmg_hip_level *L, int id, const double *g_
   if (L->num_boxes <= 0) return 0;
   hipLaunchKernelGGL(boundary_interp_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, g_c, n_c);
   HPGMG_LAUNCH_CHECK("boundary_interp_kernel");
+  return 0;
+}
+
+int hpgmg_hip_boundary_interp_faces(const hpgmg_hip_level *L, int id, const hpgmg_hip_level *Lc, int boxes_per_side, const double *g_c, double h_c, int mask) {
+  HPGMG_SKIP_IF_REPLAY();
+  if (!bnd_cube(L) || !bnd_cube(Lc) || 2 * Lc->dim_i != L->dim_i || mask < 0 || mask > 63 || Lc->num_boxes <= 0)
+    return record_error(hipErrorInvalidValue, "boundary_interp_faces: the levels are not a Dirichlet cube and its coarsening");
+  if (boxes_per_side > 0 && (boxes_per_side * Lc->dim != Lc->dim_i || boxes_per_side * boxes_per_side * boxes_per_side != Lc->num_boxes))
+    return record_error(hipErrorInvalidValue, "boundary_interp_faces: the coarse boxes do not tile the cube");
+  if (L->num_boxes <= 0) return 0;
+  hipLaunchKernelGGL(boundary_interp_faces_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, *Lc, boxes_per_side,
+                     g_c, h_c, mask);
+  HPGMG_LAUNCH_CHECK("boundary_interp_faces_kernel");
   return 0;
 }
 

@@ -13,6 +13,12 @@ array as the call's others): boundary[0], [1] the i-low / i-high faces indexed [
 k-low / k-high indexed [j][i].  A boundary cell's ghost is 2 g - u instead of -u, so the solve is A0 u = f + T(g), and
 apply(x, boundary=g) is A0 x - T(g).  Solver.boundary_from(fn) samples fn(x, y, z) at the face centres.
 
+Neumann and mixed walls: bc="neumann", or a 6-tuple of "dirichlet" / "neumann" in the face order of `boundary` (i-low, i-high, j-low, j-high,
+k-low, k-high).  On a Neumann face the entry of `boundary` is the OUTWARD normal derivative du/dn at the face centre (the ghost is u + h du/dn)
+and boundary=None is zero data on every face.  The beta arrays keep their Dirichlet shapes; a Neumann wall's beta (still > 0) weighs its data.
+Six Neumann faces without an a alpha term determine u up to a constant: the mean of f + T(boundary) is subtracted (mean_shift) and the
+mean-free u is returned.  Periodic cannot be mixed per face.  DESIGN.md §11.2.
+
 NumPy arrays take the host path.  torch tensors on the library's GPU (float64, contiguous) are read and written in place, and results come
 back as tensors on that device.  torch must be imported before this package loads its libraries: both bring a HIP runtime
 (libamdhip64.so.7), and a device pointer is only valid inside the runtime that made it.  The C entry points are hpgmg_user_* of
@@ -26,6 +32,7 @@ import numpy as np
 import hpgmg_amd as H
 
 _BC = {"dirichlet": H.BC_DIRICHLET, "periodic": H.BC_PERIODIC}
+_FACE = {"dirichlet": H.FACE_DIRICHLET, "neumann": H.FACE_NEUMANN}
 _SMOOTHER = {"cheby": H.SMOOTH_CHEBY, "chebyshev": H.SMOOTH_CHEBY, "gsrb": H.SMOOTH_GSRB, "jacobi": H.SMOOTH_JACOBI}
 _OPERATOR = {"7pt": H.OP_7PT, "27pt": H.OP_27PT, "fv4": H.OP_FV4, "fv2": H.OP_FV2}
 _METHOD = {"fmg": H.USER_FMG, "mg": H.USER_MG}
@@ -73,20 +80,38 @@ class Solver:
     """One user problem.  `lib` is the driver library to run on (default: the HIP build, hpgmg_amd.load_driver())."""
 
     def __init__(self, n, box_dim=None, bc="dirichlet", smoother="cheby", a=0.0, b=1.0, h=None, operator="7pt", lib=None, verbose=False):
-        if bc not in _BC:
-            raise ValueError(f"bc: {bc!r} is not one of {sorted(_BC)}")
+        faces = None                    # per-face kinds of a solver with at least one Neumann wall; None: the dirichlet / periodic solver
+        if isinstance(bc, str) and bc == "neumann":
+            bc = ("neumann",) * 6
+        if isinstance(bc, (tuple, list)):
+            if len(bc) != 6:
+                raise ValueError(f"bc: a tuple needs 6 entries (i-low, i-high, j-low, j-high, k-low, k-high), got {len(bc)}")
+            for kind in bc:
+                if kind == "periodic":
+                    raise ValueError("bc: periodic cannot be mixed per face (pass bc='periodic' for a periodic box)")
+                if not isinstance(kind, str) or kind not in _FACE:
+                    raise ValueError(f"bc: {kind!r} is not one of {sorted(_FACE)}")
+            faces = tuple(bc) if "neumann" in bc else None
+            bc = "dirichlet"            # the shapes and the level's boundary condition; six Dirichlet faces are the "dirichlet" solver
+        elif not isinstance(bc, str) or bc not in _BC:
+            raise ValueError(f"bc: {bc!r} is not one of {sorted(_BC) + ['neumann']} or a 6-tuple of {sorted(_FACE)}")
         if smoother not in _SMOOTHER:
             raise ValueError(f"smoother: {smoother!r} is not one of {sorted(_SMOOTHER)}")
         if operator not in _OPERATOR:
             raise ValueError(f"operator: {operator!r} is not one of {sorted(_OPERATOR)}")
         self.lib = lib if lib is not None else H.load_driver()
         self.hip = self.lib.hpgmg_backend_name() == b"hip"
-        self.n, self.bc, self.a, self.b = int(n), bc, float(a), float(b)
+        self.n, self.bc, self.faces, self.a, self.b = int(n), bc, faces, float(a), float(b)
         self.h = float(h) if h is not None and h > 0 else 1.0 / self.n
         self._ptr = None
         out = ctypes.c_void_p()
-        st = self.lib.hpgmg_user_create(self.n, int(box_dim or 0), _BC[bc], _OPERATOR[operator], _SMOOTHER[smoother], self.a, self.b,
-                                        float(h or 0.0), ctypes.byref(out))
+        if faces is None:
+            st = self.lib.hpgmg_user_create(self.n, int(box_dim or 0), _BC[bc], _OPERATOR[operator], _SMOOTHER[smoother], self.a, self.b,
+                                            float(h or 0.0), ctypes.byref(out))
+        else:
+            kinds = (ctypes.c_int * 6)(*[_FACE[k] for k in faces])
+            st = self.lib.hpgmg_user_create_faces(self.n, int(box_dim or 0), kinds, _OPERATOR[operator], _SMOOTHER[smoother], self.a, self.b,
+                                                  float(h or 0.0), ctypes.byref(out))
         self._check(st, "operator" if st == H.USER_UNSUPPORTED else "n, box_dim, a, b or h")
         self._ptr = out.value
         if verbose:
@@ -192,9 +217,12 @@ class Solver:
             raise ValueError(f"boundary: boundary values need a Dirichlet domain (this solver is {self.bc})")
         return self._arg(g, (6, self.n, self.n), "boundary", kind)[0]
 
-    def boundary_from(self, fn):
+    def boundary_from(self, fn, grad=None):
         """Boundary values sampled from fn(x, y, z) (NumPy arrays in, an array of their shape out) at the 6 N^2 face centres: cell (i,j,k) is
-        centred at ((i+1/2)h, (j+1/2)h, (k+1/2)h), so the faces lie at 0 and N h.  Returns the (6,N,N) NumPy array that boundary= takes."""
+        centred at ((i+1/2)h, (j+1/2)h, (k+1/2)h), so the faces lie at 0 and N h.  Returns the (6,N,N) NumPy array that boundary= takes.
+        A Neumann face takes the outward normal derivative from grad(x, y, z), which returns the three components of grad u."""
+        if self.faces is not None and grad is None:
+            raise ValueError("grad: required when a face is Neumann (grad(x, y, z) returns the three components of grad u)")
         n, h = self.n, self.h
         c = (np.arange(n) + 0.5) * h
         slow, fast = np.meshgrid(c, c, indexing="ij")          # entry [q][p]: p the faster index
@@ -207,11 +235,16 @@ class Solver:
                 x, y, z = fast, wall, slow                       # [k][i]
             else:
                 x, y, z = fast, slow, wall                       # [j][i]
-            g[face] = np.broadcast_to(np.asarray(fn(x, y, z), dtype=np.float64), (n, n))
+            if self.faces is not None and self.faces[face] == "neumann":
+                normal = np.asarray(grad(x, y, z)[face // 2], dtype=np.float64)
+                g[face] = np.broadcast_to(normal if face & 1 else -normal, (n, n))
+            else:
+                g[face] = np.broadcast_to(np.asarray(fn(x, y, z), dtype=np.float64), (n, n))
         return g
 
     def set_rhs(self, f, boundary=None):
-        """Packs f (with boundary values: f + T(boundary)); returns the mean subtracted from f (periodic without an a alpha term), else 0.0."""
+        """Packs f (with boundary values: f + T(boundary)); returns the mean subtracted from it (periodic, or six Neumann faces, without an
+        a alpha term), else 0.0."""
         p, where, kind = self._arg(f, (self.n,) * 3, "f")
         shift = ctypes.c_double(0.0)
         if boundary is None:

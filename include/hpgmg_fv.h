@@ -96,6 +96,14 @@ int  hpgmg_user_apply(hpgmg_user_solver *s, const double *x, double *y, int wher
  * apply_dirichlet: y = A0 x - T(g), the residual operator of the boundary-value problem.  A periodic solver: HPGMG_USER_UNSUPPORTED. */
 int  hpgmg_user_set_rhs_dirichlet(hpgmg_user_solver *s, const double *f, const double *g, int where, double *mean_shift);
 int  hpgmg_user_apply_dirichlet(hpgmg_user_solver *s, const double *x, const double *g, double *y, int where);
+/* Neumann and mixed walls: hpgmg_user_create with one kind per domain face, in the order of g's faces (i-low, i-high, j-low,
+ * j-high, k-low, k-high).  Six HPGMG_FACE_DIRICHLET is hpgmg_user_create(BC_DIRICHLET)'s solver.  On a Neumann face the ghost is u + h gn, gn the
+ * OUTWARD normal derivative: the entry of g that set_rhs_dirichlet / apply_dirichlet take for that face (Dirichlet faces keep u's value).  The
+ * beta arrays keep their Dirichlet shapes; a Neumann wall's beta (still > 0) weighs its data, phi = ((b * (1.0 / h)) * beta) * gn, and the operator
+ * A_N has 0 there.  set_rhs on such a solver is set_rhs_dirichlet with zero data.  Six Neumann faces without an a alpha term: the constants are in
+ * the null space, so set_rhs* subtracts the mean of f + T(g) (*mean_shift) and the solution is the mean-free one. */
+enum { HPGMG_FACE_DIRICHLET = 0, HPGMG_FACE_NEUMANN = 1 };
+int  hpgmg_user_create_faces(int n, int box_dim, const int face_bc[6], int op, int smoother, double a, double b, double h, hpgmg_user_solver **out);
 
 /* ---- small accessors so a ctypes caller never needs the struct layouts ---- */
 enum { HPGMG_INFO_DIM = 0, HPGMG_INFO_BOX_DIM, HPGMG_INFO_GHOSTS, HPGMG_INFO_JSTRIDE, HPGMG_INFO_KSTRIDE,

@@ -360,6 +360,14 @@ int hpgmg_hip_boundary_flux(const hpgmg_hip_level *L, double *phi, const double 
 int hpgmg_hip_boundary_restrict(double *g_c, const double *g_f, int n_c);
 int hpgmg_hip_boundary_lift(const hpgmg_hip_level *L, int id, const double *phi, const double *phi_fine, double sign);
 int hpgmg_hip_boundary_interp(const hpgmg_hip_level *L, int id, const double *g_c, int n_c);
+/* the same with per-face kinds (Neumann walls; include/hpgmg_operators.h hpgmg_dense_pack_walls / *_faces): mask bit f = face f is Neumann, wall the
+ * level's wall-beta array, wn = b * (1.0 / h).  pack_walls: axis 0 / 1 / 2 = a FACE_I / J / K array.  interp_faces reads vector id of the coarse level
+ * Lc where each cell lives: boxes_per_side > 0 says its boxes are in i-fastest order, that many per side; 0 makes the kernel search for the owner. */
+int hpgmg_hip_dense_pack_walls(const hpgmg_hip_level *L, int id, const double *src, int axis, int check, int mask, double *wall, int *status);
+int hpgmg_hip_dense_pack_lifted_faces(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int mask, const double *wall,
+                                      double wn, int *status);
+int hpgmg_hip_boundary_flux_faces(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn, int *status);
+int hpgmg_hip_boundary_interp_faces(const hpgmg_hip_level *L, int id, const hpgmg_hip_level *Lc, int boxes_per_side, const double *g_c, double h_c, int mask);
 
 /* ---- operators/rebuild.c:47-208 black-box rebuild: accumulate one colouring (x = 0/1 pattern, ghosts
  *      already exchanged / BCs applied) into Aii and sum|Aij|, then turn them into Dinv, L1inv, lambda_max ---- */

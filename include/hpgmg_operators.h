@@ -155,6 +155,23 @@ int     hpgmg_boundary_flux(level_type *level, double *phi, const double *g, dou
 void    hpgmg_boundary_restrict(level_type *coarse, double *g_c, level_type *fine, const double *g_f);
 void    hpgmg_boundary_lift(level_type *level, int id, const double *phi, const double *phi_fine, double sign);
 void    hpgmg_boundary_interp(level_type *fine, int id, level_type *coarse, const double *g_c);
+/* Neumann and mixed walls.  mask: bit f set = domain face f (the order above) is a Neumann wall, whose entry of a boundary
+ * array is the OUTWARD normal derivative gn and whose ghost is u + h gn.  The level's beta is 0.0 on a Neumann wall (the operator A_N); the
+ * wall's own beta lives in `wall`, a boundary array (6 n^2; only the masked faces' entries are used), restricted with boundary_restrict.
+ *   pack_walls:         hpgmg_dense_pack of a face array (same pass, same checks of every value read), except that a value on a masked domain
+ *                       wall (index 0 of a box on the low wall, the high ghost layer dim of a box on the high wall) goes to `wall` and the
+ *                       vector takes 0.0 there.  mask 0: hpgmg_dense_pack's bytes, `wall` untouched.
+ *   pack_lifted_faces,  as pack_lifted / boundary_flux, a masked face's entry being  phi = ((b * (1.0 / h)) * wall) * gn ; the other faces
+ *   flux_faces:         keep ((2.0 * b) * (1.0 / (h * h))) * beta) * g.  T(c) sums in the same order.
+ *   interp_faces:       boundary_interp with the coarse iterate u_c (vector id of `coarse`) read as well.  A ghost outside along m axes, P its
+ *                       cell clamped into the domain: no outside axis masked: boundary_interp's delta.  Else
+ *                       delta = c * u_c(P) + s,  s = 0.0 + per outside axis in the order i, j, k (masked: h_c * gn(P), else: 2.0 * g(P)),
+ *                       c = 1 - 2 * (outside axes not masked) + (m odd ? 1 : -1): the ghost u_c(P) + sum of (h_c gn | 2 (g - u_c(P))),
+ *                       exact for linear u, minus the homogeneous-Dirichlet ghost (-1)^m u_c(P). */
+int     hpgmg_dense_pack_walls(level_type *level, int id, const double *src, int where, int layout, int check, int mask, double *wall);
+int     hpgmg_dense_pack_lifted_faces(level_type *level, int id, const double *f, int where, const double *g, double b, int mask, const double *wall);
+int     hpgmg_boundary_flux_faces(level_type *level, double *phi, const double *g, double b, int mask, const double *wall);
+void    hpgmg_boundary_interp_faces(level_type *fine, int id, level_type *coarse, const double *g_c, int mask);
 /* Launch-bound stretches of a cycle (everything done on levels of <= 64^3 cells between two
  * bottom solves) are bracketed by the cycle driver as a SEGMENT with a key that repeats every
  * solve, so the HIP plugin can capture it once into a hipGraph and replay it.  Plugins without
