@@ -51,7 +51,7 @@ DENSE_NOT_FINITE, DENSE_OUT_OF_RANGE = 1, 2
 WHERE_HOST, WHERE_PLUGIN = 0, 1
 (USER_OK, USER_BAD_ARGUMENT, USER_CONFLICT, USER_MULTI_RANK, USER_NOT_FINITE, USER_OUT_OF_RANGE,
  USER_NOT_READY, USER_UNSUPPORTED) = 0, -1, -2, -3, -4, -5, -6, -7
-USER_FMG, USER_MG = 0, 1
+USER_FMG, USER_MG, USER_PCG = 0, 1, 2
 FACE_DIRICHLET, FACE_NEUMANN = 0, 1
 
 
@@ -146,6 +146,7 @@ def _declare_driver_api(lib):
         "hpgmg_user_set_coefficients": (c_int, [vp, vp, vp, vp, vp, c_int]),
         "hpgmg_user_set_rhs": (c_int, [vp, vp, c_int, P(c_dbl)]),
         "hpgmg_user_solve": (c_int, [vp, c_int, c_dbl, vp, c_int, P(UserInfo)]),
+        "hpgmg_user_set_max_iterations": (c_int, [vp, c_int]),
         "hpgmg_user_get_solution": (c_int, [vp, vp, c_int]),
         "hpgmg_user_apply": (c_int, [vp, vp, vp, c_int]),
         "hpgmg_user_set_rhs_dirichlet": (c_int, [vp, vp, vp, c_int, P(c_dbl)]),
@@ -161,6 +162,10 @@ def _declare_driver_api(lib):
         "hpgmg_dense_pack_lifted_faces": (c_int, [vp, c_int, vp, c_int, vp, c_dbl, c_int, vp]),
         "hpgmg_boundary_flux_faces": (c_int, [vp, vp, vp, c_dbl, c_int, vp]),
         "hpgmg_boundary_interp_faces": (None, [vp, c_int, vp, vp, c_int]),
+        # the fine-level passes of method="pcg" 
+        "hpgmg_pcg_apply_dot": (c_int, [vp, c_int, c_int, c_dbl, c_dbl, P(c_dbl)]),
+        "hpgmg_pcg_update": (c_int, [vp, c_int, c_int, c_int, c_int, c_dbl, P(c_dbl)]),
+        "hpgmg_pcg_dot": (c_int, [vp, c_int, c_int, P(c_dbl)]),
         "hpgmg_vector_alloc": (vp, [ctypes.c_size_t]),
         "hpgmg_vector_free": (None, [vp]),
         "hpgmg_vector_copy": (None, [vp, vp, ctypes.c_size_t]),

@@ -495,6 +495,82 @@ __attribute__((weak)) void hpgmg_boundary_interp(level_type *Lf, int id, level_t
   free(v); free(gc);
 }
 
+/* ------------------------------------------------------------------ the CG passes: portable forms (include/hpgmg_operators.h)
+ * The operators, then the sums on the host from downloaded boxes, in the one order the header defines.  The hooks are weak like the dense pair above:
+ * the HIP plugin (host/plugin_pcg.c) replaces them with its kernels and comes back to the _host forms on a level those do not take. */
+typedef struct { double *V; size_t W, S, len; } pcg_leaves;
+static pcg_leaves pcg_leaves_of(const level_type *L) {
+  pcg_leaves P;
+  const size_t dim = (size_t)L->box_dim, used = HPGMG_PCG_COLUMNS * ((dim * dim + HPGMG_PCG_COLUMNS - 1) / HPGMG_PCG_COLUMNS);
+  P.W = used; P.S = (dim + HPGMG_PCG_SEGMENT - 1) / HPGMG_PCG_SEGMENT;
+  for (P.len = 1; P.len < P.W * P.S * (size_t)L->num_my_boxes; P.len *= 2) {}
+  P.V = (double *)calloc(P.len, sizeof(double));
+  return P;
+}
+static double pcg_fold(pcg_leaves *P) {
+  size_t stride, m;
+  for (stride = 1; stride < P->len; stride *= 2)
+    for (m = 0; m + stride < P->len; m += 2 * stride) P->V[m] = P->V[m] + P->V[m + stride];
+  const double sum = P->V[0];
+  free(P->V);
+  return sum;
+}
+int hpgmg_pcg_dot_host(level_type *L, int a_id, int b_id, double *dot) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  double *va = (double *)malloc((size_t)L->box_volume * sizeof(double)), *vb = (double *)malloc((size_t)L->box_volume * sizeof(double));
+  pcg_leaves P = pcg_leaves_of(L);
+  int bx, i, j, k;
+  size_t s;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    hpgmg_vector_download(va, L->my_boxes[bx].vectors[a_id], (size_t)L->box_volume);
+    hpgmg_vector_download(vb, L->my_boxes[bx].vectors[b_id], (size_t)L->box_volume);
+    for (s = 0; s < P.S; s++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int k1 = (int)(s + 1) * HPGMG_PCG_SEGMENT < dim ? (int)(s + 1) * HPGMG_PCG_SEGMENT : dim;
+      double chain = 0.0;
+      for (k = (int)s * HPGMG_PCG_SEGMENT; k < k1; k++) {
+        const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+        const double q = va[ijk] * vb[ijk];
+        chain = chain + q;
+      }
+      P.V[(size_t)(i + dim * j) + P.W * (s + P.S * (size_t)bx)] = chain;
+    }
+  }
+  free(va); free(vb);
+  *dot = pcg_fold(&P);
+  return 0;
+}
+int hpgmg_pcg_apply_dot_host(level_type *L, int Ap_id, int p_id, double a, double b, double *dot) {
+  apply_op(L, Ap_id, p_id, a, b);
+  return hpgmg_pcg_dot_host(L, p_id, Ap_id, dot);
+}
+int hpgmg_pcg_update_host(level_type *L, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t vol = (size_t)L->box_volume;
+  double *v = (double *)malloc(4 * vol * sizeof(double)), *x = v, *r = v + vol, *p = v + 2 * vol, *Ap = v + 3 * vol;
+  double best = 0.0;
+  int bx, i, j, k;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    const box_type *B = &L->my_boxes[bx];
+    hpgmg_vector_download(x, B->vectors[x_id], vol); hpgmg_vector_download(r, B->vectors[r_id], vol);
+    hpgmg_vector_download(p, B->vectors[p_id], vol); hpgmg_vector_download(Ap, B->vectors[Ap_id], vol);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+      const double dx = alpha * p[ijk], dr = alpha * Ap[ijk];
+      x[ijk] = x[ijk] + dx;
+      r[ijk] = r[ijk] - dr;
+      const double f = fabs(r[ijk]);
+      if (f > best) best = f;
+    }
+    hpgmg_vector_upload(B->vectors[x_id], x, vol); hpgmg_vector_upload(B->vectors[r_id], r, vol);
+  }
+  free(v);
+  *rmax = best;
+  return 0;
+}
+__attribute__((weak)) int hpgmg_pcg_apply_dot(level_type *L, int Ap_id, int p_id, double a, double b, double *dot) { return hpgmg_pcg_apply_dot_host(L, Ap_id, p_id, a, b, dot); }
+__attribute__((weak)) int hpgmg_pcg_update(level_type *L, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax) { return hpgmg_pcg_update_host(L, x_id, r_id, p_id, Ap_id, alpha, rmax); }
+__attribute__((weak)) int hpgmg_pcg_dot(level_type *L, int a_id, int b_id, double *dot) { return hpgmg_pcg_dot_host(L, a_id, b_id, dot); }
+
 /* ------------------------------------------------------------------ user problems on dense arrays (include/hpgmg_fv.h) */
 struct hpgmg_user_solver {
   hpgmg_solver s;              /* the finest level, the hierarchy, a, b, h */
@@ -505,6 +581,7 @@ struct hpgmg_user_solver {
   int bnd;                     /* 1: f was set with boundary values (set_rhs_dirichlet): an F-cycle runs with the hook below */
   double **bnd_g, **bnd_phi;   /* per level: the boundary values g_l and their lift flux phi_l (plugin memory; allocated on first use) */
   double *app_g, *app_phi;     /* apply_dirichlet's g and phi on the finest level */
+  int max_iter;                /* HPGMG_USER_PCG: the iteration limit (hpgmg_user_set_max_iterations; default 100) */
   int mask;                    /* bit f: domain face f is a Neumann wall (hpgmg_user_create_faces); 0: every wall Dirichlet, or periodic */
   double *wall0, **wall;       /* mask != 0: wall0 = wall[0]; per level, the wall beta of the Neumann faces (a boundary array; the level's own beta is 0 there) */
 };
@@ -586,6 +663,7 @@ static int user_create(int n, int box_dim, int bc, int mask, int op, int smoothe
   hpgmg_user_solver *us = (hpgmg_user_solver *)calloc(1, sizeof(*us));
   hpgmg_solver *s = &us->s;
   us->n = n; us->bc = bc; us->operator_ok = us->rhs_ok = 1;
+  us->max_iter = 100;
   us->mask = mask;
   USER_QUIET(us);
   s->boxes_in_i = n / box_dim; s->box_dim = box_dim; s->my_rank = 0; s->num_ranks = 1;
@@ -631,6 +709,11 @@ void hpgmg_user_destroy(hpgmg_user_solver *us) {
 }
 
 void hpgmg_user_set_verbose(hpgmg_user_solver *us, int on) { us->verbose = on; }
+int hpgmg_user_set_max_iterations(hpgmg_user_solver *us, int n) {
+  if (!us || n < 1) return HPGMG_USER_BAD_ARGUMENT;
+  us->max_iter = n;
+  return HPGMG_USER_OK;
+}
 hpgmg_solver *hpgmg_user_solver_of(hpgmg_user_solver *us) { return &us->s; }
 
 int hpgmg_user_set_coefficients(hpgmg_user_solver *us, const double *alpha, const double *beta_i, const double *beta_j, const double *beta_k, int where) {
@@ -755,12 +838,20 @@ static void user_bnd_interpolated(const hpgmg_fmg_hook *hook, mg_type *G, int l,
 int hpgmg_user_solve(hpgmg_user_solver *us, int method, double rtol, const double *u0, int where, hpgmg_user_info *info) {
   hpgmg_solver *s = &us->s;
   level_type *L = &s->level_h;
-  if ((method != HPGMG_USER_FMG && method != HPGMG_USER_MG) || !(rtol > 0.0)) return HPGMG_USER_BAD_ARGUMENT;
+  if ((method != HPGMG_USER_FMG && method != HPGMG_USER_MG && method != HPGMG_USER_PCG) || !(rtol > 0.0)) return HPGMG_USER_BAD_ARGUMENT;
   if (!us->operator_ok || !us->rhs_ok) return HPGMG_USER_NOT_READY;
   if (!user_config_ok()) return HPGMG_USER_CONFLICT;
   USER_QUIET(us);
   const int v0 = L->vcycles_from_this_level;
   double norm_of_F, r;
+  if (method == HPGMG_USER_PCG) {                  /* CG around the V-cycle, from u0 or from 0 */
+    if (u0) {
+      const int st = user_pack_status(hpgmg_dense_pack(L, VECTOR_U, u0, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
+      if (st) { USER_LOUD(); return st; }
+    }
+    MGPCGSolve(&s->mg, 0, VECTOR_U, VECTOR_F, s->a, s->b, rtol, us->max_iter, u0 != NULL);
+    norm_of_F = hpgmg_last_solve.norm_of_F; r = hpgmg_last_solve.norm_of_residual;
+  } else
   if (u0) {                     /* u = u0 + e with A e = f - A u0; the V-cycles stop when |f - A u| has dropped below rtol |f| */
     const int st = user_pack_status(hpgmg_dense_pack(L, VECTOR_U, u0, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
     if (st) { USER_LOUD(); return st; }

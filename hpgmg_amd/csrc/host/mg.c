@@ -607,6 +607,79 @@ void MGPCG(mg_type *G, int onLevel, int x_id, int F_id, double a, double b, doub
   SAY(L->my_rank, "done (%f seconds)\n", now() - t0);
 }
 
+/* The user-problem API's CG (include/hpgmg_mg.h): MGPCG's algorithm and vectors, but the fine-level work outside the V-cycle is three
+ * fused passes (hpgmg_pcg_apply_dot / _update / _dot) whose sums have their own order, the recurrence residual decides when the TRUE residual is worth a
+ * pass, the iteration limit is the caller's and nothing aborts.  Nothing here pins the reference's digits: MGPCG above does that. */
+static double pcg_true_residual(level_type *L, int res_id, int x_id, int F_id, double a, double b) {
+  double r;
+  if (L->must_subtract_mean == 1) { const double m = mean(L, x_id); shift_vector(L, x_id, x_id, -m); }
+  if (!hpgmg_residual_norm_fused(L, res_id, x_id, F_id, a, b, &r)) {
+    residual(L, res_id, x_id, F_id, a, b);
+    r = norm(L, res_id);
+  }
+  return r;
+}
+static int pcg_broken(double v) { return v == 0.0 || !isfinite(v); }
+int MGPCGSolve(mg_type *G, int onLevel, int x_id, int F_id, double a, double b, double rtol, int max_iter, int x_is_guess) {
+  level_type *L = G->levels[onLevel];
+  const int r_id = VECTOR_R, p_id = hpgmg_vectors_reserved(), Ap_id = p_id + 1, z_id = p_id + 2;
+  int l, j = 0, converged = 0, vcycles = 0;
+  if (!L->active) return 0;
+  for (l = 0; l < G->num_levels; l++) create_vectors(G->levels[l], hpgmg_vectors_reserved() + 3);     /* allocates the first time only */
+  SAY(L->my_rank, "MGPCGSolve...  ");
+  const double t0 = now();
+  seg_reset(G, onLevel + 192, x_id, F_id, a, b);
+  G->MGSolves_performed++;
+  const double norm_of_F = norm(L, F_id), target = rtol * norm_of_F;
+  if (!x_is_guess) zero_vector(L, x_id);
+  double r_true = pcg_true_residual(L, r_id, x_id, F_id, a, b);      /* r = F - A x */
+  if (L->must_subtract_mean == 1) { const double m = mean(L, r_id); shift_vector(L, r_id, r_id, -m); }
+  if (r_true == 0.0 || r_true < target) converged = 1;               /* entered with the solution */
+  double r_dot_z = 0.0;
+  if (!converged) {
+    L->vcycles_from_this_level++; vcycles++;
+    zero_vector(L, z_id);
+    MGVCycle(G, z_id, r_id, a, b, onLevel);                           /* z = M^-1 r */
+    seg_close();
+    scale_vector(L, p_id, 1.0, z_id);
+    hpgmg_pcg_dot(L, r_id, z_id, &r_dot_z);
+  }
+  while (!converged && !pcg_broken(r_dot_z)) {
+    double Ap_dot_p, rmax, r_dot_z_new;
+    j++;
+    hpgmg_pcg_apply_dot(L, Ap_id, p_id, a, b, &Ap_dot_p);
+    if (pcg_broken(Ap_dot_p)) break;                                  /* pivot breakdown */
+    const double alpha = r_dot_z / Ap_dot_p;
+    if (pcg_broken(alpha)) break;
+    hpgmg_pcg_update(L, x_id, r_id, p_id, Ap_id, alpha, &rmax);
+    if (L->must_subtract_mean == 1) { const double m = mean(L, r_id); shift_vector(L, r_id, r_id, -m); rmax = norm(L, r_id); }
+    if (!isfinite(rmax)) break;                                       /* an overflow; a NaN in r never reaches rmax (a maximum skips it): the r.z test below ends that solve */
+    if (j > 1) SAY(L->my_rank, "\n               ");
+    SAY(L->my_rank, "iter=%3d  |r|=%1.15e  rel=%1.15e  ", j, rmax, rmax / norm_of_F);
+    if (rmax < target) {                                              /* the recurrence says so: the true residual decides, and replaces r if it disagrees */
+      r_true = pcg_true_residual(L, r_id, x_id, F_id, a, b);
+      if (r_true < target) { converged = 1; break; }
+      if (L->must_subtract_mean == 1) { const double m = mean(L, r_id); shift_vector(L, r_id, r_id, -m); }
+    }
+    if (j >= max_iter) break;
+    L->vcycles_from_this_level++; vcycles++;
+    zero_vector(L, z_id);
+    MGVCycle(G, z_id, r_id, a, b, onLevel);
+    seg_close();
+    hpgmg_pcg_dot(L, r_id, z_id, &r_dot_z_new);
+    if (pcg_broken(r_dot_z_new)) break;                               /* Lanczos breakdown */
+    const double beta = r_dot_z_new / r_dot_z;
+    if (pcg_broken(beta)) break;
+    add_vectors(L, p_id, 1.0, z_id, beta, p_id);
+    r_dot_z = r_dot_z_new;
+  }
+  if (!converged) r_true = pcg_true_residual(L, VECTOR_TEMP, x_id, F_id, a, b);
+  hpgmg_last_solve.norm_of_F = norm_of_F; hpgmg_last_solve.norm_of_residual = r_true; hpgmg_last_solve.vcycles = vcycles;
+  G->timers.MGSolve += now() - t0;
+  SAY(L->my_rank, "%s (%f seconds)\n", converged ? "done" : "not converged", now() - t0);
+  return converged;
+}
+
 /* V-cycles FMGSolve may add after its F-cycle until the residual has dropped by rtol: 0, or 20 = the reference built with -DUNLIMIT_FMG_ITERATIONS (mg.c:1239-1247) */
 static int hpgmg_fmg_vcycles = 0;
 void hpgmg_set_fmg_vcycles(int n) { hpgmg_fmg_vcycles = n > 0 ? n : 0; }

@@ -345,6 +345,14 @@ int hpgmg_hip_sum(const hpgmg_hip_level *L, int id, double *out);               
  * id_A[mm] * id_B[nn] for nn >= mm, mirrored to C_host[nn * cols + mm] where that entry exists.  Per box one chain in k, j, i order, products first;
  * box partials added in box order (NOT the tile order above).  One launch; synchronises.  rows, cols <= 32; the ids must name vectors of the level. */
 int hpgmg_hip_gram(const hpgmg_hip_level *L, const int *id_A, int rows, const int *id_B, int cols, double *C_host);
+/* The fine-level passes of the V-cycle-preconditioned CG (include/hpgmg_operators.h hpgmg_pcg_*; kernels/pcg.hip), each one pass plus a tiny launch that
+ * finishes the reduction; the sums in the header's order (a function of dim and num_boxes only).  _supported: a 7-point variable-coefficient variant on
+ * a level with the face-neighbour table, every neighbour local (apply_dot reads neighbouring boxes where they live, a Dirichlet face as -x). */
+int hpgmg_hip_pcg_supported(const hpgmg_hip_level *L, int variant);
+int hpgmg_hip_pcg_apply_dot(const hpgmg_hip_level *L, int variant, int Ap_id, int p_id, double a, double b, double h2inv, double *dot);
+int hpgmg_hip_pcg_update(const hpgmg_hip_level *L, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax);
+int hpgmg_hip_pcg_dot(const hpgmg_hip_level *L, int a_id, int b_id, double *dot);
+
 /* dense arrays <-> vector id (include/hpgmg_operators.h hpgmg_dense_pack / unpack; kernels/dense_io.hip).  src / dst are DEVICE arrays.
  * pack: a (nk, nj, ni) array, each extent the level's global one or one more (a Dirichlet face array); writes every double of every box
  * and returns the validation bits in *status (HPGMG_DENSE_*; check = HPGMG_DENSE_CHECK_*).  Both synchronise. */

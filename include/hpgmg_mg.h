@@ -49,6 +49,11 @@ typedef struct hpgmg_fmg_hook {
 } hpgmg_fmg_hook;
 void hpgmg_fmg_set_hook(const hpgmg_fmg_hook *hook);
 void MGPCG(mg_type *all_grids, int onLevel, int x_id, int F_id, double a, double b, double rtol);   /* mg.c:1500-1605: CG preconditioned with one V-cycle per iteration; grows every level by three vectors */
+/* CG on A u = F preconditioned with one V-cycle per iteration, for the user-problem API: Saad's algorithm 9.1 as MGPCG, but through the
+ * fused passes hpgmg_pcg_* (include/hpgmg_operators.h) with their own summation order, up to max_iter iterations, and never aborting.  x_is_guess: start from
+ * what x_id holds (else from 0).  Returns 1 when |F - A x|_inf < rtol |F|_inf, 0 after max_iter iterations or a breakdown (a zero or non-finite p.Ap, r.z,
+ * alpha or beta): x is then the last iterate.  hpgmg_last_solve holds |F|, the TRUE residual norm of x and the number of V-cycles run (= iterations). */
+int  MGPCGSolve(mg_type *all_grids, int onLevel, int x_id, int F_id, double a, double b, double rtol, int max_iter, int x_is_guess);
 void MGPrintTiming(mg_type *all_grids, int fromLevel);
 void MGResetTimers(mg_type *all_grids);
 void richardson_error(mg_type *all_grids, int levelh, int u_id);

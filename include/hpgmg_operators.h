@@ -172,6 +172,25 @@ int     hpgmg_dense_pack_walls(level_type *level, int id, const double *src, int
 int     hpgmg_dense_pack_lifted_faces(level_type *level, int id, const double *f, int where, const double *g, double b, int mask, const double *wall);
 int     hpgmg_boundary_flux_faces(level_type *level, double *phi, const double *g, double b, int mask, const double *wall);
 void    hpgmg_boundary_interp_faces(level_type *fine, int id, level_type *coarse, const double *g_c, int mask);
+/* The fine-level passes of the V-cycle-preconditioned CG of the user-problem API (MGPCGSolve, include/hpgmg_mg.h), 7-point operator:
+ *   pcg_apply_dot: Ap = A p exactly as apply_op(level, Ap_id, p_id, a, b) leaves it (its ghost exchange and boundary conditions), and *dot = p . Ap
+ *   pcg_update:    per interior cell  x = x + alpha * p ;  r = r - alpha * Ap  (the product first, then the sum / difference), *rmax = max |r| (0.0 <= it)
+ *   pcg_dot:       *dot = a . b
+ * The two sums have ONE order, a function of the level's geometry only (it is not dot()'s): with dim the box side, the products a * b of box B are
+ * formed first; column c = i + dim * j of segment s (the planes 16 s <= k < min(16 s + 16, dim)) is the chain 0.0 + q(k = 16 s) + q(16 s + 1) + ...;
+ * with W = 256 * ceil(dim^2 / 256) and S = ceil(dim / 16) the chains are the leaves V[c + W * (s + S * B)] (0.0 where c >= dim^2) of an array padded
+ * with 0.0 to a power of two, folded for stride = 1, 2, 4, ...:  V[m] = V[m] + V[m + stride]  for every m that is a multiple of 2 * stride; V[0] is
+ * the sum.  No chain of dependent additions is longer than 16 + log2(cells).  Return value: 1 = a fused kernel of the plugin ran, 0 = the portable
+ * form did (host/driver.c: the operators, then the sums on the host from downloaded boxes -- the CPU oracle; a plugin falls back to it on a level
+ * its kernels do not take).  Same bits either way. */
+#define HPGMG_PCG_SEGMENT 16
+#define HPGMG_PCG_COLUMNS 256
+int     hpgmg_pcg_apply_dot(level_type *level, int Ap_id, int p_id, double a, double b, double *dot);
+int     hpgmg_pcg_update(level_type *level, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax);
+int     hpgmg_pcg_dot(level_type *level, int a_id, int b_id, double *dot);
+int     hpgmg_pcg_apply_dot_host(level_type *level, int Ap_id, int p_id, double a, double b, double *dot);      /* the portable forms themselves (always 0) */
+int     hpgmg_pcg_update_host(level_type *level, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax);
+int     hpgmg_pcg_dot_host(level_type *level, int a_id, int b_id, double *dot);
 /* Launch-bound stretches of a cycle (everything done on levels of <= 64^3 cells between two
  * bottom solves) are bracketed by the cycle driver as a SEGMENT with a key that repeats every
  * solve, so the HIP plugin can capture it once into a hipGraph and replay it.  Plugins without
