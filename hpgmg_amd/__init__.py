@@ -51,7 +51,7 @@ DENSE_NOT_FINITE, DENSE_OUT_OF_RANGE = 1, 2
 WHERE_HOST, WHERE_PLUGIN = 0, 1
 (USER_OK, USER_BAD_ARGUMENT, USER_CONFLICT, USER_MULTI_RANK, USER_NOT_FINITE, USER_OUT_OF_RANGE,
  USER_NOT_READY, USER_UNSUPPORTED) = 0, -1, -2, -3, -4, -5, -6, -7
-USER_FMG, USER_MG, USER_PCG = 0, 1, 2
+USER_FMG, USER_MG, USER_PCG, USER_FPCG = 0, 1, 2, 3
 FACE_DIRICHLET, FACE_NEUMANN = 0, 1
 
 
@@ -166,6 +166,7 @@ def _declare_driver_api(lib):
         "hpgmg_pcg_apply_dot": (c_int, [vp, c_int, c_int, c_dbl, c_dbl, P(c_dbl)]),
         "hpgmg_pcg_update": (c_int, [vp, c_int, c_int, c_int, c_int, c_dbl, P(c_dbl)]),
         "hpgmg_pcg_dot": (c_int, [vp, c_int, c_int, P(c_dbl)]),
+        "hpgmg_pcg_dot2": (c_int, [vp, c_int, c_int, c_int, P(c_dbl), P(c_dbl)]),      # method="fpcg" (§11.4): a . b and c . b in one pass
         "hpgmg_vector_alloc": (vp, [ctypes.c_size_t]),
         "hpgmg_vector_free": (None, [vp]),
         "hpgmg_vector_copy": (None, [vp, vp, ctypes.c_size_t]),
@@ -206,6 +207,7 @@ def _declare_kernel_api(lib):
         "hpgmg_hip_dot": (c_int, [L, c_int, c_int, P(c_dbl)]),
         "hpgmg_hip_sum": (c_int, [L, c_int, P(c_dbl)]),
         "hpgmg_hip_gram": (c_int, [L, P(c_int), c_int, P(c_int), c_int, P(c_dbl)]),
+        "hpgmg_hip_pcg_dot2": (c_int, [L, c_int, c_int, c_int, P(c_dbl), P(c_dbl)]),
         "hpgmg_hip_pair_launch_counts": (None, [P(ctypes.c_longlong)]),
     }
     for name, (res, args) in sig.items():

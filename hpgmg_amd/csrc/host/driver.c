@@ -515,28 +515,51 @@ static double pcg_fold(pcg_leaves *P) {
   free(P->V);
   return sum;
 }
-int hpgmg_pcg_dot_host(level_type *L, int a_id, int b_id, double *dot) {
+/* the leaves of box bx: per column and segment the chain over its planes of the products va * vb */
+static void pcg_box_leaves(const level_type *L, pcg_leaves *P, int bx, const double *va, const double *vb) {
   const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  int i, j, k;
+  size_t s;
+  for (s = 0; s < P->S; s++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+    const int k1 = (int)(s + 1) * HPGMG_PCG_SEGMENT < dim ? (int)(s + 1) * HPGMG_PCG_SEGMENT : dim;
+    double chain = 0.0;
+    for (k = (int)s * HPGMG_PCG_SEGMENT; k < k1; k++) {
+      const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+      const double q = va[ijk] * vb[ijk];
+      chain = chain + q;
+    }
+    P->V[(size_t)(i + dim * j) + P->W * (s + P->S * (size_t)bx)] = chain;
+  }
+}
+int hpgmg_pcg_dot_host(level_type *L, int a_id, int b_id, double *dot) {
   double *va = (double *)malloc((size_t)L->box_volume * sizeof(double)), *vb = (double *)malloc((size_t)L->box_volume * sizeof(double));
   pcg_leaves P = pcg_leaves_of(L);
-  int bx, i, j, k;
-  size_t s;
+  int bx;
   for (bx = 0; bx < L->num_my_boxes; bx++) {
     hpgmg_vector_download(va, L->my_boxes[bx].vectors[a_id], (size_t)L->box_volume);
     hpgmg_vector_download(vb, L->my_boxes[bx].vectors[b_id], (size_t)L->box_volume);
-    for (s = 0; s < P.S; s++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
-      const int k1 = (int)(s + 1) * HPGMG_PCG_SEGMENT < dim ? (int)(s + 1) * HPGMG_PCG_SEGMENT : dim;
-      double chain = 0.0;
-      for (k = (int)s * HPGMG_PCG_SEGMENT; k < k1; k++) {
-        const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
-        const double q = va[ijk] * vb[ijk];
-        chain = chain + q;
-      }
-      P.V[(size_t)(i + dim * j) + P.W * (s + P.S * (size_t)bx)] = chain;
-    }
+    pcg_box_leaves(L, &P, bx, va, vb);
   }
   free(va); free(vb);
   *dot = pcg_fold(&P);
+  return 0;
+}
+/* a . b and c . b from one download of b: two trees of the one order, so each has the bits of hpgmg_pcg_dot_host on its pair */
+int hpgmg_pcg_dot2_host(level_type *L, int a_id, int c_id, int b_id, double *ab, double *cb) {
+  const size_t vol = (size_t)L->box_volume;
+  double *v = (double *)malloc(3 * vol * sizeof(double)), *va = v, *vc = v + vol, *vb = v + 2 * vol;
+  pcg_leaves P = pcg_leaves_of(L), Q = pcg_leaves_of(L);
+  int bx;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    hpgmg_vector_download(va, L->my_boxes[bx].vectors[a_id], vol);
+    hpgmg_vector_download(vc, L->my_boxes[bx].vectors[c_id], vol);
+    hpgmg_vector_download(vb, L->my_boxes[bx].vectors[b_id], vol);
+    pcg_box_leaves(L, &P, bx, va, vb);
+    pcg_box_leaves(L, &Q, bx, vc, vb);
+  }
+  free(v);
+  *ab = pcg_fold(&P);
+  *cb = pcg_fold(&Q);
   return 0;
 }
 int hpgmg_pcg_apply_dot_host(level_type *L, int Ap_id, int p_id, double a, double b, double *dot) {
@@ -570,6 +593,7 @@ int hpgmg_pcg_update_host(level_type *L, int x_id, int r_id, int p_id, int Ap_id
 __attribute__((weak)) int hpgmg_pcg_apply_dot(level_type *L, int Ap_id, int p_id, double a, double b, double *dot) { return hpgmg_pcg_apply_dot_host(L, Ap_id, p_id, a, b, dot); }
 __attribute__((weak)) int hpgmg_pcg_update(level_type *L, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax) { return hpgmg_pcg_update_host(L, x_id, r_id, p_id, Ap_id, alpha, rmax); }
 __attribute__((weak)) int hpgmg_pcg_dot(level_type *L, int a_id, int b_id, double *dot) { return hpgmg_pcg_dot_host(L, a_id, b_id, dot); }
+__attribute__((weak)) int hpgmg_pcg_dot2(level_type *L, int a_id, int c_id, int b_id, double *ab, double *cb) { return hpgmg_pcg_dot2_host(L, a_id, c_id, b_id, ab, cb); }
 
 /* ------------------------------------------------------------------ user problems on dense arrays (include/hpgmg_fv.h) */
 struct hpgmg_user_solver {
@@ -581,7 +605,7 @@ struct hpgmg_user_solver {
   int bnd;                     /* 1: f was set with boundary values (set_rhs_dirichlet): an F-cycle runs with the hook below */
   double **bnd_g, **bnd_phi;   /* per level: the boundary values g_l and their lift flux phi_l (plugin memory; allocated on first use) */
   double *app_g, *app_phi;     /* apply_dirichlet's g and phi on the finest level */
-  int max_iter;                /* HPGMG_USER_PCG: the iteration limit (hpgmg_user_set_max_iterations; default 100) */
+  int max_iter;                /* HPGMG_USER_PCG / _FPCG: the iteration limit (hpgmg_user_set_max_iterations; default 100) */
   int mask;                    /* bit f: domain face f is a Neumann wall (hpgmg_user_create_faces); 0: every wall Dirichlet, or periodic */
   double *wall0, **wall;       /* mask != 0: wall0 = wall[0]; per level, the wall beta of the Neumann faces (a boundary array; the level's own beta is 0 there) */
 };
@@ -838,18 +862,18 @@ static void user_bnd_interpolated(const hpgmg_fmg_hook *hook, mg_type *G, int l,
 int hpgmg_user_solve(hpgmg_user_solver *us, int method, double rtol, const double *u0, int where, hpgmg_user_info *info) {
   hpgmg_solver *s = &us->s;
   level_type *L = &s->level_h;
-  if ((method != HPGMG_USER_FMG && method != HPGMG_USER_MG && method != HPGMG_USER_PCG) || !(rtol > 0.0)) return HPGMG_USER_BAD_ARGUMENT;
+  if ((method != HPGMG_USER_FMG && method != HPGMG_USER_MG && method != HPGMG_USER_PCG && method != HPGMG_USER_FPCG) || !(rtol > 0.0)) return HPGMG_USER_BAD_ARGUMENT;
   if (!us->operator_ok || !us->rhs_ok) return HPGMG_USER_NOT_READY;
   if (!user_config_ok()) return HPGMG_USER_CONFLICT;
   USER_QUIET(us);
   const int v0 = L->vcycles_from_this_level;
   double norm_of_F, r;
-  if (method == HPGMG_USER_PCG) {                  /* CG around the V-cycle, from u0 or from 0 */
+  if (method == HPGMG_USER_PCG || method == HPGMG_USER_FPCG) {    /* CG around the V-cycle, from u0 or from 0 */
     if (u0) {
       const int st = user_pack_status(hpgmg_dense_pack(L, VECTOR_U, u0, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
       if (st) { USER_LOUD(); return st; }
     }
-    MGPCGSolve(&s->mg, 0, VECTOR_U, VECTOR_F, s->a, s->b, rtol, us->max_iter, u0 != NULL);
+    (method == HPGMG_USER_FPCG ? MGFPCGSolve : MGPCGSolve)(&s->mg, 0, VECTOR_U, VECTOR_F, s->a, s->b, rtol, us->max_iter, u0 != NULL);
     norm_of_F = hpgmg_last_solve.norm_of_F; r = hpgmg_last_solve.norm_of_residual;
   } else
   if (u0) {                     /* u = u0 + e with A e = f - A u0; the V-cycles stop when |f - A u| has dropped below rtol |f| */

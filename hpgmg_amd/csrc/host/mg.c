@@ -620,15 +620,16 @@ static double pcg_true_residual(level_type *L, int res_id, int x_id, int F_id, d
   return r;
 }
 static int pcg_broken(double v) { return v == 0.0 || !isfinite(v); }
-int MGPCGSolve(mg_type *G, int onLevel, int x_id, int F_id, double a, double b, double rtol, int max_iter, int x_is_guess) {
+/* flexible = 1 (MGFPCGSolve): beta = -(Ap.z / p.Ap) from the one pass hpgmg_pcg_dot2, for a V-cycle that is not one fixed operator */
+static int pcg_solve(mg_type *G, int onLevel, int x_id, int F_id, double a, double b, double rtol, int max_iter, int x_is_guess, int flexible) {
   level_type *L = G->levels[onLevel];
   const int r_id = VECTOR_R, p_id = hpgmg_vectors_reserved(), Ap_id = p_id + 1, z_id = p_id + 2;
   int l, j = 0, converged = 0, vcycles = 0;
   if (!L->active) return 0;
   for (l = 0; l < G->num_levels; l++) create_vectors(G->levels[l], hpgmg_vectors_reserved() + 3);     /* allocates the first time only */
-  SAY(L->my_rank, "MGPCGSolve...  ");
+  SAY(L->my_rank, flexible ? "MGFPCGSolve...  " : "MGPCGSolve...  ");
   const double t0 = now();
-  seg_reset(G, onLevel + 192, x_id, F_id, a, b);
+  seg_reset(G, onLevel + (flexible ? 256 : 192), x_id, F_id, a, b);      /* a key of its own: neither replays the other's graphs */
   G->MGSolves_performed++;
   const double norm_of_F = norm(L, F_id), target = rtol * norm_of_F;
   if (!x_is_guess) zero_vector(L, x_id);
@@ -666,10 +667,19 @@ int MGPCGSolve(mg_type *G, int onLevel, int x_id, int F_id, double a, double b, 
     zero_vector(L, z_id);
     MGVCycle(G, z_id, r_id, a, b, onLevel);
     seg_close();
-    hpgmg_pcg_dot(L, r_id, z_id, &r_dot_z_new);
-    if (pcg_broken(r_dot_z_new)) break;                               /* Lanczos breakdown */
-    const double beta = r_dot_z_new / r_dot_z;
-    if (pcg_broken(beta)) break;
+    double beta;
+    if (flexible) {
+      double Ap_dot_z;
+      hpgmg_pcg_dot2(L, r_id, Ap_id, z_id, &r_dot_z_new, &Ap_dot_z);
+      if (pcg_broken(r_dot_z_new)) break;
+      beta = -(Ap_dot_z / Ap_dot_p);                                  /* p_new = z + beta p is A-orthogonal to p whatever produced z; 0.0 is legitimate (p = z) */
+      if (!isfinite(beta)) break;
+    } else {
+      hpgmg_pcg_dot(L, r_id, z_id, &r_dot_z_new);
+      if (pcg_broken(r_dot_z_new)) break;                             /* Lanczos breakdown */
+      beta = r_dot_z_new / r_dot_z;
+      if (pcg_broken(beta)) break;
+    }
     add_vectors(L, p_id, 1.0, z_id, beta, p_id);
     r_dot_z = r_dot_z_new;
   }
@@ -678,6 +688,12 @@ int MGPCGSolve(mg_type *G, int onLevel, int x_id, int F_id, double a, double b, 
   G->timers.MGSolve += now() - t0;
   SAY(L->my_rank, "%s (%f seconds)\n", converged ? "done" : "not converged", now() - t0);
   return converged;
+}
+int MGPCGSolve(mg_type *G, int onLevel, int x_id, int F_id, double a, double b, double rtol, int max_iter, int x_is_guess) {
+  return pcg_solve(G, onLevel, x_id, F_id, a, b, rtol, max_iter, x_is_guess, 0);
+}
+int MGFPCGSolve(mg_type *G, int onLevel, int x_id, int F_id, double a, double b, double rtol, int max_iter, int x_is_guess) {
+  return pcg_solve(G, onLevel, x_id, F_id, a, b, rtol, max_iter, x_is_guess, 1);
 }
 
 /* V-cycles FMGSolve may add after its F-cycle until the residual has dropped by rtol: 0, or 20 = the reference built with -DUNLIMIT_FMG_ITERATIONS (mg.c:1239-1247) */

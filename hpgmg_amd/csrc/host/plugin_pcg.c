@@ -1,5 +1,5 @@
 /*
- * plugin_pcg.c -- hpgmg_pcg_apply_dot / _update / _dot of the operator plugin (include/hpgmg_operators.h): one pass of
+ * plugin_pcg.c -- hpgmg_pcg_apply_dot / _update / _dot / _dot2 of the operator plugin (include/hpgmg_operators.h): one pass of
  * kernels/pcg.hip each, on the levels those kernels take -- the 7-point variable-coefficient operator in ghost-free mode with every box local, which
  * is every level of a user problem.  Anywhere else the portable forms of host/driver.c run (the operators, then the sums on the host): the same bits,
  * and the return value says which of the two it was.
@@ -10,6 +10,7 @@
 extern int hpgmg_pcg_apply_dot_host(level_type *, int, int, double, double, double *) __attribute__((weak));
 extern int hpgmg_pcg_update_host(level_type *, int, int, int, int, double, double *) __attribute__((weak));
 extern int hpgmg_pcg_dot_host(level_type *, int, int, double *) __attribute__((weak));
+extern int hpgmg_pcg_dot2_host(level_type *, int, int, int, double *, double *) __attribute__((weak));
 #define PORTABLE(FN, ...) do { if (!FN) hp_no_kernel(#FN " (this level is not one the CG kernels take, and the host layer's portable form is not linked)"); return FN(__VA_ARGS__); } while (0)
 
 static backend_t *pcg_backend(level_type *L) {
@@ -51,5 +52,15 @@ int hpgmg_pcg_dot(level_type *L, int a_id, int b_id, double *dot) {
   if (!B || !pcg_ids_ok(L, a_id, b_id, 0, 0)) PORTABLE(hpgmg_pcg_dot_host, L, a_id, b_id, dot);
   BLAS1(hpgmg_hip_pcg_dot(&B->dev, a_id, b_id, &v));
   *dot = hp_allreduce_scalar(L, v, HPGMG_REDUCE_SUM);
+  return 1;
+}
+
+int hpgmg_pcg_dot2(level_type *L, int a_id, int c_id, int b_id, double *ab, double *cb) {
+  backend_t *B = pcg_backend(L);
+  double v = 0.0, w = 0.0;
+  if (!B || !pcg_ids_ok(L, a_id, c_id, b_id, 0)) PORTABLE(hpgmg_pcg_dot2_host, L, a_id, c_id, b_id, ab, cb);
+  BLAS1(hpgmg_hip_pcg_dot2(&B->dev, a_id, c_id, b_id, &v, &w));
+  *ab = hp_allreduce_scalar(L, v, HPGMG_REDUCE_SUM);
+  *cb = hp_allreduce_scalar(L, w, HPGMG_REDUCE_SUM);
   return 1;
 }

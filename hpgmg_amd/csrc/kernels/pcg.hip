@@ -2,7 +2,8 @@
 //   pcg_apply_dot  Ap = A p (7-point, variable coefficients) and p . Ap in one pass: per cell p, three betas (alpha with Helmholtz) in, Ap out
 //   pcg_update     x = x + alpha p ; r = r - alpha Ap ; max |r|: four reads, two writes
 //   pcg_dot        a . b
-// One mapping for all three: a workgroup of 256 lanes owns 256 consecutive COLUMNS c = i + dim * j of one box (consecutive lanes on consecutive
+//   pcg_dot2       a . b and c . b from one read of the three vectors (the flexible CG's r . z and Ap . z): 24 B per cell for 32
+// One mapping for all four: a workgroup of 256 lanes owns 256 consecutive COLUMNS c = i + dim * j of one box (consecutive lanes on consecutive
 // doubles of a row) over one SEGMENT of 16 planes, and marches it in +k.  That is the summation order of the header: a lane's chain over its <= 16
 // planes is a leaf; lanes fold with shuffles for stride 1 .. 32, the four waves through LDS for stride 64, 128 -- the lower levels of the ONE
 // stride-doubling tree over the leaves V[c + W (s + S box)] -- and pcg_fold_kernel folds the workgroups' values (stride 256 upwards) in a second tiny
@@ -36,6 +37,15 @@ __device__ __forceinline__ double pcg_block_sum(double v, double *smem) {
   __syncthreads();
   const double lo = smem[0] + smem[1], hi = smem[2] + smem[3];
   return lo + hi;
+}
+// two such trees at once: one barrier for both (smem: 8 doubles)
+__device__ __forceinline__ void pcg_block_sum2(double &v, double &w, double *smem) {
+#pragma unroll
+  for (int stride = 1; stride < 64; stride *= 2) { v = v + __shfl_down(v, stride, 64); w = w + __shfl_down(w, stride, 64); }
+  if (threadIdx.x % 64 == 0) { smem[threadIdx.x / 64] = v; smem[4 + threadIdx.x / 64] = w; }
+  __syncthreads();
+  const double vlo = smem[0] + smem[1], vhi = smem[2] + smem[3], wlo = smem[4] + smem[5], whi = smem[6] + smem[7];
+  v = vlo + vhi; w = wlo + whi;
 }
 __device__ __forceinline__ double pcg_block_max(double v, double *smem) {
 #pragma unroll
@@ -148,6 +158,28 @@ __global__ __launch_bounds__(kPcgLanes) void pcg_dot_kernel(const hpgmg_hip_leve
   if (threadIdx.x == 0) partials[it.item] = sum;
 }
 
+// the workgroups' values of a . b go to partials[item], those of c . b to partials[items + item]: two arrays for the one fold launch below
+__global__ __launch_bounds__(kPcgLanes) void pcg_dot2_kernel(const hpgmg_hip_level L, int a_id, int c_id, int b_id, int nseg, int ncb, int per_xcd, int items,
+                                                              double *__restrict__ partials) {
+  __shared__ double smem[8];
+  PcgItem it;
+  if (!pcg_item(L, nseg, ncb, per_xcd, items, it)) return;
+  double chain_a = 0.0, chain_c = 0.0;
+  if (it.live) {
+    const int kS = L.kStride, col = it.c % L.dim + (it.c / L.dim) * L.jStride;
+    const gcptr va = gvec_origin(L, it.box, a_id) + col, vc = gvec_origin(L, it.box, c_id) + col, vb = gvec_origin(L, it.box, b_id) + col;
+#pragma unroll 4
+    for (int k = it.k0; k < it.k1; k++) {
+      const double vbk = vb[k * kS];
+      const double qa = va[k * kS] * vbk, qc = vc[k * kS] * vbk;
+      chain_a = chain_a + qa;
+      chain_c = chain_c + qc;
+    }
+  }
+  pcg_block_sum2(chain_a, chain_c, smem);
+  if (threadIdx.x == 0) { partials[it.item] = chain_a; partials[items + it.item] = chain_c; }
+}
+
 // the tree from stride 256 upwards over the workgroups' values: a lane folds its own `chunk` (a power of two) consecutive ones in place -- an aligned
 // run of the stride-doubling tree, which no other lane touches -- then the 1024 lanes fold through LDS; entries past n are the padding's 0.0
 __global__ __launch_bounds__(kFoldLanes) void pcg_fold_kernel(double *__restrict__ partials, int n, int chunk, ResultSlot *result, unsigned long long seq) {
@@ -163,6 +195,29 @@ __global__ __launch_bounds__(kFoldLanes) void pcg_fold_kernel(double *__restrict
     __syncthreads();
   }
   if (t == 0) publish(result, smem[0], seq);
+}
+// the same tree over TWO arrays of n values, partials[0 .. n) and partials[n .. 2 n), in one launch: a second LDS array (16 KB in all) and the barriers
+// of one fold.  The first sum goes to the slot's value, the second to the word behind its sequence number (reduction_second_value()), then the one
+// sequence number publishes both.
+__global__ __launch_bounds__(kFoldLanes) void pcg_fold2_kernel(double *__restrict__ partials, int n, int chunk, ResultSlot *result, unsigned long long seq) {
+  __shared__ double smem[2][kFoldLanes];
+  const int t = (int)threadIdx.x;
+  const long long lo = (long long)t * chunk;
+  for (int q = 0; q < 2; q++) {
+    double *P = partials + (long long)q * n;
+    for (int stride = 1; stride < chunk; stride *= 2)
+      for (long long m = lo; m + stride < n && m < lo + chunk; m += 2 * stride) P[m] = P[m] + P[m + stride];
+    smem[q][t] = (lo < n) ? P[lo] : 0.0;
+  }
+  __syncthreads();
+  for (int stride = 1; stride < kFoldLanes; stride *= 2) {
+    if (t % (2 * stride) == 0) { smem[0][t] = smem[0][t] + smem[0][t + stride]; smem[1][t] = smem[1][t] + smem[1][t + stride]; }
+    __syncthreads();
+  }
+  if (t == 0) {
+    reinterpret_cast<double *>(result)[2] = smem[1][0];
+    publish(result, smem[0][0], seq);
+  }
 }
 
 struct PcgGrid { int nseg, ncb, items, per_xcd, grid; };
@@ -183,6 +238,18 @@ static int pcg_fold(int items, double *out) {
   hipLaunchKernelGGL(pcg_fold_kernel, dim3(1), dim3(kFoldLanes), 0, g_stream, reduction_scratch(items), items, chunk, slot, seq);
   HPGMG_LAUNCH_CHECK("pcg_fold_kernel");
   return reduction_fetch(out);
+}
+static int pcg_fold2(int items, double *out0, double *out1) {
+  int chunk = 1;
+  while ((long long)chunk * kFoldLanes < items) chunk *= 2;
+  unsigned long long seq = 0;
+  ResultSlot *slot = reduction_slot_next(&seq);
+  if (!slot) return record_error(hipErrorOutOfMemory, "pcg: no result slot");
+  hipLaunchKernelGGL(pcg_fold2_kernel, dim3(1), dim3(kFoldLanes), 0, g_stream, reduction_scratch(2 * items), items, chunk, slot, seq);
+  HPGMG_LAUNCH_CHECK("pcg_fold2_kernel");
+  if (int e = reduction_fetch(out0)) return e;
+  *out1 = reduction_second_value();
+  return 0;
 }
 
 }  // namespace hpgmg
@@ -239,6 +306,18 @@ int hpgmg_hip_pcg_dot(const hpgmg_hip_level *L, int a_id, int b_id, double *dot)
   hipLaunchKernelGGL(pcg_dot_kernel, dim3(g.grid), dim3(kPcgLanes), 0, g_stream, *L, a_id, b_id, g.nseg, g.ncb, g.per_xcd, g.items, partials);
   HPGMG_LAUNCH_CHECK("pcg_dot_kernel");
   return pcg_fold(g.items, dot);
+}
+
+int hpgmg_hip_pcg_dot2(const hpgmg_hip_level *L, int a_id, int c_id, int b_id, double *ab, double *cb) {
+  *ab = *cb = 0.0;
+  if (!pcg_geometry_ok(L)) return record_error(hipErrorInvalidValue, "pcg_dot2: level not supported");
+  if (int e = hpgmg_hip_graph_flush()) return e;
+  const PcgGrid g = pcg_grid(L);
+  double *partials = reduction_scratch(2 * g.items);
+  if (!partials) return record_error(hipErrorOutOfMemory, "pcg_dot2: no scratch");
+  hipLaunchKernelGGL(pcg_dot2_kernel, dim3(g.grid), dim3(kPcgLanes), 0, g_stream, *L, a_id, c_id, b_id, g.nseg, g.ncb, g.per_xcd, g.items, partials);
+  HPGMG_LAUNCH_CHECK("pcg_dot2_kernel");
+  return pcg_fold2(g.items, ab, cb);
 }
 
 }  // extern "C"

@@ -21,6 +21,9 @@ mean-free u is returned.  Periodic cannot be mixed per face.  DESIGN.md §11.2.
 
 Coefficients with jumps: solve(f, method="pcg", rtol=..., max_iter=100) runs conjugate gradients preconditioned with one V-cycle per iteration
 where method="mg" (20 V-cycles at most) stalls; it reports through info.converged instead of raising.  DESIGN.md §11.3.
+method="fpcg" is its flexible form, for grids on which the V-cycle is not one fixed operator -- bc="periodic", or N / box_dim with an odd
+factor, where BiCGStab solves the coarsest level to a tolerance: "pcg" can fail to converge there, "fpcg" does not rely on the symmetry it lacks.
+Elsewhere the two take the same iterations; "fpcg" pays one more fused inner product each.  DESIGN.md §11.4.
 
 NumPy arrays take the host path.  torch tensors on the library's GPU (float64, contiguous) are read and written in place, and results come
 back as tensors on that device.  torch must be imported before this package loads its libraries: both bring a HIP runtime
@@ -38,7 +41,7 @@ _BC = {"dirichlet": H.BC_DIRICHLET, "periodic": H.BC_PERIODIC}
 _FACE = {"dirichlet": H.FACE_DIRICHLET, "neumann": H.FACE_NEUMANN}
 _SMOOTHER = {"cheby": H.SMOOTH_CHEBY, "chebyshev": H.SMOOTH_CHEBY, "gsrb": H.SMOOTH_GSRB, "jacobi": H.SMOOTH_JACOBI}
 _OPERATOR = {"7pt": H.OP_7PT, "27pt": H.OP_27PT, "fv4": H.OP_FV4, "fv2": H.OP_FV2}
-_METHOD = {"fmg": H.USER_FMG, "mg": H.USER_MG, "pcg": H.USER_PCG}
+_METHOD = {"fmg": H.USER_FMG, "mg": H.USER_MG, "pcg": H.USER_PCG, "fpcg": H.USER_FPCG}
 _STATUS = {H.USER_BAD_ARGUMENT: "refused by the library", H.USER_CONFLICT: "the process is configured for another live solver",
            H.USER_MULTI_RANK: "only one rank is supported", H.USER_NOT_FINITE: "holds a value that is not finite",
            H.USER_OUT_OF_RANGE: "is out of range (beta must be > 0, alpha >= 0)",
@@ -50,7 +53,7 @@ _STATUS = {H.USER_BAD_ARGUMENT: "refused by the library", H.USER_CONFLICT: "the 
 class SolveInfo:
     residual: float      # |f - A u|_inf (f after the mean shift)
     norm_f: float        # |f|_inf; with boundary values |f + T(g)|_inf, the right-hand side actually solved
-    vcycles: int         # V-cycles run from the finest level (an F-cycle ends with one; method "pcg": one per iteration)
+    vcycles: int         # V-cycles run from the finest level (an F-cycle ends with one; methods "pcg" and "fpcg": one per iteration)
     converged: bool      # residual < rtol * norm_f
     mean_shift: float    # subtracted from f (periodic without an a alpha term), else 0.0
 
@@ -265,15 +268,17 @@ class Solver:
     def solve(self, f, method="fmg", rtol=1e-10, u0=None, out=None, boundary=None, max_iter=100):
         """u, SolveInfo.  method 'fmg': one F-cycle (the benchmark's solve); 'mg': V-cycles until |f - A u| < rtol |f| (20 at most).
         'pcg': conjugate gradients preconditioned with one V-cycle per iteration, until |f - A u| < rtol |f| or for max_iter iterations
-        (max_iter is read by this method only) -- for coefficients with jumps, where 'mg' stalls.  It does not raise when it stops short:
+        (max_iter is read by the two CG methods only) -- for coefficients with jumps, where 'mg' stalls.  It does not raise when it stops short:
         info.converged is False, u the last iterate and info.residual its residual.  DESIGN.md §11.3.
-        u0: start from it ('pcg': as its first iterate; else u = u0 + e, the correction solved with V-cycles, and method is not used).
+        'fpcg': the same with the flexible beta = -(Ap.z / p.Ap), for bc='periodic' and N / box_dim with an odd factor, where the V-cycle
+        varies between iterations and 'pcg' can fail to converge; same arguments and reporting.  DESIGN.md §11.4.
+        u0: start from it ('pcg', 'fpcg': as the first iterate; else u = u0 + e, the correction solved with V-cycles, and method is not used).
         boundary: Dirichlet values (module docstring); f then stands for f + T(boundary) throughout."""
         if method not in _METHOD:
             raise ValueError(f"method: {method!r} is not one of {sorted(_METHOD)}")
         if not rtol > 0.0:
             raise ValueError(f"rtol: {rtol!r} must be > 0")
-        if method == "pcg" and (isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1):
+        if method in ("pcg", "fpcg") and (isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1):
             raise ValueError(f"max_iter: {max_iter!r} must be an int >= 1")
         _, _, kind = self._arg(f, (self.n,) * 3, "f")
         p0 = self._arg(u0, (self.n,) * 3, "u0", kind)[0] if u0 is not None else None
@@ -282,7 +287,7 @@ class Solver:
         out = self._out(out, kind, f, "out")
         self.set_rhs(f, boundary)
         info = H.UserInfo()
-        if method == "pcg":
+        if method in ("pcg", "fpcg"):
             self._check(self.lib.hpgmg_user_set_max_iterations(self._ptr, int(max_iter)), "max_iter")
         self._sync_torch(kind)
         self._check(self.lib.hpgmg_user_solve(self._ptr, _METHOD[method], float(rtol), p0,

@@ -63,7 +63,7 @@ int hpgmg_fv_main(int argc, char **argv);
  * The operator configuration is process-wide (hpgmg_configure): create refuses one that differs from a live user solver's. */
 enum { HPGMG_USER_OK = 0, HPGMG_USER_BAD_ARGUMENT = -1, HPGMG_USER_CONFLICT = -2, HPGMG_USER_MULTI_RANK = -3, HPGMG_USER_NOT_FINITE = -4,
        HPGMG_USER_OUT_OF_RANGE = -5, HPGMG_USER_NOT_READY = -6, HPGMG_USER_UNSUPPORTED = -7 };
-enum { HPGMG_USER_FMG = 0, HPGMG_USER_MG = 1, HPGMG_USER_PCG = 2 };
+enum { HPGMG_USER_FMG = 0, HPGMG_USER_MG = 1, HPGMG_USER_PCG = 2, HPGMG_USER_FPCG = 3 };
 typedef struct hpgmg_user_solver hpgmg_user_solver;
 typedef struct {
   double norm_of_residual;   /* |f - A u|_inf (f after the mean shift) */
@@ -87,9 +87,13 @@ int  hpgmg_user_set_rhs(hpgmg_user_solver *s, const double *f, int where, double
 int  hpgmg_user_solve(hpgmg_user_solver *s, int method, double rtol, const double *u0, int where, hpgmg_user_info *info);
 /* HPGMG_USER_PCG: conjugate gradients on A u = f preconditioned with one V-cycle per iteration (MGPCGSolve), for coefficients with
  * jumps, on which V-cycles alone stall.  Starts from u0 when given (else 0) and runs until |f - A u| < rtol |f| or for set_max_iterations() iterations
- * (default 100; n < 1: HPGMG_USER_BAD_ARGUMENT; read by this method only).  It never aborts: after the last iteration or a breakdown info.converged is 0,
+ * (default 100; n < 1: HPGMG_USER_BAD_ARGUMENT; read by the two CG methods only).  It never aborts: after the last iteration or a breakdown info.converged is 0,
  * u the last iterate and info.norm_of_residual its true residual.  info.vcycles = preconditioner applications.  The hierarchy grows by three vectors
- * per level at the first such solve.  Boundary values need no F-cycle hook: it solves A0 u = f + T(g) as HPGMG_USER_MG does. */
+ * per level at the first such solve.  Boundary values need no F-cycle hook: it solves A0 u = f + T(g) as HPGMG_USER_MG does.
+ * HPGMG_USER_FPCG: the same with the flexible beta = -(Ap.z / p.Ap) (MGFPCGSolve), which does not rely on the V-cycle being one fixed
+ * symmetric operator.  It is not one where BiCGStab solves the coarsest level to its tolerance -- periodic boxes, N with an odd factor -- and there
+ * HPGMG_USER_PCG can need many times the iterations or none that suffice; elsewhere the two take the same number.  One more fused inner product per
+ * iteration, the same three vectors, the same u0, limits (set_max_iterations is read by both) and reporting. */
 int  hpgmg_user_set_max_iterations(hpgmg_user_solver *s, int n);
 int  hpgmg_user_get_solution(hpgmg_user_solver *s, double *u, int where);
 int  hpgmg_user_apply(hpgmg_user_solver *s, const double *x, double *y, int where);   /* y = A x (apply_op) */

@@ -352,6 +352,9 @@ int hpgmg_hip_pcg_supported(const hpgmg_hip_level *L, int variant);
 int hpgmg_hip_pcg_apply_dot(const hpgmg_hip_level *L, int variant, int Ap_id, int p_id, double a, double b, double h2inv, double *dot);
 int hpgmg_hip_pcg_update(const hpgmg_hip_level *L, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax);
 int hpgmg_hip_pcg_dot(const hpgmg_hip_level *L, int a_id, int b_id, double *dot);
+/* *ab = a . b and *cb = c . b (the flexible CG's r . z and Ap . z): pcg_dot's mapping with three streams read once and two chains per lane,
+ * ONE fold launch for both trees and one wait for both values; each value has the bits of hpgmg_hip_pcg_dot on its pair. */
+int hpgmg_hip_pcg_dot2(const hpgmg_hip_level *L, int a_id, int c_id, int b_id, double *ab, double *cb);
 
 /* dense arrays <-> vector id (include/hpgmg_operators.h hpgmg_dense_pack / unpack; kernels/dense_io.hip).  src / dst are DEVICE arrays.
  * pack: a (nk, nj, ni) array, each extent the level's global one or one more (a Dirichlet face array); writes every double of every box

@@ -54,6 +54,11 @@ void MGPCG(mg_type *all_grids, int onLevel, int x_id, int F_id, double a, double
  * what x_id holds (else from 0).  Returns 1 when |F - A x|_inf < rtol |F|_inf, 0 after max_iter iterations or a breakdown (a zero or non-finite p.Ap, r.z,
  * alpha or beta): x is then the last iterate.  hpgmg_last_solve holds |F|, the TRUE residual norm of x and the number of V-cycles run (= iterations). */
 int  MGPCGSolve(mg_type *all_grids, int onLevel, int x_id, int F_id, double a, double b, double rtol, int max_iter, int x_is_guess);
+/* The flexible form (Notay's FCG truncated to one direction), for a preconditioner that is not one fixed linear operator -- a V-cycle whose
+ * coarsest level BiCGStab solves to a tolerance (periodic boxes, N with an odd factor): MGPCGSolve except that after the V-cycle ONE pass, hpgmg_pcg_dot2,
+ * returns r.z and Ap.z, and beta = -(Ap.z / p.Ap) makes the new direction A-orthogonal to the last one explicitly.  A beta of 0.0 is legitimate (p = z);
+ * only a non-finite one ends the solve.  Arguments, vectors, return value and hpgmg_last_solve as MGPCGSolve. */
+int  MGFPCGSolve(mg_type *all_grids, int onLevel, int x_id, int F_id, double a, double b, double rtol, int max_iter, int x_is_guess);
 void MGPrintTiming(mg_type *all_grids, int fromLevel);
 void MGResetTimers(mg_type *all_grids);
 void richardson_error(mg_type *all_grids, int levelh, int u_id);

@@ -176,6 +176,8 @@ void    hpgmg_boundary_interp_faces(level_type *fine, int id, level_type *coarse
  *   pcg_apply_dot: Ap = A p exactly as apply_op(level, Ap_id, p_id, a, b) leaves it (its ghost exchange and boundary conditions), and *dot = p . Ap
  *   pcg_update:    per interior cell  x = x + alpha * p ;  r = r - alpha * Ap  (the product first, then the sum / difference), *rmax = max |r| (0.0 <= it)
  *   pcg_dot:       *dot = a . b
+ *   pcg_dot2:      *ab = a . b and *cb = c . b in one pass over the three vectors (the flexible CG's r . z and Ap . z: MGFPCGSolve);
+ *                  each of the two in the order below, so *ab has the bits of pcg_dot(a, b) and *cb those of pcg_dot(c, b)
  * The two sums have ONE order, a function of the level's geometry only (it is not dot()'s): with dim the box side, the products a * b of box B are
  * formed first; column c = i + dim * j of segment s (the planes 16 s <= k < min(16 s + 16, dim)) is the chain 0.0 + q(k = 16 s) + q(16 s + 1) + ...;
  * with W = 256 * ceil(dim^2 / 256) and S = ceil(dim / 16) the chains are the leaves V[c + W * (s + S * B)] (0.0 where c >= dim^2) of an array padded
@@ -188,9 +190,11 @@ void    hpgmg_boundary_interp_faces(level_type *fine, int id, level_type *coarse
 int     hpgmg_pcg_apply_dot(level_type *level, int Ap_id, int p_id, double a, double b, double *dot);
 int     hpgmg_pcg_update(level_type *level, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax);
 int     hpgmg_pcg_dot(level_type *level, int a_id, int b_id, double *dot);
+int     hpgmg_pcg_dot2(level_type *level, int a_id, int c_id, int b_id, double *ab, double *cb);   /* *ab = a . b, *cb = c . b */
 int     hpgmg_pcg_apply_dot_host(level_type *level, int Ap_id, int p_id, double a, double b, double *dot);      /* the portable forms themselves (always 0) */
 int     hpgmg_pcg_update_host(level_type *level, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax);
 int     hpgmg_pcg_dot_host(level_type *level, int a_id, int b_id, double *dot);
+int     hpgmg_pcg_dot2_host(level_type *level, int a_id, int c_id, int b_id, double *ab, double *cb);
 /* Launch-bound stretches of a cycle (everything done on levels of <= 64^3 cells between two
  * bottom solves) are bracketed by the cycle driver as a SEGMENT with a key that repeats every
  * solve, so the HIP plugin can capture it once into a hipGraph and replay it.  Plugins without

@@ -5,7 +5,8 @@ a solve of --iters iterations, and one iteration's parts alone -- the V-cycle (z
 level (apply_op, dot, two add_vectors, residual, norm, dot, add_vectors: the operators, unchanged), timed one by one and as one bracket around the whole sequence.  hipEvent pairs on the library's launch
 stream around each call; every scalar is fetched before its call returns, so a pair brackets all of the call's device work.  Prints one JSON
 line: medians in ms, and each fused pass's achieved GB/s for its compulsory traffic per cell (apply_dot 48 B: p, three betas, alpha in, Ap out;
-update 48 B: four reads, two writes; dot 16 B).
+update 48 B: four reads, two writes; dot 16 B).  method="fpcg"  next to it: a solve of the same iterations, and its one pass
+hpgmg_pcg_dot2 (r.z and Ap.z, 24 B) next to two hpgmg_pcg_dot calls on the same vectors.
 
     python tools/user_pcg_timing.py [--n 256] [--repeats 7] [--iters 10] [--cli]
 """
@@ -63,7 +64,7 @@ def main():
     a, b, cells = 1.0, 1.0, float(n) ** 3
     res = {"n": n, "repeats": args.repeats, "iters": args.iters}
     with Solver(n, bc="dirichlet", smoother="cheby", a=a, b=b, lib=lib) as s:
-        S, info, shift, val = s._ptr, H.UserInfo(), ctypes.c_double(), ctypes.c_double()
+        S, info, shift, val, val2 = s._ptr, H.UserInfo(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
         hs = lib.hpgmg_user_solver_of(S)
         L, G = lib.hpgmg_solver_level(hs, 0), lib.hpgmg_solver_mg(hs)
         w = H.WHERE_PLUGIN
@@ -75,15 +76,24 @@ def main():
         res["solve_ms"] = timed(solve)
         res["iterations"] = info.vcycles
         res["per_iteration_ms"] = res["solve_ms"] / info.vcycles
+        fsolve = lambda: lib.hpgmg_user_solve(S, H.USER_FPCG, 1e-300, None, w, ctypes.byref(info))  # noqa: E731  (method="fpcg")
+        fsolve()                                                  # its segments have a key of their own: captured here
+        res["fpcg_solve_ms"] = timed(fsolve)
+        res["fpcg_iterations"] = info.vcycles
+        res["fpcg_per_iteration_ms"] = res["fpcg_solve_ms"] / info.vcycles
         x, r, p = H.VECTOR_U, H.VECTOR_R, lib.hpgmg_vectors_reserved()
         Ap, z, F, T = p + 1, p + 2, H.VECTOR_F, H.VECTOR_TEMP
         res["vcycle_ms"] = timed(lambda: (lib.zero_vector(L, z), lib.MGVCycle(G, z, r, a, b, 0), K.hpgmg_hip_sync()))
         res["pcg_apply_dot_ms"] = timed(lambda: lib.hpgmg_pcg_apply_dot(L, Ap, p, a, b, ctypes.byref(val)))
         res["pcg_update_ms"] = timed(lambda: lib.hpgmg_pcg_update(L, x, r, p, Ap, 1e-9, ctypes.byref(val)))
         res["pcg_dot_ms"] = timed(lambda: lib.hpgmg_pcg_dot(L, r, z, ctypes.byref(val)))
+        # fpcg's one pass for r.z and Ap.z (24 B per cell, one fold, one wait) next to the two pcg_dot calls it replaces (32 B, two of each)
+        res["pcg_dot2_ms"] = timed(lambda: lib.hpgmg_pcg_dot2(L, r, Ap, z, ctypes.byref(val), ctypes.byref(val2)))
+        res["pcg_dot_twice_ms"] = timed(lambda: (lib.hpgmg_pcg_dot(L, r, z, ctypes.byref(val)), lib.hpgmg_pcg_dot(L, Ap, z, ctypes.byref(val2))))
         res["pcg_axpy_ms"] = timed(lambda: (lib.add_vectors(L, p, 1.0, z, 0.5, p), K.hpgmg_hip_sync()))
         res["pcg_outside_vcycle_ms"] = res["pcg_apply_dot_ms"] + res["pcg_update_ms"] + res["pcg_dot_ms"] + res["pcg_axpy_ms"]
-        for key, bytes_per_cell in (("pcg_apply_dot", 48), ("pcg_update", 48), ("pcg_dot", 16)):
+        res["fpcg_outside_vcycle_ms"] = res["pcg_apply_dot_ms"] + res["pcg_update_ms"] + res["pcg_dot2_ms"] + res["pcg_axpy_ms"]
+        for key, bytes_per_cell in (("pcg_apply_dot", 48), ("pcg_update", 48), ("pcg_dot", 16), ("pcg_dot2", 24)):
             res[key + "_GBps"] = bytes_per_cell * cells / (res[key + "_ms"] * 1e-3) / 1e9
         # the passes MGPCG issues per iteration around the V-cycle (mg.c), one by one
         parts = {
@@ -113,7 +123,15 @@ def main():
             lib.add_vectors(L, p, 1.0, z, 0.5, p)
             K.hpgmg_hip_sync()
 
+        def fpcg_body():                                         # MGFPCGSolve's: dot2 in place of dot
+            lib.hpgmg_pcg_apply_dot(L, Ap, p, a, b, ctypes.byref(val))
+            lib.hpgmg_pcg_update(L, x, r, p, Ap, 1e-9, ctypes.byref(val))
+            lib.hpgmg_pcg_dot2(L, r, Ap, z, ctypes.byref(val), ctypes.byref(val2))
+            lib.add_vectors(L, p, 1.0, z, 0.5, p)
+            K.hpgmg_hip_sync()
+
         res["mgpcg_outside_vcycle_ms"] = timed(mgpcg_body)
+        res["fpcg_outside_vcycle_one_bracket_ms"] = timed(fpcg_body)
         res["pcg_outside_vcycle_one_bracket_ms"] = timed(pcg_body)
     for q in dev:
         K.hpgmg_hip_free(q)
