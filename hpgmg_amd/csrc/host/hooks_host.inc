@@ -1,0 +1,346 @@
+/*
+ * hooks_host.inc -- the portable host forms of the dense-array, boundary-value and CG hooks (include/hpgmg_operators.h hpgmg_dense_*,
+ * hpgmg_boundary_*, hpgmg_pcg_*): box by box through the plugin's hpgmg_vector_upload / download.  They are weak, so that a plugin with kernels
+ * for them (the HIP plugin: host/plugin_dense.c, host/plugin_pcg.c) replaces them while one without (the CPU oracle, whose memory is host memory
+ * for either `where`) gets these.  The boundary arithmetic itself is include/hpgmg_boundary_math.h, shared with those kernels.
+ * A part of host/driver.c's translation unit, included there.
+ */
+#include <stdlib.h>
+#include <string.h>
+#include <math.h>
+#include "hpgmg_fv.h"
+#include "hpgmg_boundary_math.h"
+
+/* ------------------------------------------------------------------ dense arrays <-> boxes (include/hpgmg_operators.h) */
+/* mask, wall: hpgmg_dense_pack_walls (0, NULL: hpgmg_dense_pack) */
+static int dense_pack_host(level_type *L, int id, const double *src, int where, int layout, int check, int mask, double *wall) {
+  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || layout < HPGMG_DENSE_CELL || layout > HPGMG_DENSE_FACE_K || !src) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  const int axis = layout - HPGMG_DENSE_FACE_I, n = L->dim.i;
+  const int lo = mask ? (mask >> (2 * axis)) & 1 : 0, hi = mask ? (mask >> (2 * axis + 1)) & 1 : 0;
+  double *wh = NULL;
+  if (lo || hi) { wh = (double *)malloc((size_t)6 * n * n * sizeof(double)); hpgmg_vector_download(wh, wall, (size_t)6 * n * n); }
+  const int high = L->boundary_condition.type == BC_DIRICHLET;      /* a face array holds the high domain face of its axis too */
+  const size_t ni = (size_t)dense_extent(L->dim.i, high && layout == HPGMG_DENSE_FACE_I), nj = (size_t)dense_extent(L->dim.j, high && layout == HPGMG_DENSE_FACE_J);
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  double *box = (double *)malloc((size_t)L->box_volume * sizeof(double));
+  int b, i, j, k, status = 0;
+  for (b = 0; b < L->num_my_boxes; b++) {
+    const box_type *B = &L->my_boxes[b];
+    /* the high ghost layer along the array's axis belongs to it on the domain's high face (Dirichlet face arrays) */
+    const int ei = dim + (ni > (size_t)L->dim.i && B->low.i + dim == L->dim.i);
+    const int ej = dim + (nj > (size_t)L->dim.j && B->low.j + dim == L->dim.j);
+    const int ek = dim + (dense_extent(L->dim.k, high && layout == HPGMG_DENSE_FACE_K) > L->dim.k && B->low.k + dim == L->dim.k);
+    memset(box, 0, (size_t)L->box_volume * sizeof(double));
+    for (k = 0; k < ek; k++) for (j = 0; j < ej; j++) for (i = 0; i < ei; i++) {
+      const double v = src[((size_t)(B->low.k + k) * nj + (size_t)(B->low.j + j)) * ni + (size_t)(B->low.i + i)];
+      if (!isfinite(v)) status |= HPGMG_DENSE_NOT_FINITE;
+      else if ((check == HPGMG_DENSE_CHECK_POSITIVE && !(v > 0.0)) || (check == HPGMG_DENSE_CHECK_NONNEGATIVE && !(v >= 0.0))) status |= HPGMG_DENSE_OUT_OF_RANGE;
+      const int c = axis == 0 ? i : axis == 1 ? j : k, gc = (axis == 0 ? B->low.i : axis == 1 ? B->low.j : B->low.k) + c;
+      if ((lo && gc == 0) || (hi && gc == n)) {               /* a masked domain wall: its beta goes to the wall array, the vector takes 0.0 */
+        const int q = axis == 2 ? B->low.j + j : B->low.k + k, p = axis == 0 ? B->low.j + j : B->low.i + i;
+        wh[((size_t)(2 * axis + (gc == n)) * n + q) * n + p] = v;
+        box[(i + g) + (j + g) * jS + (k + g) * kS] = 0.0;
+      } else
+      box[(i + g) + (j + g) * jS + (k + g) * kS] = v;
+    }
+    hpgmg_vector_upload(B->vectors[id], box, (size_t)L->box_volume);
+  }
+  free(box);
+  if (wh) { hpgmg_vector_upload(wall, wh, (size_t)6 * n * n); free(wh); }
+  return status;
+}
+__attribute__((weak)) int hpgmg_dense_pack(level_type *L, int id, const double *src, int where, int layout, int check) {
+  return dense_pack_host(L, id, src, where, layout, check, 0, NULL);
+}
+__attribute__((weak)) int hpgmg_dense_pack_walls(level_type *L, int id, const double *src, int where, int layout, int check, int mask, double *wall) {
+  if (layout < HPGMG_DENSE_FACE_I || !wall || mask < 0 || mask > 63 || L->boundary_condition.type != BC_DIRICHLET || L->dim.i != L->dim.j || L->dim.i != L->dim.k) return -1;
+  return dense_pack_host(L, id, src, where, layout, check, mask, wall);
+}
+__attribute__((weak)) int hpgmg_dense_unpack(level_type *L, int id, double *dst, int where) {
+  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || !dst) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  const size_t ni = (size_t)L->dim.i, nj = (size_t)L->dim.j;
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  double *box = (double *)malloc((size_t)L->box_volume * sizeof(double));
+  int b, i, j, k;
+  for (b = 0; b < L->num_my_boxes; b++) {
+    const box_type *B = &L->my_boxes[b];
+    hpgmg_vector_download(box, B->vectors[id], (size_t)L->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++)
+      dst[((size_t)(B->low.k + k) * nj + (size_t)(B->low.j + j)) * ni + (size_t)(B->low.i + i)] = box[(i + g) + (j + g) * jS + (k + g) * kS];
+  }
+  free(box);
+  return 0;
+}
+
+/* ------------------------------------------------------------------ boundary values: host defaults (include/hpgmg_operators.h)
+ * Box by box through hpgmg_vector_upload / download, weak like the dense pair above (the HIP plugin: host/plugin_dense.c).  The domain is the
+ * user problems' cube of n = dim.i cells per side. */
+static int bnd_box_on_domain_face(const level_type *L, const box_type *B) {
+  const int n = L->dim.i, d = L->box_dim;
+  return B->low.i == 0 || B->low.j == 0 || B->low.k == 0 || B->low.i + d == n || B->low.j + d == n || B->low.k + d == n;
+}
+/* beta of domain face `face` of the box cell at padded offset ijk */
+static double bnd_beta(const double *bi, const double *bj, const double *bk, int face, int ijk, int jS, int kS) {
+  switch (face) {
+    case 0: return bi[ijk];  case 1: return bi[ijk + 1];
+    case 2: return bj[ijk];  case 3: return bj[ijk + jS];
+    case 4: return bk[ijk];  default: return bk[ijk + kS];
+  }
+}
+static double *bnd_download(const double *src, size_t n) {
+  double *h = (double *)malloc(n * sizeof(double));
+  hpgmg_vector_download(h, src, n);
+  return h;
+}
+
+/* mask, wall: hpgmg_dense_pack_lifted_faces (0, NULL: hpgmg_dense_pack_lifted) */
+static int dense_pack_lifted_host(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
+  if (!g || L->boundary_condition.type != BC_DIRICHLET) return -1;
+  const int st = hpgmg_dense_pack(L, id, f, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE);
+  if (st < 0) return st;
+  const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const double w = bnd_weight(b, L->h), wn = bnd_weight_neumann(b, L->h);
+  double *gh = bnd_download(g, (size_t)6 * n * n), *wh = mask ? bnd_download(wall, (size_t)6 * n * n) : NULL;
+  double *v = (double *)malloc((size_t)L->box_volume * 4 * sizeof(double));
+  double *bi = v + L->box_volume, *bj = bi + L->box_volume, *bk = bj + L->box_volume;
+  int box, i, j, k, face, bad = 0;
+  for (box = 0; box < L->num_my_boxes; box++) {
+    const box_type *B = &L->my_boxes[box];
+    if (!bnd_box_on_domain_face(L, B)) continue;
+    hpgmg_vector_download(v, B->vectors[id], (size_t)L->box_volume);
+    hpgmg_vector_download(bi, B->vectors[VECTOR_BETA_I], (size_t)L->box_volume);
+    hpgmg_vector_download(bj, B->vectors[VECTOR_BETA_J], (size_t)L->box_volume);
+    hpgmg_vector_download(bk, B->vectors[VECTOR_BETA_K], (size_t)L->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      double T = 0.0;
+      int on = 0;
+      for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
+        const double gv = gh[bnd_entry(n, face, gi, gj, gk)];
+        if (!isfinite(gv)) bad = 1;
+        if ((mask >> face) & 1) T = T + (wn * wh[bnd_entry(n, face, gi, gj, gk)]) * gv;
+        else T = T + (w * bnd_beta(bi, bj, bk, face, ijk, jS, kS)) * gv;
+        on = 1;
+      }
+      if (on) v[ijk] = v[ijk] + T;
+    }
+    hpgmg_vector_upload(B->vectors[id], v, (size_t)L->box_volume);
+  }
+  free(v); free(gh); free(wh);
+  return st | (bad ? HPGMG_DENSE_NOT_FINITE : 0);
+}
+__attribute__((weak)) int hpgmg_dense_pack_lifted(level_type *L, int id, const double *f, int where, const double *g, double b) {
+  return dense_pack_lifted_host(L, id, f, where, g, b, 0, NULL);
+}
+__attribute__((weak)) int hpgmg_dense_pack_lifted_faces(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
+  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
+  return dense_pack_lifted_host(L, id, f, where, g, b, mask, wall);
+}
+
+static int boundary_flux_host(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
+  const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t len = (size_t)6 * n * n;
+  const double w = bnd_weight(b, L->h), wn = bnd_weight_neumann(b, L->h);
+  double *gh = bnd_download(g, len), *ph = (double *)calloc(len, sizeof(double)), *wh = mask ? bnd_download(wall, len) : NULL;
+  double *bi = (double *)malloc((size_t)L->box_volume * 3 * sizeof(double)), *bj = bi + L->box_volume, *bk = bj + L->box_volume;
+  int box, i, j, k, face, bad = 0;
+  size_t e;
+  for (e = 0; e < len; e++) if (!isfinite(gh[e])) bad = 1;
+  for (box = 0; box < L->num_my_boxes; box++) {
+    const box_type *B = &L->my_boxes[box];
+    if (!bnd_box_on_domain_face(L, B)) continue;
+    hpgmg_vector_download(bi, B->vectors[VECTOR_BETA_I], (size_t)L->box_volume);
+    hpgmg_vector_download(bj, B->vectors[VECTOR_BETA_J], (size_t)L->box_volume);
+    hpgmg_vector_download(bk, B->vectors[VECTOR_BETA_K], (size_t)L->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
+        e = bnd_entry(n, face, gi, gj, gk);
+        if ((mask >> face) & 1) ph[e] = (wn * wh[e]) * gh[e];
+        else ph[e] = (w * bnd_beta(bi, bj, bk, face, ijk, jS, kS)) * gh[e];
+      }
+    }
+  }
+  hpgmg_vector_upload(phi, ph, len);
+  free(bi); free(ph); free(gh); free(wh);
+  return bad ? HPGMG_DENSE_NOT_FINITE : 0;
+}
+__attribute__((weak)) int hpgmg_boundary_flux(level_type *L, double *phi, const double *g, double b) { return boundary_flux_host(L, phi, g, b, 0, NULL); }
+__attribute__((weak)) int hpgmg_boundary_flux_faces(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
+  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
+  return boundary_flux_host(L, phi, g, b, mask, wall);
+}
+
+__attribute__((weak)) void hpgmg_boundary_restrict(level_type *Lc, double *g_c, level_type *Lf, const double *g_f) {
+  const int nc = Lc->dim.i, nf = Lf->dim.i;
+  double *gf = bnd_download(g_f, (size_t)6 * nf * nf), *gc = (double *)malloc((size_t)6 * nc * nc * sizeof(double));
+  int face, q, p;
+  for (face = 0; face < 6; face++) for (q = 0; q < nc; q++) for (p = 0; p < nc; p++) {
+    const double *e = gf + ((size_t)face * nf + 2 * q) * nf + 2 * p;
+    gc[((size_t)face * nc + q) * nc + p] = (e[0] + e[1] + e[nf] + e[nf + 1]) * 0.25;
+  }
+  hpgmg_vector_upload(g_c, gc, (size_t)6 * nc * nc);
+  free(gc); free(gf);
+}
+
+__attribute__((weak)) void hpgmg_boundary_lift(level_type *L, int id, const double *phi, const double *phi_fine, double sign) {
+  const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  double *ph = bnd_download(phi, (size_t)6 * n * n), *pf = phi_fine ? bnd_download(phi_fine, (size_t)24 * n * n) : NULL;
+  double *v = (double *)malloc((size_t)L->box_volume * sizeof(double));
+  int box, i, j, k, face;
+  for (box = 0; box < L->num_my_boxes; box++) {
+    const box_type *B = &L->my_boxes[box];
+    if (!bnd_box_on_domain_face(L, B)) continue;
+    hpgmg_vector_download(v, B->vectors[id], (size_t)L->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      double T = 0.0;
+      int on = 0;
+      for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) { T = T + ph[bnd_entry(n, face, gi, gj, gk)]; on = 1; }
+      if (!on) continue;
+      if (pf) T = T - 0.125 * bnd_fine_sum(n, pf, gi, gj, gk);
+      v[ijk] = v[ijk] + sign * T;
+    }
+    hpgmg_vector_upload(B->vectors[id], v, (size_t)L->box_volume);
+  }
+  free(v); free(pf); free(ph);
+}
+
+/* D(c) of hpgmg_boundary_interp / _interp_faces for fine cell (gi,gj,gk): u the coarse iterate as a dense (nc,nc,nc) array (read only next to
+ * a Neumann wall: NULL with mask 0), hc the coarse h */
+static double bnd_interp_delta(int nc, const double *g, const double *u, double hc, int mask, int gi, int gj, int gk) {
+  const bnd_p1_cell F = bnd_p1_of(gi, gj, gk);
+  double D = 0.0, w;
+  int t, q[3];
+  for (t = 1; t < 8; t++) if (bnd_p1_ghost(nc, F, t, q, &w)) {
+    const bnd_ghost G = bnd_ghost_faces(nc, g, hc, mask, q[0], q[1], q[2]);
+    D = D + w * (G.needs_u ? G.c * u[((size_t)G.P[2] * nc + G.P[1]) * nc + G.P[0]] + G.s : G.s);
+  }
+  return D;
+}
+
+/* mask: hpgmg_boundary_interp_faces, which reads the coarse iterate next to a Neumann wall (0: hpgmg_boundary_interp) */
+static void boundary_interp_host(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) {
+  const int n = Lf->dim.i, nc = Lc->dim.i, g0 = Lf->box_ghosts, dim = Lf->box_dim, jS = Lf->box_jStride, kS = Lf->box_kStride;
+  double *gc = bnd_download(g_c, (size_t)6 * nc * nc), *v = (double *)malloc((size_t)Lf->box_volume * sizeof(double));
+  double *uc = mask ? (double *)malloc((size_t)nc * nc * nc * sizeof(double)) : NULL;
+  int box, i, j, k;
+  if (uc) hpgmg_dense_unpack(Lc, id, uc, HPGMG_WHERE_HOST);
+  for (box = 0; box < Lf->num_my_boxes; box++) {
+    const box_type *B = &Lf->my_boxes[box];
+    if (!bnd_box_on_domain_face(Lf, B)) continue;
+    hpgmg_vector_download(v, B->vectors[id], (size_t)Lf->box_volume);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      if (gi > 0 && gj > 0 && gk > 0 && gi < n - 1 && gj < n - 1 && gk < n - 1) continue;
+      v[ijk] = v[ijk] + bnd_interp_delta(nc, gc, uc, Lc->h, mask, gi, gj, gk);
+    }
+    hpgmg_vector_upload(B->vectors[id], v, (size_t)Lf->box_volume);
+  }
+  free(uc); free(v); free(gc);
+}
+__attribute__((weak)) void hpgmg_boundary_interp(level_type *Lf, int id, level_type *Lc, const double *g_c) { boundary_interp_host(Lf, id, Lc, g_c, 0); }
+__attribute__((weak)) void hpgmg_boundary_interp_faces(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) { boundary_interp_host(Lf, id, Lc, g_c, mask); }
+
+/* ------------------------------------------------------------------ the CG passes: portable forms (include/hpgmg_operators.h; DESIGN.md §11.3)
+ * The operators, then the sums on the host from downloaded boxes, in the one order the header defines.  The hooks are weak like the dense pair above:
+ * the HIP plugin (host/plugin_pcg.c) replaces them with its kernels and comes back to the _host forms on a level those do not take. */
+typedef struct { double *V; size_t W, S, len; } pcg_leaves;
+static pcg_leaves pcg_leaves_of(const level_type *L) {
+  pcg_leaves P;
+  const size_t dim = (size_t)L->box_dim, used = HPGMG_PCG_COLUMNS * ((dim * dim + HPGMG_PCG_COLUMNS - 1) / HPGMG_PCG_COLUMNS);
+  P.W = used; P.S = (dim + HPGMG_PCG_SEGMENT - 1) / HPGMG_PCG_SEGMENT;
+  for (P.len = 1; P.len < P.W * P.S * (size_t)L->num_my_boxes; P.len *= 2) {}
+  P.V = (double *)calloc(P.len, sizeof(double));
+  return P;
+}
+static double pcg_fold(pcg_leaves *P) {
+  size_t stride, m;
+  for (stride = 1; stride < P->len; stride *= 2)
+    for (m = 0; m + stride < P->len; m += 2 * stride) P->V[m] = P->V[m] + P->V[m + stride];
+  const double sum = P->V[0];
+  free(P->V);
+  return sum;
+}
+/* the leaves of box bx: per column and segment the chain over its planes of the products va * vb */
+static void pcg_box_leaves(const level_type *L, pcg_leaves *P, int bx, const double *va, const double *vb) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  int i, j, k;
+  size_t s;
+  for (s = 0; s < P->S; s++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+    const int k1 = (int)(s + 1) * HPGMG_PCG_SEGMENT < dim ? (int)(s + 1) * HPGMG_PCG_SEGMENT : dim;
+    double chain = 0.0;
+    for (k = (int)s * HPGMG_PCG_SEGMENT; k < k1; k++) {
+      const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+      const double q = va[ijk] * vb[ijk];
+      chain = chain + q;
+    }
+    P->V[(size_t)(i + dim * j) + P->W * (s + P->S * (size_t)bx)] = chain;
+  }
+}
+int hpgmg_pcg_dot_host(level_type *L, int a_id, int b_id, double *dot) {
+  double *va = (double *)malloc((size_t)L->box_volume * sizeof(double)), *vb = (double *)malloc((size_t)L->box_volume * sizeof(double));
+  pcg_leaves P = pcg_leaves_of(L);
+  int bx;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    hpgmg_vector_download(va, L->my_boxes[bx].vectors[a_id], (size_t)L->box_volume);
+    hpgmg_vector_download(vb, L->my_boxes[bx].vectors[b_id], (size_t)L->box_volume);
+    pcg_box_leaves(L, &P, bx, va, vb);
+  }
+  free(va); free(vb);
+  *dot = pcg_fold(&P);
+  return 0;
+}
+/* a . b and c . b from one download of b: two trees of the one order, so each has the bits of hpgmg_pcg_dot_host on its pair */
+int hpgmg_pcg_dot2_host(level_type *L, int a_id, int c_id, int b_id, double *ab, double *cb) {
+  const size_t vol = (size_t)L->box_volume;
+  double *v = (double *)malloc(3 * vol * sizeof(double)), *va = v, *vc = v + vol, *vb = v + 2 * vol;
+  pcg_leaves P = pcg_leaves_of(L), Q = pcg_leaves_of(L);
+  int bx;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    hpgmg_vector_download(va, L->my_boxes[bx].vectors[a_id], vol);
+    hpgmg_vector_download(vc, L->my_boxes[bx].vectors[c_id], vol);
+    hpgmg_vector_download(vb, L->my_boxes[bx].vectors[b_id], vol);
+    pcg_box_leaves(L, &P, bx, va, vb);
+    pcg_box_leaves(L, &Q, bx, vc, vb);
+  }
+  free(v);
+  *ab = pcg_fold(&P);
+  *cb = pcg_fold(&Q);
+  return 0;
+}
+int hpgmg_pcg_apply_dot_host(level_type *L, int Ap_id, int p_id, double a, double b, double *dot) {
+  apply_op(L, Ap_id, p_id, a, b);
+  return hpgmg_pcg_dot_host(L, p_id, Ap_id, dot);
+}
+int hpgmg_pcg_update_host(level_type *L, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t vol = (size_t)L->box_volume;
+  double *v = (double *)malloc(4 * vol * sizeof(double)), *x = v, *r = v + vol, *p = v + 2 * vol, *Ap = v + 3 * vol;
+  double best = 0.0;
+  int bx, i, j, k;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    const box_type *B = &L->my_boxes[bx];
+    hpgmg_vector_download(x, B->vectors[x_id], vol); hpgmg_vector_download(r, B->vectors[r_id], vol);
+    hpgmg_vector_download(p, B->vectors[p_id], vol); hpgmg_vector_download(Ap, B->vectors[Ap_id], vol);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+      const double dx = alpha * p[ijk], dr = alpha * Ap[ijk];
+      x[ijk] = x[ijk] + dx;
+      r[ijk] = r[ijk] - dr;
+      const double f = fabs(r[ijk]);
+      if (f > best) best = f;
+    }
+    hpgmg_vector_upload(B->vectors[x_id], x, vol); hpgmg_vector_upload(B->vectors[r_id], r, vol);
+  }
+  free(v);
+  *rmax = best;
+  return 0;
+}
+__attribute__((weak)) int hpgmg_pcg_apply_dot(level_type *L, int Ap_id, int p_id, double a, double b, double *dot) { return hpgmg_pcg_apply_dot_host(L, Ap_id, p_id, a, b, dot); }
+__attribute__((weak)) int hpgmg_pcg_update(level_type *L, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax) { return hpgmg_pcg_update_host(L, x_id, r_id, p_id, Ap_id, alpha, rmax); }
+__attribute__((weak)) int hpgmg_pcg_dot(level_type *L, int a_id, int b_id, double *dot) { return hpgmg_pcg_dot_host(L, a_id, b_id, dot); }
+__attribute__((weak)) int hpgmg_pcg_dot2(level_type *L, int a_id, int c_id, int b_id, double *ab, double *cb) { return hpgmg_pcg_dot2_host(L, a_id, c_id, b_id, ab, cb); }
+

@@ -2,14 +2,11 @@
  * plugin_dense.c -- hpgmg_dense_pack / hpgmg_dense_unpack of the operator plugin (include/hpgmg_operators.h): one launch of
  * kernels/dense_io.hip per array.  A device array is read / written in place; a host array is copied once into the level's staging buffer
  * (allocated on first use, freed with the level) and packed from there, or unpacked into it and copied out once.  They replace the weak
- * host defaults of host/driver.c, which go box by box through hpgmg_vector_upload / download.  The boundary-value hooks below likewise.
+ * host defaults of host/hooks_host.inc, which go box by box through hpgmg_vector_upload / download.  The boundary-value hooks below likewise
+ * (their arithmetic: include/hpgmg_boundary_math.h, shared with the kernels and the host defaults).
  */
 #include "plugin_internal.h"
-
-static size_t dense_extent(const level_type *L, int layout, int axis) {     /* axis 0 = i, 1 = j, 2 = k */
-  const int n = axis == 0 ? L->dim.i : axis == 1 ? L->dim.j : L->dim.k;
-  return (size_t)n + (layout == HPGMG_DENSE_FACE_I + axis && L->boundary_condition.type == BC_DIRICHLET);
-}
+#include "hpgmg_boundary_math.h"
 
 static double *dense_stage(backend_t *B, size_t n) {
   if (B->dense_stage_len < n) {
@@ -20,20 +17,30 @@ static double *dense_stage(backend_t *B, size_t n) {
   }
   return B->dense_stage;
 }
+/* what every pack checks first, then the caller's len doubles at src where the kernels can read them: in place for a device array, else
+ * copied once into the staging buffer.  NULL: the call is refused */
+static const double *dense_source(level_type *L, int id, const double *src, int where, size_t len) {
+  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || !src) return NULL;
+  if (where == HPGMG_WHERE_PLUGIN) return src;
+  if (where != HPGMG_WHERE_HOST) return NULL;
+  double *stage = dense_stage(hp_backend_of(L), len);
+  HIP_OK(hpgmg_hip_memcpy_h2d(stage, src, len * sizeof(double)));
+  return stage;
+}
+static void dense_extents(const level_type *L, int layout, size_t n[3]) {      /* of a dense array of that layout, i, j, k */
+  const int high = L->boundary_condition.type == BC_DIRICHLET;
+  n[0] = (size_t)dense_extent(L->dim.i, high && layout == HPGMG_DENSE_FACE_I);
+  n[1] = (size_t)dense_extent(L->dim.j, high && layout == HPGMG_DENSE_FACE_J);
+  n[2] = (size_t)dense_extent(L->dim.k, high && layout == HPGMG_DENSE_FACE_K);
+}
 
 int hpgmg_dense_pack(level_type *L, int id, const double *src, int where, int layout, int check) {
-  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || layout < HPGMG_DENSE_CELL || layout > HPGMG_DENSE_FACE_K || !src) return -1;
-  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
-  backend_t *B = hp_backend_of(L);
-  const size_t ni = dense_extent(L, layout, 0), nj = dense_extent(L, layout, 1), nk = dense_extent(L, layout, 2);
-  const double *d_src = src;
+  size_t n[3];
   int status = 0;
-  if (where == HPGMG_WHERE_HOST) {
-    double *stage = dense_stage(B, ni * nj * nk);
-    HIP_OK(hpgmg_hip_memcpy_h2d(stage, src, ni * nj * nk * sizeof(double)));
-    d_src = stage;
-  }
-  HIP_OK(hpgmg_hip_dense_pack(&B->dev, id, d_src, (int)ni, (int)nj, (int)nk, check, &status));
+  if (layout < HPGMG_DENSE_CELL || layout > HPGMG_DENSE_FACE_K) return -1;
+  dense_extents(L, layout, n);
+  if (!(src = dense_source(L, id, src, where, n[0] * n[1] * n[2]))) return -1;
+  HIP_OK(hpgmg_hip_dense_pack(&hp_backend_of(L)->dev, id, src, (int)n[0], (int)n[1], (int)n[2], check, &status));
   return status;
 }
 
@@ -49,31 +56,37 @@ int hpgmg_dense_unpack(level_type *L, int id, double *dst, int where) {
   return 0;
 }
 
-/* boundary values (include/hpgmg_operators.h): one launch of kernels/dense_boundary.hip each.  g, phi are device arrays (hpgmg_vector_alloc);
- * f is staged as hpgmg_dense_pack stages it. */
-static double bnd_weight(const level_type *L, double b) { return (2.0 * b) * (1.0 / (L->h * L->h)); }
+/* boundary values (include/hpgmg_operators.h): one launch of kernels/dense_boundary.hip each.  g, phi, wall are device arrays
+ * (hpgmg_vector_alloc); f is staged as hpgmg_dense_pack stages it.  The plain forms are the per-face forms without a Neumann wall. */
+int hpgmg_dense_pack_walls(level_type *L, int id, const double *src, int where, int layout, int check, int mask, double *wall) {
+  size_t n[3];
+  int status = 0;
+  if (layout < HPGMG_DENSE_FACE_I || layout > HPGMG_DENSE_FACE_K || !wall) return -1;
+  if (mask < 0 || mask > 63 || L->boundary_condition.type != BC_DIRICHLET || L->dim.i != L->dim.j || L->dim.i != L->dim.k) return -1;
+  dense_extents(L, layout, n);
+  if (!(src = dense_source(L, id, src, where, n[0] * n[1] * n[2]))) return -1;
+  HIP_OK(hpgmg_hip_dense_pack_walls(&hp_backend_of(L)->dev, id, src, layout - HPGMG_DENSE_FACE_I, check, mask, wall, &status));
+  return status;
+}
 
+int hpgmg_dense_pack_lifted_faces(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
+  int status = 0;
+  if (!g || L->boundary_condition.type != BC_DIRICHLET || mask < 0 || mask > 63 || (mask && !wall)) return -1;
+  if (!(f = dense_source(L, id, f, where, (size_t)L->dim.i * L->dim.j * L->dim.k))) return -1;
+  HIP_OK(hpgmg_hip_dense_pack_lifted_faces(&hp_backend_of(L)->dev, id, f, g, bnd_weight(b, L->h), mask, wall, bnd_weight_neumann(b, L->h), &status));
+  return status;
+}
 int hpgmg_dense_pack_lifted(level_type *L, int id, const double *f, int where, const double *g, double b) {
-  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || !f || !g || L->boundary_condition.type != BC_DIRICHLET) return -1;
-  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
-  backend_t *B = hp_backend_of(L);
-  const size_t n = (size_t)L->dim.i * L->dim.j * L->dim.k;
-  const double *d_src = f;
-  int status = 0;
-  if (where == HPGMG_WHERE_HOST) {
-    double *stage = dense_stage(B, n);
-    HIP_OK(hpgmg_hip_memcpy_h2d(stage, f, n * sizeof(double)));
-    d_src = stage;
-  }
-  HIP_OK(hpgmg_hip_dense_pack_lifted(&B->dev, id, d_src, g, bnd_weight(L, b), &status));
-  return status;
+  return hpgmg_dense_pack_lifted_faces(L, id, f, where, g, b, 0, NULL);
 }
 
-int hpgmg_boundary_flux(level_type *L, double *phi, const double *g, double b) {
+int hpgmg_boundary_flux_faces(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
   int status = 0;
-  HIP_OK(hpgmg_hip_boundary_flux(&hp_backend_of(L)->dev, phi, g, bnd_weight(L, b), &status));
+  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
+  HIP_OK(hpgmg_hip_boundary_flux_faces(&hp_backend_of(L)->dev, phi, g, bnd_weight(b, L->h), mask, wall, bnd_weight_neumann(b, L->h), &status));
   return status;
 }
+int hpgmg_boundary_flux(level_type *L, double *phi, const double *g, double b) { return hpgmg_boundary_flux_faces(L, phi, g, b, 0, NULL); }
 
 void hpgmg_boundary_restrict(level_type *Lc, double *g_c, level_type *Lf, const double *g_f) {
   (void)Lf;
@@ -86,50 +99,6 @@ void hpgmg_boundary_lift(level_type *L, int id, const double *phi, const double 
 
 void hpgmg_boundary_interp(level_type *Lf, int id, level_type *Lc, const double *g_c) {
   HIP_OK(hpgmg_hip_boundary_interp(&hp_backend_of(Lf)->dev, id, g_c, Lc->dim.i));
-}
-
-/* Neumann walls (include/hpgmg_operators.h): the same launches with per-face kinds */
-static double bnd_weight_neumann(const level_type *L, double b) { return b * (1.0 / L->h); }
-
-int hpgmg_dense_pack_walls(level_type *L, int id, const double *src, int where, int layout, int check, int mask, double *wall) {
-  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || layout < HPGMG_DENSE_FACE_I || layout > HPGMG_DENSE_FACE_K || !src || !wall) return -1;
-  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
-  if (mask < 0 || mask > 63 || L->boundary_condition.type != BC_DIRICHLET || L->dim.i != L->dim.j || L->dim.i != L->dim.k) return -1;
-  backend_t *B = hp_backend_of(L);
-  const size_t ni = dense_extent(L, layout, 0), nj = dense_extent(L, layout, 1), nk = dense_extent(L, layout, 2);
-  const double *d_src = src;
-  int status = 0;
-  if (where == HPGMG_WHERE_HOST) {
-    double *stage = dense_stage(B, ni * nj * nk);
-    HIP_OK(hpgmg_hip_memcpy_h2d(stage, src, ni * nj * nk * sizeof(double)));
-    d_src = stage;
-  }
-  HIP_OK(hpgmg_hip_dense_pack_walls(&B->dev, id, d_src, layout - HPGMG_DENSE_FACE_I, check, mask, wall, &status));
-  return status;
-}
-
-int hpgmg_dense_pack_lifted_faces(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
-  if (L->num_ranks != 1 || id < 0 || id >= L->numVectors || !f || !g || L->boundary_condition.type != BC_DIRICHLET) return -1;
-  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
-  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
-  backend_t *B = hp_backend_of(L);
-  const size_t n = (size_t)L->dim.i * L->dim.j * L->dim.k;
-  const double *d_src = f;
-  int status = 0;
-  if (where == HPGMG_WHERE_HOST) {
-    double *stage = dense_stage(B, n);
-    HIP_OK(hpgmg_hip_memcpy_h2d(stage, f, n * sizeof(double)));
-    d_src = stage;
-  }
-  HIP_OK(hpgmg_hip_dense_pack_lifted_faces(&B->dev, id, d_src, g, bnd_weight(L, b), mask, wall, bnd_weight_neumann(L, b), &status));
-  return status;
-}
-
-int hpgmg_boundary_flux_faces(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
-  int status = 0;
-  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
-  HIP_OK(hpgmg_hip_boundary_flux_faces(&hp_backend_of(L)->dev, phi, g, bnd_weight(L, b), mask, wall, bnd_weight_neumann(L, b), &status));
-  return status;
 }
 
 void hpgmg_boundary_interp_faces(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) {

@@ -1,12 +1,12 @@
 /*
  * plugin_pcg.c -- hpgmg_pcg_apply_dot / _update / _dot / _dot2 of the operator plugin (include/hpgmg_operators.h): one pass of
  * kernels/pcg.hip each, on the levels those kernels take -- the 7-point variable-coefficient operator in ghost-free mode with every box local, which
- * is every level of a user problem.  Anywhere else the portable forms of host/driver.c run (the operators, then the sums on the host): the same bits,
+ * is every level of a user problem.  Anywhere else the portable forms of host/hooks_host.inc run (the operators, then the sums on the host): the same bits,
  * and the return value says which of the two it was.
  */
 #include "plugin_internal.h"
 
-/* the portable forms live with the host layer (host/driver.c); under another driver (INTEGRATION.md Route B) they are absent, and so is every caller */
+/* the portable forms live with the host layer (host/hooks_host.inc); under another driver (INTEGRATION.md Route B) they are absent, and so is every caller */
 extern int hpgmg_pcg_apply_dot_host(level_type *, int, int, double, double, double *) __attribute__((weak));
 extern int hpgmg_pcg_update_host(level_type *, int, int, int, int, double, double *) __attribute__((weak));
 extern int hpgmg_pcg_dot_host(level_type *, int, int, double *) __attribute__((weak));

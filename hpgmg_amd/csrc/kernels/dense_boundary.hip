@@ -1,6 +1,7 @@
 // dense_boundary.hip -- inhomogeneous Dirichlet values of the dense-array API (include/hpgmg_operators.h hpgmg_dense_pack_lifted,
 // hpgmg_boundary_flux / _restrict / _lift / _interp and their per-face-kind forms for Neumann walls; the formulas and their order are written
-// there and in DESIGN.md §11.1, §11.2).
+// there and in DESIGN.md §11.1, §11.2).  The arithmetic the host defaults (host/hooks_host.inc) must match bit for bit is not written here but in
+// include/hpgmg_boundary_math.h, which both compile.
 //
 // A boundary array is 6 x n x n doubles (n = the level's cells per side, a cube): [0], [1] i-low / i-high indexed [k][j], [2], [3] j-low /
 // j-high [k][i], [4], [5] k-low / k-high [j][i].  w = (2.0 * b) * (1.0 / (h * h)) comes from the host, so every term (w * beta) * g has the
@@ -13,20 +14,13 @@
 // a domain face does nothing.  A cell on several domain faces (edge, corner) is handled once, by the position of the first face it touches
 // in the order i-low .. k-high, so no two lanes write one cell.  One launch per level and operation; they are launch bound (6 n^2 cells).
 #include "common.hpp"
+#include "hpgmg_boundary_math.h"
 
 namespace hpgmg {
 
 constexpr int kBndThreads = 256;
 static int *g_bnd_flag = nullptr;               // validation bits of the last lifted pack / flux (device word)
 
-__device__ __forceinline__ bool bnd_touches(int n, int face, int gi, int gj, int gk) {
-  const int c = face < 2 ? gi : face < 4 ? gj : gk;
-  return (face & 1) ? c == n - 1 : c == 0;
-}
-__device__ __forceinline__ int bnd_entry(int n, int face, int gi, int gj, int gk) {     // 6 n^2 < 2^31 for any level that fits a device
-  const int q = face < 4 ? gk : gj, p = face < 2 ? gj : gi;
-  return (face * n + q) * n + p;
-}
 // offset, from a cell's padded offset, of its beta on face `face`, and the vector holding it
 __device__ __forceinline__ int bnd_beta_vec(int face) { return face < 2 ? VECTOR_BETA_I : face < 4 ? VECTOR_BETA_J : VECTOR_BETA_K; }
 __device__ __forceinline__ int bnd_beta_step(const hpgmg_hip_level &L, int face) {
@@ -133,57 +127,16 @@ __global__ __launch_bounds__(kBndThreads) void boundary_lift_kernel(const hpgmg_
       const int gi = li + P.i, gj = lj + P.j, gk = lk + P.k;
       double T = 0.0;
       for (int face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) T = T + phi[bnd_entry(n, face, gi, gj, gk)];
-      if (phi_fine) {                      // S: the four finer entries under each face entry, faces in order
-        const int nf = 2 * n;
-        double S = 0.0;
-        for (int face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
-          const int q = face < 4 ? gk : gj, p = face < 2 ? gj : gi;
-          const double *e = phi_fine + (face * nf + 2 * q) * nf + 2 * p;
-          S = S + (((e[0] + e[1]) + e[nf]) + e[nf + 1]);
-        }
-        T = T - 0.125 * S;
-      }
+      if (phi_fine) T = T - 0.125 * bnd_fine_sum(n, phi_fine, gi, gj, gk);
       const int c = P.i + P.j * L.jStride + P.k * L.kStride;
       v[c] = v[c] + sign * T;
     }
   }
 }
 
-// the delta of the coarse ghost at (ci, cj, ck): host/driver.c bnd_ghost_delta, expression for expression
-#define BND_AT(f, i, j, k) g[((f) * n + ((f) < 4 ? (k) : (j))) * n + ((f) < 2 ? (j) : (i))]
-__device__ __forceinline__ double bnd_ghost_delta(int n, const double *g, int ci, int cj, int ck) {
-  const int q[3] = { ci, cj, ck };
-  int out[3], P[3], step[3], face[3], a, m = 0;
-  for (a = 0; a < 3; a++) {
-    out[a] = q[a] < 0 || q[a] >= n;
-    P[a] = q[a] < 0 ? 0 : q[a] >= n ? n - 1 : q[a];
-    step[a] = q[a] < 0 ? 1 : -1;                               // one cell inward
-    face[a] = 2 * a + (q[a] >= n);
-    m += out[a];
-  }
-  if (m == 1) { a = out[0] ? 0 : out[1] ? 1 : 2; return 2.0 * BND_AT(face[a], P[0], P[1], P[2]); }
-  if (n < 2) return m == 3 ? ((BND_AT(face[0], P[0], P[1], P[2]) + BND_AT(face[1], P[0], P[1], P[2])) + BND_AT(face[2], P[0], P[1], P[2])) * (2.0 / 3.0) : 0.0;
-  if (m == 2) {                      // the outside axes x < y
-    const int x = out[0] ? 0 : 1, y = out[2] ? 2 : 1;
-    const int yi = P[0] + (y == 0) * step[0], yj = P[1] + (y == 1) * step[1], yk = P[2] + (y == 2) * step[2];
-    const int xi = P[0] + (x == 0) * step[0], xj = P[1] + (x == 1) * step[1], xk = P[2] + (x == 2) * step[2];
-    return (BND_AT(face[x], P[0], P[1], P[2]) - BND_AT(face[x], yi, yj, yk)) + (BND_AT(face[y], P[0], P[1], P[2]) - BND_AT(face[y], xi, xj, xk));
-  }
-  double c[3];                       // corner: each wall's extrapolation
-  for (a = 0; a < 3; a++) {
-    const int b = a == 0 ? 1 : 0, d = a == 2 ? 1 : 2;          // the wall's in-face axes, b < d
-    const double g00 = BND_AT(face[a], P[0], P[1], P[2]);
-    const double g10 = BND_AT(face[a], P[0] + (b == 0) * step[0], P[1] + (b == 1) * step[1], P[2]);
-    const double g01 = BND_AT(face[a], P[0], P[1] + (d == 1) * step[1], P[2] + (d == 2) * step[2]);
-    c[a] = (2.0 * g00 - 0.5 * g10) - 0.5 * g01;
-  }
-  return ((c[0] + c[1]) + c[2]) * (2.0 / 3.0);
-}
-#undef BND_AT
-
+// every ghost lies between Dirichlet walls: bnd_ghost_delta, which bnd_ghost_faces gives under mask 0 too
 __global__ __launch_bounds__(kBndThreads) void boundary_interp_kernel(const hpgmg_hip_level L, int id, const double *__restrict__ gc, int nc) {
   const int positions = 6 * L.dim * L.dim;
-  const double wt[8] = { 0.421875, 0.140625, 0.140625, 0.046875, 0.140625, 0.046875, 0.046875, 0.015625 };
   for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
     const int li = L.box_low[3 * box], lj = L.box_low[3 * box + 1], lk = L.box_low[3 * box + 2];
     double *v = vec_origin(L, box, id);
@@ -191,13 +144,11 @@ __global__ __launch_bounds__(kBndThreads) void boundary_interp_kernel(const hpgm
       const FacePos P = bnd_face_pos(L, li, lj, lk, t);
       if (!P.on) continue;
       const int gi = li + P.i, gj = lj + P.j, gk = lk + P.k;
-      const int ci = gi >> 1, cj = gj >> 1, ck = gk >> 1, di = (gi & 1) ? 1 : -1, dj = (gj & 1) ? 1 : -1, dk = (gk & 1) ? 1 : -1;
-      double D = 0.0;
+      const bnd_p1_cell F = bnd_p1_of(gi, gj, gk);
+      double D = 0.0, w;
+      int q[3];
 #pragma unroll
-      for (int s = 1; s < 8; s++) {       // interpolation_p1's reads after the centre: dk, dj, dj+dk, di, di+dk, di+dj, di+dj+dk
-        const int qi = ci + ((s >> 2) & 1) * di, qj = cj + ((s >> 1) & 1) * dj, qk = ck + (s & 1) * dk;
-        if (qi < 0 || qi >= nc || qj < 0 || qj >= nc || qk < 0 || qk >= nc) D = D + wt[s] * bnd_ghost_delta(nc, gc, qi, qj, qk);
-      }
+      for (int s = 1; s < 8; s++) if (bnd_p1_ghost(nc, F, s, q, &w)) D = D + w * bnd_ghost_delta(nc, gc, q[0], q[1], q[2]);
       const int c = P.i + P.j * L.jStride + P.k * L.kStride;
       v[c] = v[c] + D;
     }
@@ -217,36 +168,10 @@ __device__ __forceinline__ double bnd_coarse_cell(const hpgmg_hip_level &Lc, int
   return vec_origin(Lc, box, id)[(i - li) + (j - lj) * Lc.jStride + (k - lk) * Lc.kStride];
 }
 
-// host/driver.c bnd_ghost_delta_faces, expression for expression
-#define BND_AT(f, i, j, k) g[((f) * n + ((f) < 4 ? (k) : (j))) * n + ((f) < 2 ? (j) : (i))]
-__device__ __forceinline__ double bnd_ghost_delta_faces(const hpgmg_hip_level &Lc, int id, int nb, const double *g, double hc, int mask,
-                                                        int ci, int cj, int ck) {
-  const int n = Lc.dim_i;
-  const int q[3] = { ci, cj, ck };
-  int out[3], P[3], face[3], a, m = 0, dirichlet = 0;
-  for (a = 0; a < 3; a++) {
-    out[a] = q[a] < 0 || q[a] >= n;
-    P[a] = q[a] < 0 ? 0 : q[a] >= n ? n - 1 : q[a];
-    face[a] = 2 * a + (q[a] >= n);
-    m += out[a];
-    dirichlet += out[a] && !((mask >> face[a]) & 1);
-  }
-  if (dirichlet == m) return bnd_ghost_delta(n, g, ci, cj, ck);
-  double s = 0.0;
-  for (a = 0; a < 3; a++) if (out[a]) {
-    const double ga = BND_AT(face[a], P[0], P[1], P[2]);
-    s = s + (((mask >> face[a]) & 1) ? hc * ga : 2.0 * ga);
-  }
-  const double c = (double)(1 - 2 * dirichlet + ((m & 1) ? 1 : -1));
-  return c * bnd_coarse_cell(Lc, id, nb, P[0], P[1], P[2]) + s;
-}
-#undef BND_AT
-
 // boundary_interp_kernel with per-face kinds: Lc, nb locate the coarse iterate (vector id of the coarse level), hc is the coarse h
 __global__ __launch_bounds__(kBndThreads) void boundary_interp_faces_kernel(const hpgmg_hip_level L, int id, const hpgmg_hip_level Lc, int nb,
                                                                             const double *__restrict__ gc, double hc, int mask) {
   const int positions = 6 * L.dim * L.dim, nc = Lc.dim_i;
-  const double wt[8] = { 0.421875, 0.140625, 0.140625, 0.046875, 0.140625, 0.046875, 0.046875, 0.015625 };
   for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
     const int li = L.box_low[3 * box], lj = L.box_low[3 * box + 1], lk = L.box_low[3 * box + 2];
     double *v = vec_origin(L, box, id);
@@ -254,12 +179,13 @@ __global__ __launch_bounds__(kBndThreads) void boundary_interp_faces_kernel(cons
       const FacePos P = bnd_face_pos(L, li, lj, lk, t);
       if (!P.on) continue;
       const int gi = li + P.i, gj = lj + P.j, gk = lk + P.k;
-      const int ci = gi >> 1, cj = gj >> 1, ck = gk >> 1, di = (gi & 1) ? 1 : -1, dj = (gj & 1) ? 1 : -1, dk = (gk & 1) ? 1 : -1;
-      double D = 0.0;
+      const bnd_p1_cell F = bnd_p1_of(gi, gj, gk);
+      double D = 0.0, w;
+      int q[3];
 #pragma unroll
-      for (int s = 1; s < 8; s++) {       // interpolation_p1's reads after the centre
-        const int qi = ci + ((s >> 2) & 1) * di, qj = cj + ((s >> 1) & 1) * dj, qk = ck + (s & 1) * dk;
-        if (qi < 0 || qi >= nc || qj < 0 || qj >= nc || qk < 0 || qk >= nc) D = D + wt[s] * bnd_ghost_delta_faces(Lc, id, nb, gc, hc, mask, qi, qj, qk);
+      for (int s = 1; s < 8; s++) if (bnd_p1_ghost(nc, F, s, q, &w)) {
+        const bnd_ghost G = bnd_ghost_faces(nc, gc, hc, mask, q[0], q[1], q[2]);
+        D = D + w * (G.needs_u ? G.c * bnd_coarse_cell(Lc, id, nb, G.P[0], G.P[1], G.P[2]) + G.s : G.s);
       }
       const int c = P.i + P.j * L.jStride + P.k * L.kStride;
       v[c] = v[c] + D;
@@ -272,6 +198,18 @@ static dim3 bnd_grid(int per_box, int boxes) {       // x: the positions of one 
   return dim3(blocks < 16384 ? (blocks > 0 ? blocks : 1) : 16384, boxes < 65535 ? boxes : 65535);
 }
 static int bnd_cube(const hpgmg_hip_level *L) { return L->dim_i == L->dim_j && L->dim_i == L->dim_k && L->periodic == 0; }
+// around a kernel that ORs validation bits into g_bnd_flag: clear the word; after the launch, copy the bits to *status and wait for them
+static int bnd_flag_begin() {
+  if (!g_bnd_flag) HPGMG_CHECK(hipMalloc((void **)&g_bnd_flag, sizeof(int)));
+  HPGMG_CHECK(hipMemsetAsync(g_bnd_flag, 0, sizeof(int), g_stream));
+  return 0;
+}
+static int bnd_flag_end(const char *name, int *status) {
+  HPGMG_LAUNCH_CHECK(name);
+  HPGMG_CHECK(hipMemcpyAsync(status, g_bnd_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
+  HPGMG_CHECK(hipStreamSynchronize(g_stream));
+  return 0;
+}
 
 }  // namespace hpgmg
 
@@ -297,13 +235,9 @@ int hpgmg_hip_dense_pack_lifted_faces(const hpgmg_hip_level *L, int id, const do
   if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "dense_pack_lifted: the level is not a Dirichlet cube");
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
-  if (!g_bnd_flag) HPGMG_CHECK(hipMalloc((void **)&g_bnd_flag, sizeof(int)));
-  HPGMG_CHECK(hipMemsetAsync(g_bnd_flag, 0, sizeof(int), g_stream));
+  if (int e = bnd_flag_begin()) return e;
   hipLaunchKernelGGL(dense_pack_lifted_kernel, bnd_grid(L->volume, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, src, g, w, mask, wall, wn, g_bnd_flag);
-  HPGMG_LAUNCH_CHECK("dense_pack_lifted_kernel");
-  HPGMG_CHECK(hipMemcpyAsync(status, g_bnd_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-  HPGMG_CHECK(hipStreamSynchronize(g_stream));
-  return 0;
+  return bnd_flag_end("dense_pack_lifted_kernel", status);
 }
 
 int hpgmg_hip_boundary_flux_faces(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn, int *status) {
@@ -312,13 +246,9 @@ int hpgmg_hip_boundary_flux_faces(const hpgmg_hip_level *L, double *phi, const d
   if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "boundary_flux: the level is not a Dirichlet cube");
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
-  if (!g_bnd_flag) HPGMG_CHECK(hipMalloc((void **)&g_bnd_flag, sizeof(int)));
-  HPGMG_CHECK(hipMemsetAsync(g_bnd_flag, 0, sizeof(int), g_stream));
+  if (int e = bnd_flag_begin()) return e;
   hipLaunchKernelGGL(boundary_flux_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, phi, g, w, mask, wall, wn, g_bnd_flag);
-  HPGMG_LAUNCH_CHECK("boundary_flux_kernel");
-  HPGMG_CHECK(hipMemcpyAsync(status, g_bnd_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-  HPGMG_CHECK(hipStreamSynchronize(g_stream));
-  return 0;
+  return bnd_flag_end("boundary_flux_kernel", status);
 }
 
 int hpgmg_hip_boundary_restrict(double *g_c, const double *g_f, int n_c) {

@@ -1,0 +1,132 @@
+/*
+ * hpgmg_boundary_math.h -- INTERNAL: the arithmetic of the dense-array boundary hooks (include/hpgmg_operators.h hpgmg_dense_*, hpgmg_boundary_*;
+ * DESIGN.md §11.1, §11.2), written once for the host defaults (host/hooks_host.inc), the HIP plugin (host/plugin_dense.c) and its kernels
+ * (kernels/dense_boundary.hip).  Not part of the C ABI: it declares nothing extern and no caller of the library includes it.
+ *
+ * The GPU tests hold the HIP build to the host defaults bit for bit, and every build has -ffp-contract=off, so the written order of each
+ * floating-point expression here IS the contract: change one and both sides change together.  Whatever reads a vector of the level (the coarse
+ * iterate, a beta) stays with the caller, which knows where that lives.
+ *
+ * Compiles as gnu99 C and as HIP C++.  Indices into a boundary array are int on both sides: 24 n^2 (the finer array under a lift) stays below
+ * 2^31 up to n = 9459 cells per side, where one vector of the level would hold 6.7 TB.
+ */
+#ifndef HPGMG_BOUNDARY_MATH_H
+#define HPGMG_BOUNDARY_MATH_H
+
+#ifdef __HIPCC__
+#define HPGMG_BND_FN __host__ __device__ __forceinline__
+#else
+#define HPGMG_BND_FN static inline
+#endif
+
+/* extent along one axis of a dense array of a level with n cells there; high_face: it is a face array of that axis on a Dirichlet level, which
+ * holds the high domain face too */
+HPGMG_BND_FN int dense_extent(int n, int high_face) { return n + (high_face != 0); }
+
+/* A boundary array is 6 x n x n doubles (n cells per side, a cube): [0], [1] i-low / i-high indexed [k][j], [2], [3] j-low / j-high [k][i],
+ * [4], [5] k-low / k-high [j][i]. */
+HPGMG_BND_FN int bnd_touches(int n, int face, int gi, int gj, int gk) {          /* cell (gi,gj,gk) lies on domain face `face` */
+  const int c = face < 2 ? gi : face < 4 ? gj : gk;
+  return (face & 1) ? c == n - 1 : c == 0;
+}
+HPGMG_BND_FN int bnd_entry(int n, int face, int gi, int gj, int gk) {            /* its entry in the boundary array */
+  const int q = face < 4 ? gk : gj, p = face < 2 ? gj : gi;
+  return (face * n + q) * n + p;
+}
+/* BND_AT(face, i, j, k): the entry of `face` at the in-range cell (i, j, k) (its own axis not read) of the array g of an n-cube in scope */
+#define BND_AT(f, i, j, k) g[((f) * n + ((f) < 4 ? (k) : (j))) * n + ((f) < 2 ? (j) : (i))]
+
+/* a Dirichlet face's entry of the lift is (w * beta) * g, a Neumann wall's (wn * wall beta) * gn (b the operator's b, h the level's h) */
+HPGMG_BND_FN double bnd_weight(double b, double h) { return (2.0 * b) * (1.0 / (h * h)); }
+HPGMG_BND_FN double bnd_weight_neumann(double b, double h) { return b * (1.0 / h); }
+
+/* S(c) of hpgmg_boundary_lift: the four finer entries under each face entry of coarse cell (gi,gj,gk) of an n-cube, faces in order */
+HPGMG_BND_FN double bnd_fine_sum(int n, const double *phi_f, int gi, int gj, int gk) {
+  const int nf = 2 * n;
+  double S = 0.0;
+  int face;
+  for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
+    const int q = face < 4 ? gk : gj, p = face < 2 ? gj : gi;
+    const double *e = phi_f + (face * nf + 2 * q) * nf + 2 * p;
+    S = S + (((e[0] + e[1]) + e[nf]) + e[nf + 1]);
+  }
+  return S;
+}
+
+/* delta of the ghost at coarse (ci,cj,ck) between Dirichlet walls (hpgmg_boundary_interp): 2 g on a face, the wall-by-wall
+ * linear rule on an edge or corner (exact for u linear near them) */
+HPGMG_BND_FN double bnd_ghost_delta(int n, const double *g, int ci, int cj, int ck) {
+  const int q[3] = { ci, cj, ck };
+  int out[3], P[3], step[3], face[3], a, m = 0;
+  for (a = 0; a < 3; a++) {
+    out[a] = q[a] < 0 || q[a] >= n;
+    P[a] = q[a] < 0 ? 0 : q[a] >= n ? n - 1 : q[a];
+    step[a] = q[a] < 0 ? 1 : -1;                               /* one cell inward */
+    face[a] = 2 * a + (q[a] >= n);
+    m += out[a];
+  }
+  if (m == 1) { a = out[0] ? 0 : out[1] ? 1 : 2; return 2.0 * BND_AT(face[a], P[0], P[1], P[2]); }
+  if (n < 2) return m == 3 ? ((BND_AT(face[0], P[0], P[1], P[2]) + BND_AT(face[1], P[0], P[1], P[2])) + BND_AT(face[2], P[0], P[1], P[2])) * (2.0 / 3.0) : 0.0;
+  if (m == 2) {                      /* the outside axes x < y: each wall's entry next to the edge minus the one a cell further along the other wall */
+    const int x = out[0] ? 0 : 1, y = out[2] ? 2 : 1;
+    const int yi = P[0] + (y == 0) * step[0], yj = P[1] + (y == 1) * step[1], yk = P[2] + (y == 2) * step[2];
+    const int xi = P[0] + (x == 0) * step[0], xj = P[1] + (x == 1) * step[1], xk = P[2] + (x == 2) * step[2];
+    return (BND_AT(face[x], P[0], P[1], P[2]) - BND_AT(face[x], yi, yj, yk)) + (BND_AT(face[y], P[0], P[1], P[2]) - BND_AT(face[y], xi, xj, xk));
+  }
+  double c[3];                       /* corner: each wall's linear extrapolation to the corner point */
+  for (a = 0; a < 3; a++) {
+    const int b = a == 0 ? 1 : 0, d = a == 2 ? 1 : 2;          /* the wall's in-face axes, b < d */
+    const double g00 = BND_AT(face[a], P[0], P[1], P[2]);
+    const double g10 = BND_AT(face[a], P[0] + (b == 0) * step[0], P[1] + (b == 1) * step[1], P[2]);
+    const double g01 = BND_AT(face[a], P[0], P[1] + (d == 1) * step[1], P[2] + (d == 2) * step[2]);
+    c[a] = (2.0 * g00 - 0.5 * g10) - 0.5 * g01;
+  }
+  return ((c[0] + c[1]) + c[2]) * (2.0 / 3.0);
+}
+
+/* The same ghost with per-face kinds (hpgmg_boundary_interp_faces; bit f of mask: face f is a Neumann wall, hc the coarse h).
+ * Its delta is  needs_u ? c * u + s : s  with u the coarse iterate at the in-range cell P, which the caller reads.  Between Dirichlet walls
+ * alone (any ghost under mask 0) needs_u is 0 and s is bnd_ghost_delta: no 0 * u + s, which would turn an s of -0.0 into +0.0. */
+typedef struct { int needs_u, P[3]; double c, s; } bnd_ghost;
+HPGMG_BND_FN bnd_ghost bnd_ghost_faces(int n, const double *g, double hc, int mask, int ci, int cj, int ck) {
+  const int q[3] = { ci, cj, ck };
+  int out[3], face[3], a, m = 0, dirichlet = 0;
+  bnd_ghost G;
+  for (a = 0; a < 3; a++) {
+    out[a] = q[a] < 0 || q[a] >= n;
+    G.P[a] = q[a] < 0 ? 0 : q[a] >= n ? n - 1 : q[a];
+    face[a] = 2 * a + (q[a] >= n);
+    m += out[a];
+    dirichlet += out[a] && !((mask >> face[a]) & 1);
+  }
+  G.needs_u = dirichlet != m;
+  G.c = 0.0;
+  if (!G.needs_u) { G.s = bnd_ghost_delta(n, g, ci, cj, ck); return G; }
+  double s = 0.0;
+  for (a = 0; a < 3; a++) if (out[a]) {
+    const double ga = BND_AT(face[a], G.P[0], G.P[1], G.P[2]);
+    s = s + (((mask >> face[a]) & 1) ? hc * ga : 2.0 * ga);
+  }
+  G.c = (double)(1 - 2 * dirichlet + ((m & 1) ? 1 : -1));
+  G.s = s;
+  return G;
+}
+#undef BND_AT
+
+/* D(c) of hpgmg_boundary_interp / _interp_faces for a fine cell is the sum over t = 1 .. 7, in this order, of w * delta for the reads of
+ * interpolation_p1 after the centre (dk, dj, dj+dk, di, di+dk, di+dj, di+dj+dk) that are ghosts of the coarse nc-cube; delta is bnd_ghost_delta
+ * of the ghost between Dirichlet walls, bnd_ghost_faces' with per-face kinds.  bnd_p1_of: the fine cell's coarse cell c and the side d it leans
+ * to, once per cell.  bnd_p1_ghost: whether read t is a ghost, and then its coarse cell q and its p1 weight *w. */
+typedef struct { int c[3], d[3]; } bnd_p1_cell;
+HPGMG_BND_FN bnd_p1_cell bnd_p1_of(int gi, int gj, int gk) {
+  const bnd_p1_cell F = { { gi >> 1, gj >> 1, gk >> 1 }, { (gi & 1) ? 1 : -1, (gj & 1) ? 1 : -1, (gk & 1) ? 1 : -1 } };
+  return F;
+}
+HPGMG_BND_FN int bnd_p1_ghost(int nc, bnd_p1_cell F, int t, int q[3], double *w) {
+  const double wt[8] = { 0.421875, 0.140625, 0.140625, 0.046875, 0.140625, 0.046875, 0.046875, 0.015625 };
+  q[0] = F.c[0] + ((t >> 2) & 1) * F.d[0]; q[1] = F.c[1] + ((t >> 1) & 1) * F.d[1]; q[2] = F.c[2] + (t & 1) * F.d[2];
+  *w = wt[t];
+  return q[0] < 0 || q[0] >= nc || q[1] < 0 || q[1] >= nc || q[2] < 0 || q[2] >= nc;
+}
+
+#endif

@@ -125,7 +125,7 @@ void    hpgmg_vector_download(double *dst_host, const double *src_plugin, size_t
  * POSITIVE: v > 0, NONNEGATIVE: v >= 0) -- the vector is then written but not to be used -- or -1 for an argument the plugin refuses.
  * unpack: the interior cells of the vector into a (N,N,N) array; nothing else of the array is written.  where: HPGMG_WHERE_HOST = the array
  * is in host memory, HPGMG_WHERE_PLUGIN = in the plugin's memory (device memory in the HIP build; read and written in place).
- * host/driver.c holds weak host defaults (box by box through hpgmg_vector_upload / download: the CPU oracle); the HIP plugin overrides them
+ * host/hooks_host.inc holds weak host defaults (box by box through hpgmg_vector_upload / download: the CPU oracle); the HIP plugin overrides them
  * with one launch per array (kernels/dense_io.hip). */
 enum { HPGMG_DENSE_CELL = 0, HPGMG_DENSE_FACE_I = 1, HPGMG_DENSE_FACE_J = 2, HPGMG_DENSE_FACE_K = 3 };
 enum { HPGMG_DENSE_CHECK_FINITE = 0, HPGMG_DENSE_CHECK_POSITIVE = 1, HPGMG_DENSE_CHECK_NONNEGATIVE = 2 };
@@ -148,7 +148,7 @@ int     hpgmg_dense_unpack(level_type *level, int id, double *dst, int where);
  *   boundary_interp:   after interpolation_fcycle (p1) of coarse onto fine: every fine boundary cell adds D = 0.0 + weight * delta over its p1 reads
  *                      that land on a coarse ghost, in interpolation_p1's order; delta = the inhomogeneous minus the homogeneous ghost, from g_c
  *                      (the coarse level's boundary array): 2 g on a face, the linear rules of DESIGN.md §11.1 on an edge or corner.
- * g, g_c, g_f, phi, phi_fine live in the plugin's memory (hpgmg_vector_alloc).  host/driver.c holds weak host defaults (the CPU oracle); the HIP
+ * g, g_c, g_f, phi, phi_fine live in the plugin's memory (hpgmg_vector_alloc).  host/hooks_host.inc holds weak host defaults (the CPU oracle); the HIP
  * plugin overrides them (kernels/dense_boundary.hip), one launch each. */
 int     hpgmg_dense_pack_lifted(level_type *level, int id, const double *f, int where, const double *g, double b);
 int     hpgmg_boundary_flux(level_type *level, double *phi, const double *g, double b);
@@ -183,7 +183,7 @@ void    hpgmg_boundary_interp_faces(level_type *fine, int id, level_type *coarse
  * with W = 256 * ceil(dim^2 / 256) and S = ceil(dim / 16) the chains are the leaves V[c + W * (s + S * B)] (0.0 where c >= dim^2) of an array padded
  * with 0.0 to a power of two, folded for stride = 1, 2, 4, ...:  V[m] = V[m] + V[m + stride]  for every m that is a multiple of 2 * stride; V[0] is
  * the sum.  No chain of dependent additions is longer than 16 + log2(cells).  Return value: 1 = a fused kernel of the plugin ran, 0 = the portable
- * form did (host/driver.c: the operators, then the sums on the host from downloaded boxes -- the CPU oracle; a plugin falls back to it on a level
+ * form did (host/hooks_host.inc: the operators, then the sums on the host from downloaded boxes -- the CPU oracle; a plugin falls back to it on a level
  * its kernels do not take).  Same bits either way. */
 #define HPGMG_PCG_SEGMENT 16
 #define HPGMG_PCG_COLUMNS 256
