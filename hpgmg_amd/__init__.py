@@ -52,7 +52,7 @@ WHERE_HOST, WHERE_PLUGIN = 0, 1
 (USER_OK, USER_BAD_ARGUMENT, USER_CONFLICT, USER_MULTI_RANK, USER_NOT_FINITE, USER_OUT_OF_RANGE,
  USER_NOT_READY, USER_UNSUPPORTED) = 0, -1, -2, -3, -4, -5, -6, -7
 USER_FMG, USER_MG, USER_PCG, USER_FPCG = 0, 1, 2, 3
-FACE_DIRICHLET, FACE_NEUMANN = 0, 1
+FACE_DIRICHLET, FACE_NEUMANN, FACE_ROBIN = 0, 1, 3
 
 
 class HipLevel(ctypes.Structure):
@@ -90,6 +90,7 @@ def _declare_driver_api(lib):
         "hpgmg_set_timer_mode": (None, [c_int]),
         "hpgmg_get_timer_mode": (c_int, []),
         "hpgmg_level_eigenvalue": (c_dbl, [vp]),
+        "hpgmg_level_must_subtract_mean": (c_int, [vp]),
         "hpgmg_level_set_eigenvalue": (None, [vp, c_dbl]),
         "hpgmg_level_box_low": (None, [vp, c_int, P(c_int)]),
         "hpgmg_level_list_counts": (c_int, [vp, c_int, c_int, P(c_int)]),
@@ -162,6 +163,13 @@ def _declare_driver_api(lib):
         "hpgmg_dense_pack_lifted_faces": (c_int, [vp, c_int, vp, c_int, vp, c_dbl, c_int, vp]),
         "hpgmg_boundary_flux_faces": (c_int, [vp, vp, vp, c_dbl, c_int, vp]),
         "hpgmg_boundary_interp_faces": (None, [vp, c_int, vp, vp, c_int]),
+        # Robin walls
+        "hpgmg_user_set_coefficients_robin": (c_int, [vp, vp, vp, vp, vp, vp, c_int]),
+        "hpgmg_boundary_check_kappa": (c_int, [vp, vp, c_int, c_int, P(c_int)]),
+        "hpgmg_boundary_store_walls": (None, [vp, vp, vp, c_int]),
+        "hpgmg_dense_pack_lifted_robin": (c_int, [vp, c_int, vp, c_int, vp, c_dbl, c_int, vp, vp]),
+        "hpgmg_boundary_flux_robin": (c_int, [vp, vp, vp, c_dbl, c_int, vp, vp]),
+        "hpgmg_boundary_interp_robin": (None, [vp, c_int, vp, vp, c_int, vp]),
         # the fine-level passes of method="pcg" 
         "hpgmg_pcg_apply_dot": (c_int, [vp, c_int, c_int, c_dbl, c_dbl, P(c_dbl)]),
         "hpgmg_pcg_update": (c_int, [vp, c_int, c_int, c_int, c_int, c_dbl, P(c_dbl)]),

@@ -95,14 +95,15 @@ static double *bnd_download(const double *src, size_t n) {
   return h;
 }
 
-/* mask, wall: hpgmg_dense_pack_lifted_faces (0, NULL: hpgmg_dense_pack_lifted) */
-static int dense_pack_lifted_host(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
+/* mask, wall: hpgmg_dense_pack_lifted_faces (0, NULL: hpgmg_dense_pack_lifted); kappa: hpgmg_dense_pack_lifted_robin (NULL: the masked walls are Neumann) */
+static int dense_pack_lifted_host(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall, const double *kappa) {
   if (!g || L->boundary_condition.type != BC_DIRICHLET) return -1;
   const int st = hpgmg_dense_pack(L, id, f, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE);
   if (st < 0) return st;
   const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
   const double w = bnd_weight(b, L->h), wn = bnd_weight_neumann(b, L->h);
   double *gh = bnd_download(g, (size_t)6 * n * n), *wh = mask ? bnd_download(wall, (size_t)6 * n * n) : NULL;
+  double *kh = mask && kappa ? bnd_download(kappa, (size_t)6 * n * n) : NULL;
   double *v = (double *)malloc((size_t)L->box_volume * 4 * sizeof(double));
   double *bi = v + L->box_volume, *bj = bi + L->box_volume, *bk = bj + L->box_volume;
   int box, i, j, k, face, bad = 0;
@@ -118,9 +119,10 @@ static int dense_pack_lifted_host(level_type *L, int id, const double *f, int wh
       double T = 0.0;
       int on = 0;
       for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
-        const double gv = gh[bnd_entry(n, face, gi, gj, gk)];
+        const int e = bnd_entry(n, face, gi, gj, gk);
+        const double gv = gh[e];
         if (!isfinite(gv)) bad = 1;
-        if ((mask >> face) & 1) T = T + (wn * wh[bnd_entry(n, face, gi, gj, gk)]) * gv;
+        if ((mask >> face) & 1) T = T + (kh ? bnd_wall_phi(wn, wh[e], gv, kh[e], L->h) : (wn * wh[e]) * gv);
         else T = T + (w * bnd_beta(bi, bj, bk, face, ijk, jS, kS)) * gv;
         on = 1;
       }
@@ -128,22 +130,28 @@ static int dense_pack_lifted_host(level_type *L, int id, const double *f, int wh
     }
     hpgmg_vector_upload(B->vectors[id], v, (size_t)L->box_volume);
   }
-  free(v); free(gh); free(wh);
+  free(v); free(gh); free(wh); free(kh);
   return st | (bad ? HPGMG_DENSE_NOT_FINITE : 0);
 }
 __attribute__((weak)) int hpgmg_dense_pack_lifted(level_type *L, int id, const double *f, int where, const double *g, double b) {
-  return dense_pack_lifted_host(L, id, f, where, g, b, 0, NULL);
+  return dense_pack_lifted_host(L, id, f, where, g, b, 0, NULL, NULL);
 }
 __attribute__((weak)) int hpgmg_dense_pack_lifted_faces(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
   if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
-  return dense_pack_lifted_host(L, id, f, where, g, b, mask, wall);
+  return dense_pack_lifted_host(L, id, f, where, g, b, mask, wall, NULL);
+}
+__attribute__((weak)) int hpgmg_dense_pack_lifted_robin(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall,
+                                                        const double *kappa) {
+  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
+  return dense_pack_lifted_host(L, id, f, where, g, b, mask, wall, kappa);
 }
 
-static int boundary_flux_host(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
+static int boundary_flux_host(level_type *L, double *phi, const double *g, double b, int mask, const double *wall, const double *kappa) {
   const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
   const size_t len = (size_t)6 * n * n;
   const double w = bnd_weight(b, L->h), wn = bnd_weight_neumann(b, L->h);
   double *gh = bnd_download(g, len), *ph = (double *)calloc(len, sizeof(double)), *wh = mask ? bnd_download(wall, len) : NULL;
+  double *kh = mask && kappa ? bnd_download(kappa, len) : NULL;
   double *bi = (double *)malloc((size_t)L->box_volume * 3 * sizeof(double)), *bj = bi + L->box_volume, *bk = bj + L->box_volume;
   int box, i, j, k, face, bad = 0;
   size_t e;
@@ -158,19 +166,64 @@ static int boundary_flux_host(level_type *L, double *phi, const double *g, doubl
       const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
       for (face = 0; face < 6; face++) if (bnd_touches(n, face, gi, gj, gk)) {
         e = bnd_entry(n, face, gi, gj, gk);
-        if ((mask >> face) & 1) ph[e] = (wn * wh[e]) * gh[e];
+        if ((mask >> face) & 1) ph[e] = kh ? bnd_wall_phi(wn, wh[e], gh[e], kh[e], L->h) : (wn * wh[e]) * gh[e];
         else ph[e] = (w * bnd_beta(bi, bj, bk, face, ijk, jS, kS)) * gh[e];
       }
     }
   }
   hpgmg_vector_upload(phi, ph, len);
-  free(bi); free(ph); free(gh); free(wh);
+  free(bi); free(ph); free(gh); free(wh); free(kh);
   return bad ? HPGMG_DENSE_NOT_FINITE : 0;
 }
-__attribute__((weak)) int hpgmg_boundary_flux(level_type *L, double *phi, const double *g, double b) { return boundary_flux_host(L, phi, g, b, 0, NULL); }
+__attribute__((weak)) int hpgmg_boundary_flux(level_type *L, double *phi, const double *g, double b) { return boundary_flux_host(L, phi, g, b, 0, NULL, NULL); }
 __attribute__((weak)) int hpgmg_boundary_flux_faces(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
   if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
-  return boundary_flux_host(L, phi, g, b, mask, wall);
+  return boundary_flux_host(L, phi, g, b, mask, wall, NULL);
+}
+__attribute__((weak)) int hpgmg_boundary_flux_robin(level_type *L, double *phi, const double *g, double b, int mask, const double *wall, const double *kappa) {
+  if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
+  return boundary_flux_host(L, phi, g, b, mask, wall, kappa);
+}
+
+/* Robin walls (DESIGN.md §11.5) */
+__attribute__((weak)) int hpgmg_boundary_check_kappa(level_type *L, const double *kappa, int where, int robin_mask, int *any_positive) {
+  const int n = L->dim.i, len = 6 * n * n;
+  int e, bits = 0;
+  if (any_positive) *any_positive = 0;
+  if (!kappa || robin_mask < 0 || robin_mask > 63 || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return -1;
+  double *kh = where == HPGMG_WHERE_PLUGIN ? bnd_download(kappa, (size_t)len) : NULL;
+  for (e = 0; e < len; e++) bits |= bnd_kappa_bits(n, robin_mask, e, kh ? kh[e] : kappa[e]);
+  free(kh);
+  if (any_positive) *any_positive = (bits & BND_KAPPA_POSITIVE) != 0;
+  return bits & (HPGMG_DENSE_NOT_FINITE | HPGMG_DENSE_OUT_OF_RANGE);
+}
+__attribute__((weak)) void hpgmg_boundary_store_walls(level_type *L, const double *wall, const double *kappa, int mask) {
+  const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t len = (size_t)6 * n * n, vol = (size_t)L->box_volume;
+  if (!mask || !wall) return;
+  double *wh = bnd_download(wall, len), *kh = kappa ? bnd_download(kappa, len) : NULL;
+  double *beta[3];
+  int box, face, q, p;
+  beta[0] = (double *)malloc(vol * 3 * sizeof(double)); beta[1] = beta[0] + vol; beta[2] = beta[1] + vol;
+  for (box = 0; box < L->num_my_boxes; box++) {
+    const box_type *B = &L->my_boxes[box];
+    if (!bnd_box_on_domain_face(L, B)) continue;
+    hpgmg_vector_download(beta[0], B->vectors[VECTOR_BETA_I], vol);
+    hpgmg_vector_download(beta[1], B->vectors[VECTOR_BETA_J], vol);
+    hpgmg_vector_download(beta[2], B->vectors[VECTOR_BETA_K], vol);
+    for (face = 0; face < 6; face++) if ((mask >> face) & 1) for (q = 0; q < dim; q++) for (p = 0; p < dim; p++) {
+      const int side = (face & 1) ? dim - 1 : 0;
+      const int i = face < 2 ? side : p, j = face < 2 ? p : face < 4 ? side : q, k = face < 4 ? q : side;
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k;
+      if (!bnd_touches(n, face, gi, gj, gk)) continue;
+      const int e = bnd_entry(n, face, gi, gj, gk), step = !(face & 1) ? 0 : face == 1 ? 1 : face == 3 ? jS : kS;
+      beta[face >> 1][(i + g0) + (j + g0) * jS + (k + g0) * kS + step] = bnd_wall_beta(wh[e], kh ? kh[e] : 0.0, L->h);
+    }
+    hpgmg_vector_upload(B->vectors[VECTOR_BETA_I], beta[0], vol);
+    hpgmg_vector_upload(B->vectors[VECTOR_BETA_J], beta[1], vol);
+    hpgmg_vector_upload(B->vectors[VECTOR_BETA_K], beta[2], vol);
+  }
+  free(beta[0]); free(wh); free(kh);
 }
 
 __attribute__((weak)) void hpgmg_boundary_restrict(level_type *Lc, double *g_c, level_type *Lf, const double *g_f) {
@@ -208,24 +261,25 @@ __attribute__((weak)) void hpgmg_boundary_lift(level_type *L, int id, const doub
   free(v); free(pf); free(ph);
 }
 
-/* D(c) of hpgmg_boundary_interp / _interp_faces for fine cell (gi,gj,gk): u the coarse iterate as a dense (nc,nc,nc) array (read only next to
- * a Neumann wall: NULL with mask 0), hc the coarse h */
-static double bnd_interp_delta(int nc, const double *g, const double *u, double hc, int mask, int gi, int gj, int gk) {
+/* D(c) of hpgmg_boundary_interp / _interp_faces / _interp_robin for fine cell (gi,gj,gk): u the coarse iterate as a dense (nc,nc,nc) array (read
+ * only next to a masked wall: NULL with mask 0), hc the coarse h, kappa the coarse kappa array (NULL: the masked walls are Neumann) */
+static double bnd_interp_delta(int nc, const double *g, const double *u, double hc, int mask, const double *kappa, int gi, int gj, int gk) {
   const bnd_p1_cell F = bnd_p1_of(gi, gj, gk);
   double D = 0.0, w;
   int t, q[3];
   for (t = 1; t < 8; t++) if (bnd_p1_ghost(nc, F, t, q, &w)) {
-    const bnd_ghost G = bnd_ghost_faces(nc, g, hc, mask, q[0], q[1], q[2]);
+    const bnd_ghost G = bnd_ghost_faces(nc, g, hc, mask, kappa, q[0], q[1], q[2]);
     D = D + w * (G.needs_u ? G.c * u[((size_t)G.P[2] * nc + G.P[1]) * nc + G.P[0]] + G.s : G.s);
   }
   return D;
 }
 
 /* mask: hpgmg_boundary_interp_faces, which reads the coarse iterate next to a Neumann wall (0: hpgmg_boundary_interp) */
-static void boundary_interp_host(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) {
+static void boundary_interp_host(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask, const double *kappa_c) {
   const int n = Lf->dim.i, nc = Lc->dim.i, g0 = Lf->box_ghosts, dim = Lf->box_dim, jS = Lf->box_jStride, kS = Lf->box_kStride;
   double *gc = bnd_download(g_c, (size_t)6 * nc * nc), *v = (double *)malloc((size_t)Lf->box_volume * sizeof(double));
   double *uc = mask ? (double *)malloc((size_t)nc * nc * nc * sizeof(double)) : NULL;
+  double *kc = mask && kappa_c ? bnd_download(kappa_c, (size_t)6 * nc * nc) : NULL;
   int box, i, j, k;
   if (uc) hpgmg_dense_unpack(Lc, id, uc, HPGMG_WHERE_HOST);
   for (box = 0; box < Lf->num_my_boxes; box++) {
@@ -235,14 +289,17 @@ static void boundary_interp_host(level_type *Lf, int id, level_type *Lc, const d
     for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
       const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
       if (gi > 0 && gj > 0 && gk > 0 && gi < n - 1 && gj < n - 1 && gk < n - 1) continue;
-      v[ijk] = v[ijk] + bnd_interp_delta(nc, gc, uc, Lc->h, mask, gi, gj, gk);
+      v[ijk] = v[ijk] + bnd_interp_delta(nc, gc, uc, Lc->h, mask, kc, gi, gj, gk);
     }
     hpgmg_vector_upload(B->vectors[id], v, (size_t)Lf->box_volume);
   }
-  free(uc); free(v); free(gc);
+  free(uc); free(kc); free(v); free(gc);
 }
-__attribute__((weak)) void hpgmg_boundary_interp(level_type *Lf, int id, level_type *Lc, const double *g_c) { boundary_interp_host(Lf, id, Lc, g_c, 0); }
-__attribute__((weak)) void hpgmg_boundary_interp_faces(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) { boundary_interp_host(Lf, id, Lc, g_c, mask); }
+__attribute__((weak)) void hpgmg_boundary_interp(level_type *Lf, int id, level_type *Lc, const double *g_c) { boundary_interp_host(Lf, id, Lc, g_c, 0, NULL); }
+__attribute__((weak)) void hpgmg_boundary_interp_faces(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) { boundary_interp_host(Lf, id, Lc, g_c, mask, NULL); }
+__attribute__((weak)) void hpgmg_boundary_interp_robin(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask, const double *kappa_c) {
+  boundary_interp_host(Lf, id, Lc, g_c, mask, kappa_c);
+}
 
 /* ------------------------------------------------------------------ the CG passes: portable forms (include/hpgmg_operators.h; DESIGN.md §11.3)
  * The operators, then the sums on the host from downloaded boxes, in the one order the header defines.  The hooks are weak like the dense pair above:

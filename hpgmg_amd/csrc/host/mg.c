@@ -379,6 +379,24 @@ void MGRebuildCoarse(mg_type *G, double a, double b) {
   }
 }
 
+void MGRebuildCoarseWalls(mg_type *G, double a, double b, void (*store_walls)(void *ctx, mg_type *G, int l), void *ctx) {
+  int l;
+  for (l = 1; l < G->num_levels; l++) {
+    rebuild_operator(G->levels[l], G->levels[l - 1], a, b);
+    store_walls(ctx, G, l);
+    rebuild_operator(G->levels[l], NULL, a, b);
+  }
+  SAY(G->my_rank, "\n");
+
+  for (l = 0; l < G->num_levels; l++) {
+    level_type *L = G->levels[l];
+    int alpha_is_zero = 1;
+    L->must_subtract_mean = 0;
+    if (hpgmg_vectors_reserved() > VECTOR_ALPHA && L->active) alpha_is_zero = (dot(L, VECTOR_ALPHA, VECTOR_ALPHA) == 0.0);
+    if (L->boundary_condition.type == BC_PERIODIC && (a == 0 || alpha_is_zero)) L->must_subtract_mean = 1;
+  }
+}
+
 void MGDestroy(mg_type *G) {
   int l, t;
   SAY(G->my_rank, "attempting to free the restriction and interpolation lists... ");

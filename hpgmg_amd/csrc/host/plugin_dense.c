@@ -69,22 +69,30 @@ int hpgmg_dense_pack_walls(level_type *L, int id, const double *src, int where, 
   return status;
 }
 
-int hpgmg_dense_pack_lifted_faces(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
+int hpgmg_dense_pack_lifted_robin(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall, const double *kappa) {
   int status = 0;
   if (!g || L->boundary_condition.type != BC_DIRICHLET || mask < 0 || mask > 63 || (mask && !wall)) return -1;
   if (!(f = dense_source(L, id, f, where, (size_t)L->dim.i * L->dim.j * L->dim.k))) return -1;
-  HIP_OK(hpgmg_hip_dense_pack_lifted_faces(&hp_backend_of(L)->dev, id, f, g, bnd_weight(b, L->h), mask, wall, bnd_weight_neumann(b, L->h), &status));
+  HIP_OK(hpgmg_hip_dense_pack_lifted_robin(&hp_backend_of(L)->dev, id, f, g, bnd_weight(b, L->h), mask, wall, bnd_weight_neumann(b, L->h),
+                                           mask ? kappa : NULL, L->h, &status));
   return status;
+}
+int hpgmg_dense_pack_lifted_faces(level_type *L, int id, const double *f, int where, const double *g, double b, int mask, const double *wall) {
+  return hpgmg_dense_pack_lifted_robin(L, id, f, where, g, b, mask, wall, NULL);
 }
 int hpgmg_dense_pack_lifted(level_type *L, int id, const double *f, int where, const double *g, double b) {
   return hpgmg_dense_pack_lifted_faces(L, id, f, where, g, b, 0, NULL);
 }
 
-int hpgmg_boundary_flux_faces(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
+int hpgmg_boundary_flux_robin(level_type *L, double *phi, const double *g, double b, int mask, const double *wall, const double *kappa) {
   int status = 0;
   if (mask < 0 || mask > 63 || (mask && !wall)) return -1;
-  HIP_OK(hpgmg_hip_boundary_flux_faces(&hp_backend_of(L)->dev, phi, g, bnd_weight(b, L->h), mask, wall, bnd_weight_neumann(b, L->h), &status));
+  HIP_OK(hpgmg_hip_boundary_flux_robin(&hp_backend_of(L)->dev, phi, g, bnd_weight(b, L->h), mask, wall, bnd_weight_neumann(b, L->h), mask ? kappa : NULL, L->h,
+                                       &status));
   return status;
+}
+int hpgmg_boundary_flux_faces(level_type *L, double *phi, const double *g, double b, int mask, const double *wall) {
+  return hpgmg_boundary_flux_robin(L, phi, g, b, mask, wall, NULL);
 }
 int hpgmg_boundary_flux(level_type *L, double *phi, const double *g, double b) { return hpgmg_boundary_flux_faces(L, phi, g, b, 0, NULL); }
 
@@ -101,12 +109,30 @@ void hpgmg_boundary_interp(level_type *Lf, int id, level_type *Lc, const double 
   HIP_OK(hpgmg_hip_boundary_interp(&hp_backend_of(Lf)->dev, id, g_c, Lc->dim.i));
 }
 
-void hpgmg_boundary_interp_faces(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) {
+void hpgmg_boundary_interp_robin(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask, const double *kappa_c) {
   int nb = Lc->dim.i / Lc->box_dim, bx;          /* the kernel's box formula holds when the coarse boxes are in i-fastest order */
   if (Lc->num_my_boxes != nb * nb * nb) nb = 0;
   for (bx = 0; nb && bx < Lc->num_my_boxes; bx++) {
     const box_type *X = &Lc->my_boxes[bx];
     if (X->low.i != (bx % nb) * Lc->box_dim || X->low.j != ((bx / nb) % nb) * Lc->box_dim || X->low.k != (bx / (nb * nb)) * Lc->box_dim) nb = 0;
   }
-  HIP_OK(hpgmg_hip_boundary_interp_faces(&hp_backend_of(Lf)->dev, id, &hp_backend_of(Lc)->dev, nb, g_c, Lc->h, mask));
+  HIP_OK(hpgmg_hip_boundary_interp_robin(&hp_backend_of(Lf)->dev, id, &hp_backend_of(Lc)->dev, nb, g_c, Lc->h, mask, mask ? kappa_c : NULL));
+}
+void hpgmg_boundary_interp_faces(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) {
+  hpgmg_boundary_interp_robin(Lf, id, Lc, g_c, mask, NULL);
+}
+
+/* Robin walls: a host array of kappa is staged as hpgmg_dense_pack stages its array */
+int hpgmg_boundary_check_kappa(level_type *L, const double *kappa, int where, int robin_mask, int *any_positive) {
+  int status = 0;
+  if (any_positive) *any_positive = 0;
+  if (robin_mask < 0 || robin_mask > 63 || L->dim.i != L->dim.j || L->dim.i != L->dim.k) return -1;
+  if (!(kappa = dense_source(L, 0, kappa, where, (size_t)6 * L->dim.i * L->dim.i))) return -1;
+  HIP_OK(hpgmg_hip_boundary_check_kappa(kappa, L->dim.i, robin_mask, &status));
+  if (any_positive) *any_positive = (status & BND_KAPPA_POSITIVE) != 0;
+  return status & (HPGMG_DENSE_NOT_FINITE | HPGMG_DENSE_OUT_OF_RANGE);
+}
+void hpgmg_boundary_store_walls(level_type *L, const double *wall, const double *kappa, int mask) {
+  if (!mask || !wall) return;
+  HIP_OK(hpgmg_hip_boundary_store_walls(&hp_backend_of(L)->dev, wall, kappa, L->h, mask));
 }

@@ -19,8 +19,12 @@ struct hpgmg_user_solver {
   double **bnd_g, **bnd_phi;   /* per level: the boundary values g_l and their lift flux phi_l (plugin memory; allocated on first use) */
   double *app_g, *app_phi;     /* apply_dirichlet's g and phi on the finest level */
   int max_iter;                /* HPGMG_USER_PCG / _FPCG: the iteration limit (hpgmg_user_set_max_iterations; default 100) */
-  int mask;                    /* bit f: domain face f is a Neumann wall (hpgmg_user_create_faces; DESIGN.md §11.2); 0: every wall Dirichlet, or periodic */
-  double *wall0, **wall;       /* mask != 0: wall0 = wall[0]; per level, the wall beta of the Neumann faces (a boundary array; the level's own beta is 0 there) */
+  int mask;                    /* bit f: domain face f is a Neumann or Robin wall (hpgmg_user_create_faces; DESIGN.md §11.2, §11.5); 0: every wall Dirichlet, or periodic */
+  double *wall0, **wall;       /* mask != 0: wall0 = wall[0]; per level, the wall beta of the masked faces (a boundary array; the level's own beta is 0 there,
+                                  on a Robin wall wall * t / (2 + t)) */
+  int robin_mask;              /* bit f: face f is a Robin wall (a subset of mask) */
+  int kappa_positive;          /* some kappa of a Robin face is > 0: six masked walls are then not singular */
+  double **kappa;              /* robin_mask != 0: per level, kappa of the Robin walls (a boundary array, 0.0 on the other faces), allocated and freed with wall */
 };
 static int user_live = 0;              /* user solvers alive: the process-wide configuration belongs to them */
 static hpgmg_config user_cfg;
@@ -28,6 +32,7 @@ static hpgmg_config user_cfg;
 /* user calls print only when the solver's verbose flag is on (the library's default, hpgmg_verbose = 1, is the benchmark's) */
 #define USER_QUIET(us) const int verbose_saved_ = hpgmg_verbose; hpgmg_verbose = (us)->verbose
 #define USER_LOUD() hpgmg_verbose = verbose_saved_
+#define USER_KAPPA(us, l) ((us)->kappa ? (us)->kappa[l] : NULL)      /* level l's kappa array; NULL: no Robin wall, the _faces forms */
 
 static int user_config_ok(void) {                 /* nobody has reconfigured the process under the live user solvers */
   hpgmg_config cfg;
@@ -42,6 +47,7 @@ static int user_pack_status(int st) {
 }
 
 static void user_bnd_alloc(hpgmg_user_solver *us);
+static void user_bnd_take(hpgmg_user_solver *us, double *dst, const double *g, int where);
 /* a face array of the coefficients into the finest level: with Neumann walls through the masked pack, which keeps their beta in wall[0] */
 static int user_pack_beta(hpgmg_user_solver *us, int id, const double *src, int where, int layout) {
   level_type *L = &us->s.level_h;
@@ -50,12 +56,12 @@ static int user_pack_beta(hpgmg_user_solver *us, int id, const double *src, int 
 }
 /* after rebuild_operator + MGRebuildCoarse of a solver with Neumann walls: every level's wall beta, and the singular case.  Six Neumann walls
  * without an a * alpha term leave the constants in the null space, as periodic Poisson does: the same path (MGRebuildCoarse has just reset it) */
-static void user_walls_rebuilt(hpgmg_user_solver *us) {
+static void user_walls_rebuilt(hpgmg_user_solver *us, int restricted) {      /* restricted: MGRebuildCoarseWalls has made wall[l] already */
   mg_type *G = &us->s.mg;
   int l;
   if (!us->mask) return;
-  for (l = 1; l < G->num_levels; l++) hpgmg_boundary_restrict(G->levels[l], us->wall[l], G->levels[l - 1], us->wall[l - 1]);
-  if (us->mask != 63) return;
+  if (!restricted) for (l = 1; l < G->num_levels; l++) hpgmg_boundary_restrict(G->levels[l], us->wall[l], G->levels[l - 1], us->wall[l - 1]);
+  if (us->mask != 63 || us->kappa_positive) return;
   for (l = 0; l < G->num_levels; l++) {
     level_type *L = G->levels[l];
     int alpha_is_zero = 1;
@@ -64,22 +70,32 @@ static void user_walls_rebuilt(hpgmg_user_solver *us) {
   }
 }
 
-static int user_create(int n, int box_dim, int bc, int mask, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out);
+/* MGRebuildCoarseWalls' callback of a solver with a Robin wall (DESIGN.md §11.5): level l's wall beta and kappa from level l - 1's, then the
+ * level's beta on the masked walls from them and its own h */
+static void user_store_walls(void *ctx, mg_type *G, int l) {
+  hpgmg_user_solver *us = (hpgmg_user_solver *)ctx;
+  hpgmg_boundary_restrict(G->levels[l], us->wall[l], G->levels[l - 1], us->wall[l - 1]);
+  hpgmg_boundary_restrict(G->levels[l], us->kappa[l], G->levels[l - 1], us->kappa[l - 1]);
+  hpgmg_boundary_store_walls(G->levels[l], us->wall[l], us->kappa[l], us->mask);
+}
+
+static int user_create(int n, int box_dim, int bc, int mask, int robin_mask, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out);
 int hpgmg_user_create(int n, int box_dim, int bc, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out) {
-  return user_create(n, box_dim, bc, 0, op, smoother, a, b, h, out);
+  return user_create(n, box_dim, bc, 0, 0, op, smoother, a, b, h, out);
 }
 int hpgmg_user_create_faces(int n, int box_dim, const int face_bc[6], int op, int smoother, double a, double b, double h, hpgmg_user_solver **out) {
-  int f, mask = 0;
+  int f, mask = 0, robin_mask = 0;
   if (out) *out = NULL;
   if (!face_bc) return HPGMG_USER_BAD_ARGUMENT;
   for (f = 0; f < 6; f++) {
-    if (face_bc[f] != HPGMG_FACE_DIRICHLET && face_bc[f] != HPGMG_FACE_NEUMANN) return HPGMG_USER_BAD_ARGUMENT;
-    if (face_bc[f] == HPGMG_FACE_NEUMANN) mask |= 1 << f;
+    if (face_bc[f] != HPGMG_FACE_DIRICHLET && face_bc[f] != HPGMG_FACE_NEUMANN && face_bc[f] != HPGMG_FACE_ROBIN) return HPGMG_USER_BAD_ARGUMENT;
+    if (face_bc[f] != HPGMG_FACE_DIRICHLET) mask |= 1 << f;
+    if (face_bc[f] == HPGMG_FACE_ROBIN) robin_mask |= 1 << f;
   }
-  return user_create(n, box_dim, BC_DIRICHLET, mask, op, smoother, a, b, h, out);       /* mask 0 is hpgmg_user_create's solver */
+  return user_create(n, box_dim, BC_DIRICHLET, mask, robin_mask, op, smoother, a, b, h, out);       /* mask 0 is hpgmg_user_create's solver */
 }
 
-static int user_create(int n, int box_dim, int bc, int mask, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out) {
+static int user_create(int n, int box_dim, int bc, int mask, int robin_mask, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out) {
   const hpgmg_transport *T = hpgmg_get_transport();
   if (!out) return HPGMG_USER_BAD_ARGUMENT;
   *out = NULL;
@@ -101,7 +117,7 @@ static int user_create(int n, int box_dim, int bc, int mask, int op, int smoothe
   hpgmg_solver *s = &us->s;
   us->n = n; us->bc = bc; us->operator_ok = us->rhs_ok = 1;
   us->max_iter = 100;
-  us->mask = mask;
+  us->mask = mask; us->robin_mask = robin_mask;      /* kappa starts as 0: Neumann walls until set_coefficients_robin */
   USER_QUIET(us);
   s->boxes_in_i = n / box_dim; s->box_dim = box_dim; s->my_rank = 0; s->num_ranks = 1;
   s->a = a; s->b = b; s->h = h;
@@ -123,7 +139,7 @@ static int user_create(int n, int box_dim, int bc, int mask, int op, int smoothe
   rebuild_operator(&s->level_h, NULL, a, b);
   /* six Neumann walls: a level of one cell would have Aii = 0 for Poisson, so stop at 2^3 as the periodic case does */
   MGBuild(&s->mg, &s->level_h, a, b, (bc == BC_PERIODIC || mask == 63) ? 2 : 1);
-  if (mask) { user_bnd_alloc(us); user_walls_rebuilt(us); }
+  if (mask) { user_bnd_alloc(us); user_walls_rebuilt(us, 0); }
   USER_LOUD();
   *out = us;
   return HPGMG_USER_OK;
@@ -134,9 +150,13 @@ void hpgmg_user_destroy(hpgmg_user_solver *us) {
   USER_QUIET(us);
   if (us->bnd_g) {
     int l;
-    for (l = 0; l < us->s.mg.num_levels; l++) { hpgmg_vector_free(us->bnd_g[l]); hpgmg_vector_free(us->bnd_phi[l]); if (us->wall) hpgmg_vector_free(us->wall[l]); }
+    for (l = 0; l < us->s.mg.num_levels; l++) {
+      hpgmg_vector_free(us->bnd_g[l]); hpgmg_vector_free(us->bnd_phi[l]);
+      if (us->wall) hpgmg_vector_free(us->wall[l]);
+      if (us->kappa) hpgmg_vector_free(us->kappa[l]);
+    }
     hpgmg_vector_free(us->app_g); hpgmg_vector_free(us->app_phi);
-    free(us->bnd_g); free(us->bnd_phi); free(us->wall);
+    free(us->bnd_g); free(us->bnd_phi); free(us->wall); free(us->kappa);
   }
   MGDestroy(&us->s.mg);
   destroy_level(&us->s.level_h);     /* frees the plugin's staging buffer with the level */
@@ -153,16 +173,42 @@ int hpgmg_user_set_max_iterations(hpgmg_user_solver *us, int n) {
 }
 hpgmg_solver *hpgmg_user_solver_of(hpgmg_user_solver *us) { return &us->s; }
 
+/* kappa of set_coefficients_robin into kappa[0]: validated as the caller gave it, then 0.0 on the faces that are not Robin */
+static int user_take_kappa(hpgmg_user_solver *us, const double *kappa, int where) {
+  const size_t face = (size_t)us->n * us->n;
+  int f, st;
+  user_bnd_take(us, us->kappa[0], kappa, where);
+  st = hpgmg_boundary_check_kappa(&us->s.level_h, us->kappa[0], HPGMG_WHERE_PLUGIN, us->robin_mask, &us->kappa_positive);
+  if (us->robin_mask != 63) {
+    double *zero = (double *)calloc(face, sizeof(double));
+    for (f = 0; f < 6; f++) if (!((us->robin_mask >> f) & 1)) hpgmg_vector_upload(us->kappa[0] + f * face, zero, face);
+    free(zero);
+  }
+  return st;
+}
+
 int hpgmg_user_set_coefficients(hpgmg_user_solver *us, const double *alpha, const double *beta_i, const double *beta_j, const double *beta_k, int where) {
+  if (us->robin_mask) return HPGMG_USER_BAD_ARGUMENT;      /* a Robin wall needs its kappa: hpgmg_user_set_coefficients_robin */
+  return hpgmg_user_set_coefficients_robin(us, alpha, beta_i, beta_j, beta_k, NULL, where);
+}
+
+int hpgmg_user_set_coefficients_robin(hpgmg_user_solver *us, const double *alpha, const double *beta_i, const double *beta_j, const double *beta_k,
+                                      const double *kappa, int where) {
   hpgmg_solver *s = &us->s;
   level_type *L = &s->level_h;
   const int helmholtz = s->a != 0.0;
   if (!beta_i || !beta_j || !beta_k || (helmholtz && !alpha) || (!helmholtz && alpha)) return HPGMG_USER_BAD_ARGUMENT;
+  if ((us->robin_mask != 0) != (kappa != NULL)) return HPGMG_USER_BAD_ARGUMENT;
+  if (kappa && where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return HPGMG_USER_BAD_ARGUMENT;
   if (!user_config_ok()) return HPGMG_USER_CONFLICT;
   int st = 0, e;
   USER_QUIET(us);
   us->operator_ok = 0;
   if (us->bnd) us->rhs_ok = 0;           /* the lifted f and every phi_l were made with the old beta: a new set_rhs_dirichlet is needed */
+  if (kappa) {
+    if ((e = user_take_kappa(us, kappa, where)) < 0) goto refused;
+    if (e) { USER_LOUD(); return user_pack_status(e); }
+  }
   if ((e = user_pack_beta(us, VECTOR_BETA_I, beta_i, where, HPGMG_DENSE_FACE_I)) < 0) goto refused;
   st |= e;
   if ((e = user_pack_beta(us, VECTOR_BETA_J, beta_j, where, HPGMG_DENSE_FACE_J)) < 0) goto refused;
@@ -172,9 +218,15 @@ int hpgmg_user_set_coefficients(hpgmg_user_solver *us, const double *alpha, cons
   if (helmholtz && (e = hpgmg_dense_pack(L, VECTOR_ALPHA, alpha, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_NONNEGATIVE)) < 0) goto refused;
   if (helmholtz) st |= e;
   if (st) { USER_LOUD(); return user_pack_status(st); }
-  rebuild_operator(L, NULL, s->a, s->b);
-  MGRebuildCoarse(&s->mg, s->a, s->b);
-  user_walls_rebuilt(us);
+  if (us->robin_mask) {                  /* the wall's part of the diagonal depends on each level's own h (DESIGN.md §11.5) */
+    hpgmg_boundary_store_walls(L, us->wall[0], us->kappa[0], us->mask);
+    rebuild_operator(L, NULL, s->a, s->b);
+    MGRebuildCoarseWalls(&s->mg, s->a, s->b, user_store_walls, us);
+  } else {
+    rebuild_operator(L, NULL, s->a, s->b);
+    MGRebuildCoarse(&s->mg, s->a, s->b);
+  }
+  user_walls_rebuilt(us, us->robin_mask != 0);
   us->operator_ok = 1;
   USER_LOUD();
   return HPGMG_USER_OK;
@@ -209,11 +261,13 @@ static void user_bnd_alloc(hpgmg_user_solver *us) {
   us->bnd_g = (double **)calloc((size_t)G->num_levels, sizeof(double *));
   us->bnd_phi = (double **)calloc((size_t)G->num_levels, sizeof(double *));
   if (us->mask) us->wall = (double **)calloc((size_t)G->num_levels, sizeof(double *));
+  if (us->robin_mask) us->kappa = (double **)calloc((size_t)G->num_levels, sizeof(double *));
   for (l = 0; l < G->num_levels; l++) {
     const size_t n = (size_t)G->levels[l]->dim.i;
     us->bnd_g[l] = hpgmg_vector_alloc(6 * n * n);
     us->bnd_phi[l] = hpgmg_vector_alloc(6 * n * n);
     if (us->mask) us->wall[l] = l ? hpgmg_vector_alloc(6 * n * n) : us->wall0;
+    if (us->robin_mask) us->kappa[l] = hpgmg_vector_alloc(6 * n * n);
   }
   us->app_g = hpgmg_vector_alloc((size_t)6 * us->n * us->n);
   us->app_phi = hpgmg_vector_alloc((size_t)6 * us->n * us->n);
@@ -240,13 +294,13 @@ int hpgmg_user_set_rhs_dirichlet(hpgmg_user_solver *us, const double *f, const d
     hpgmg_vector_upload(us->bnd_g[0], zero, (size_t)6 * us->n * us->n);
     free(zero);
   }
-  const int st = user_pack_status(us->mask ? hpgmg_dense_pack_lifted_faces(L, VECTOR_F, f, where, us->bnd_g[0], s->b, us->mask, us->wall[0])
+  const int st = user_pack_status(us->mask ? hpgmg_dense_pack_lifted_robin(L, VECTOR_F, f, where, us->bnd_g[0], s->b, us->mask, us->wall[0], USER_KAPPA(us, 0))
                                            : hpgmg_dense_pack_lifted(L, VECTOR_F, f, where, us->bnd_g[0], s->b));     /* F = f + T(g) */
   us->rhs_ok = (st == HPGMG_USER_OK);
   if (us->rhs_ok) {                  /* g_l and phi_l of every level, for the F-cycle's right-hand-side correction */
     for (l = 0; l < s->mg.num_levels; l++) {
       if (l > 0) hpgmg_boundary_restrict(s->mg.levels[l], us->bnd_g[l], s->mg.levels[l - 1], us->bnd_g[l - 1]);
-      if (us->mask) hpgmg_boundary_flux_faces(s->mg.levels[l], us->bnd_phi[l], us->bnd_g[l], s->b, us->mask, us->wall[l]);
+      if (us->mask) hpgmg_boundary_flux_robin(s->mg.levels[l], us->bnd_phi[l], us->bnd_g[l], s->b, us->mask, us->wall[l], USER_KAPPA(us, l));
       else hpgmg_boundary_flux(s->mg.levels[l], us->bnd_phi[l], us->bnd_g[l], s->b);
     }
     us->bnd = 1;
@@ -268,7 +322,7 @@ static void user_bnd_restricted(const hpgmg_fmg_hook *hook, mg_type *G, int l, i
 /* after interpolation_fcycle onto level l: the fine cells that read a coarse ghost get what the inhomogeneous ghost adds */
 static void user_bnd_interpolated(const hpgmg_fmg_hook *hook, mg_type *G, int l, int e_id) {
   const hpgmg_user_solver *us = (const hpgmg_user_solver *)hook->ctx;
-  if (us->mask) hpgmg_boundary_interp_faces(G->levels[l], e_id, G->levels[l + 1], us->bnd_g[l + 1], us->mask);
+  if (us->mask) hpgmg_boundary_interp_robin(G->levels[l], e_id, G->levels[l + 1], us->bnd_g[l + 1], us->mask, USER_KAPPA(us, l + 1));
   else hpgmg_boundary_interp(G->levels[l], e_id, G->levels[l + 1], us->bnd_g[l + 1]);
 }
 
@@ -356,7 +410,7 @@ int hpgmg_user_apply_dirichlet(hpgmg_user_solver *us, const double *x, const dou
   USER_QUIET(us);
   user_bnd_alloc(us);
   user_bnd_take(us, us->app_g, g, where);
-  int st = user_pack_status(us->mask ? hpgmg_boundary_flux_faces(L, us->app_phi, us->app_g, s->b, us->mask, us->wall[0])
+  int st = user_pack_status(us->mask ? hpgmg_boundary_flux_robin(L, us->app_phi, us->app_g, s->b, us->mask, us->wall[0], USER_KAPPA(us, 0))
                                      : hpgmg_boundary_flux(L, us->app_phi, us->app_g, s->b));
   if (st == HPGMG_USER_OK) st = user_pack_status(hpgmg_dense_pack(L, us->x_id, x, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
   if (st == HPGMG_USER_OK) {

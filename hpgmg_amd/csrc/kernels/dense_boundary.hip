@@ -1,6 +1,6 @@
 // dense_boundary.hip -- inhomogeneous Dirichlet values of the dense-array API (include/hpgmg_operators.h hpgmg_dense_pack_lifted,
-// hpgmg_boundary_flux / _restrict / _lift / _interp and their per-face-kind forms for Neumann walls; the formulas and their order are written
-// there and in DESIGN.md §11.1, §11.2).  The arithmetic the host defaults (host/hooks_host.inc) must match bit for bit is not written here but in
+// hpgmg_boundary_flux / _restrict / _lift / _interp, their per-face-kind forms for Neumann walls and the Robin forms of those, with
+// hpgmg_boundary_check_kappa / _store_walls; the formulas and their order are written there and in DESIGN.md §11.1, §11.2, §11.5).  The arithmetic the host defaults (host/hooks_host.inc) must match bit for bit is not written here but in
 // include/hpgmg_boundary_math.h, which both compile.
 //
 // A boundary array is 6 x n x n doubles (n = the level's cells per side, a cube): [0], [1] i-low / i-high indexed [k][j], [2], [3] j-low /
@@ -45,9 +45,13 @@ __device__ __forceinline__ FacePos bnd_face_pos(const hpgmg_hip_level &L, int li
 
 // mask, wall, wn (lifted pack and flux): bit f of mask set = face f is a Neumann wall, whose entry is (wn * wall[e]) * gn with
 // wn = b * (1.0 / h) from the host and wall the level's wall-beta array; mask 0 leaves every expression as it was.
+// ROBIN, kappa, h (the Robin forms): the level's kappa array and h; a masked face's entry is then bnd_wall_phi's.  The forms
+// without a kappa array are instantiations of their own, so that they stay the code they were.
+template <bool ROBIN>
 __global__ __launch_bounds__(kBndThreads) void dense_pack_lifted_kernel(const hpgmg_hip_level L, int id, const double *__restrict__ src,
                                                                         const double *__restrict__ g, double w, int mask,
-                                                                        const double *__restrict__ wall, double wn, int *flag) {
+                                                                        const double *__restrict__ wall, double wn,
+                                                                        const double *__restrict__ kappa, double h, int *flag) {
   const int gh = L.ghosts, dim = L.dim, n = L.dim_i;
   int bits = 0;
   for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
@@ -70,7 +74,7 @@ __global__ __launch_bounds__(kBndThreads) void dense_pack_lifted_kernel(const hp
             const double gv = g[e];
             if (!isfinite(gv)) bits |= HPGMG_DENSE_NOT_FINITE;
             const double *beta = face < 2 ? bi : face < 4 ? bj : bk;
-            if ((mask >> face) & 1) T = T + (wn * wall[e]) * gv;
+            if ((mask >> face) & 1) T = T + (ROBIN ? bnd_wall_phi(wn, wall[e], gv, kappa[e], h) : (wn * wall[e]) * gv);
             else T = T + (w * beta[ofs + bnd_beta_step(L, face)]) * gv;
           }
           v = v + T;
@@ -82,9 +86,11 @@ __global__ __launch_bounds__(kBndThreads) void dense_pack_lifted_kernel(const hp
   if (bits) atomicOr(flag, bits);
 }
 
+template <bool ROBIN>
 __global__ __launch_bounds__(kBndThreads) void boundary_flux_kernel(const hpgmg_hip_level L, double *__restrict__ phi,
                                                                     const double *__restrict__ g, double w, int mask,
-                                                                    const double *__restrict__ wall, double wn, int *flag) {
+                                                                    const double *__restrict__ wall, double wn,
+                                                                    const double *__restrict__ kappa, double h, int *flag) {
   const int n = L.dim_i, positions = 6 * L.dim * L.dim;
   int bits = 0;
   for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
@@ -98,12 +104,40 @@ __global__ __launch_bounds__(kBndThreads) void boundary_flux_kernel(const hpgmg_
       const int e = bnd_entry(n, face, gi, gj, gk);
       const double gv = g[e];
       if (!isfinite(gv)) bits |= HPGMG_DENSE_NOT_FINITE;
-      if ((mask >> face) & 1) { phi[e] = (wn * wall[e]) * gv; continue; }
+      if ((mask >> face) & 1) { phi[e] = ROBIN ? bnd_wall_phi(wn, wall[e], gv, kappa[e], h) : (wn * wall[e]) * gv; continue; }
       const double beta = vec_origin(L, box, bnd_beta_vec(face))[i + j * L.jStride + k * L.kStride + bnd_beta_step(L, face)];
       phi[e] = (w * beta) * gv;
     }
   }
   if (bits) atomicOr(flag, bits);
+}
+
+// hpgmg_boundary_check_kappa: one lane per entry of the 6 n^2 array, its bits (bnd_kappa_bits) into the device word
+__global__ __launch_bounds__(kBndThreads) void boundary_check_kappa_kernel(const double *__restrict__ kappa, int n, int robin_mask, int *flag) {
+  const int total = 6 * n * n;
+  int bits = 0;
+  for (int e = (int)(blockIdx.x * kBndThreads + threadIdx.x); e < total; e += (int)(gridDim.x * kBndThreads)) bits |= bnd_kappa_bits(n, robin_mask, e, kappa[e]);
+  if (bits) atomicOr(flag, bits);
+}
+
+// hpgmg_boundary_store_walls: the flux kernel's mapping (grid row y = box, x over its 6 dim^2 face positions, consecutive lanes on consecutive
+// entries of a face).  A position on a masked domain face writes that face's beta of its cell -- index 0 of a box on a low wall, the high ghost
+// layer dim of a box on a high wall -- from the entry of wall and kappa it alone owns; every other position, and a box on no wall, does nothing.
+__global__ __launch_bounds__(kBndThreads) void boundary_store_walls_kernel(const hpgmg_hip_level L, const double *__restrict__ wall,
+                                                                           const double *__restrict__ kappa, double h, int mask) {
+  const int n = L.dim_i, positions = 6 * L.dim * L.dim;
+  for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
+    const int li = L.box_low[3 * box], lj = L.box_low[3 * box + 1], lk = L.box_low[3 * box + 2];
+    for (int t = (int)(blockIdx.x * kBndThreads + threadIdx.x); t < positions; t += (int)(gridDim.x * kBndThreads)) {
+      const int face = t / (L.dim * L.dim);
+      const int r = t - face * L.dim * L.dim, q = r / L.dim, p = r - q * L.dim, side = (face & 1) ? L.dim - 1 : 0;
+      const int i = face < 2 ? side : p, j = face < 2 ? p : face < 4 ? side : q, k = face < 4 ? q : side;
+      const int gi = li + i, gj = lj + j, gk = lk + k;
+      if (!((mask >> face) & 1) || !bnd_touches(n, face, gi, gj, gk)) continue;
+      const int e = bnd_entry(n, face, gi, gj, gk);
+      vec_origin(L, box, bnd_beta_vec(face))[i + j * L.jStride + k * L.kStride + bnd_beta_step(L, face)] = bnd_wall_beta(wall[e], kappa ? kappa[e] : 0.0, h);
+    }
+  }
 }
 
 __global__ __launch_bounds__(kBndThreads) void boundary_restrict_kernel(double *__restrict__ gc, const double *__restrict__ gf, int nc) {
@@ -168,9 +202,12 @@ __device__ __forceinline__ double bnd_coarse_cell(const hpgmg_hip_level &Lc, int
   return vec_origin(Lc, box, id)[(i - li) + (j - lj) * Lc.jStride + (k - lk) * Lc.kStride];
 }
 
-// boundary_interp_kernel with per-face kinds: Lc, nb locate the coarse iterate (vector id of the coarse level), hc is the coarse h
+// boundary_interp_kernel with per-face kinds: Lc, nb locate the coarse iterate (vector id of the coarse level), hc is the coarse h, kappa the
+// coarse level's kappa array (Robin walls; nullptr: the masked walls are Neumann)
+template <bool ROBIN>
 __global__ __launch_bounds__(kBndThreads) void boundary_interp_faces_kernel(const hpgmg_hip_level L, int id, const hpgmg_hip_level Lc, int nb,
-                                                                            const double *__restrict__ gc, double hc, int mask) {
+                                                                            const double *__restrict__ gc, double hc, int mask,
+                                                                            const double *__restrict__ kappa) {
   const int positions = 6 * L.dim * L.dim, nc = Lc.dim_i;
   for (int box = (int)blockIdx.y; box < L.num_boxes; box += (int)gridDim.y) {
     const int li = L.box_low[3 * box], lj = L.box_low[3 * box + 1], lk = L.box_low[3 * box + 2];
@@ -184,7 +221,7 @@ __global__ __launch_bounds__(kBndThreads) void boundary_interp_faces_kernel(cons
       int q[3];
 #pragma unroll
       for (int s = 1; s < 8; s++) if (bnd_p1_ghost(nc, F, s, q, &w)) {
-        const bnd_ghost G = bnd_ghost_faces(nc, gc, hc, mask, q[0], q[1], q[2]);
+        const bnd_ghost G = bnd_ghost_faces(nc, gc, hc, mask, ROBIN ? kappa : nullptr, q[0], q[1], q[2]);
         D = D + w * (G.needs_u ? G.c * bnd_coarse_cell(Lc, id, nb, G.P[0], G.P[1], G.P[2]) + G.s : G.s);
       }
       const int c = P.i + P.j * L.jStride + P.k * L.kStride;
@@ -221,6 +258,12 @@ int hpgmg_hip_graph_flush(void);
 int hpgmg_hip_dense_pack_lifted_faces(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int mask, const double *wall,
                                       double wn, int *status);
 int hpgmg_hip_boundary_flux_faces(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn, int *status);
+int hpgmg_hip_dense_pack_lifted_robin(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int mask, const double *wall,
+                                      double wn, const double *kappa, double h, int *status);
+int hpgmg_hip_boundary_flux_robin(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn,
+                                  const double *kappa, double h, int *status);
+int hpgmg_hip_boundary_interp_robin(const hpgmg_hip_level *L, int id, const hpgmg_hip_level *Lc, int boxes_per_side, const double *g_c, double h_c, int mask,
+                                    const double *kappa_c);
 int hpgmg_hip_dense_pack_lifted(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int *status) {
   return hpgmg_hip_dense_pack_lifted_faces(L, id, src, g, w, 0, nullptr, 0.0, status);
 }
@@ -230,25 +273,54 @@ int hpgmg_hip_boundary_flux(const hpgmg_hip_level *L, double *phi, const double 
 
 int hpgmg_hip_dense_pack_lifted_faces(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int mask, const double *wall,
                                       double wn, int *status) {
+  return hpgmg_hip_dense_pack_lifted_robin(L, id, src, g, w, mask, wall, wn, nullptr, 0.0, status);
+}
+int hpgmg_hip_dense_pack_lifted_robin(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int mask, const double *wall,
+                                      double wn, const double *kappa, double h, int *status) {
   *status = 0;
   if (mask < 0 || mask > 63 || (mask && !wall)) return record_error(hipErrorInvalidValue, "dense_pack_lifted: a wall mask without the wall betas");
   if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "dense_pack_lifted: the level is not a Dirichlet cube");
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
   if (int e = bnd_flag_begin()) return e;
-  hipLaunchKernelGGL(dense_pack_lifted_kernel, bnd_grid(L->volume, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, src, g, w, mask, wall, wn, g_bnd_flag);
+  hipLaunchKernelGGL(kappa ? dense_pack_lifted_kernel<true> : dense_pack_lifted_kernel<false>, bnd_grid(L->volume, L->num_boxes), dim3(kBndThreads), 0, g_stream,
+                     *L, id, src, g, w, mask, wall, wn, kappa, h, g_bnd_flag);
   return bnd_flag_end("dense_pack_lifted_kernel", status);
 }
 
 int hpgmg_hip_boundary_flux_faces(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn, int *status) {
+  return hpgmg_hip_boundary_flux_robin(L, phi, g, w, mask, wall, wn, nullptr, 0.0, status);
+}
+int hpgmg_hip_boundary_flux_robin(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn,
+                                  const double *kappa, double h, int *status) {
   *status = 0;
   if (mask < 0 || mask > 63 || (mask && !wall)) return record_error(hipErrorInvalidValue, "boundary_flux: a wall mask without the wall betas");
   if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "boundary_flux: the level is not a Dirichlet cube");
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
   if (int e = bnd_flag_begin()) return e;
-  hipLaunchKernelGGL(boundary_flux_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, phi, g, w, mask, wall, wn, g_bnd_flag);
+  hipLaunchKernelGGL(kappa ? boundary_flux_kernel<true> : boundary_flux_kernel<false>, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream,
+                     *L, phi, g, w, mask, wall, wn, kappa, h, g_bnd_flag);
   return bnd_flag_end("boundary_flux_kernel", status);
+}
+
+int hpgmg_hip_boundary_check_kappa(const double *kappa, int n, int robin_mask, int *status) {
+  *status = 0;
+  if (!kappa || n <= 0 || n > 9459 || robin_mask < 0 || robin_mask > 63) return record_error(hipErrorInvalidValue, "boundary_check_kappa: no array, or not a face mask");
+  if (int e = hpgmg_hip_graph_flush()) return e;
+  if (int e = bnd_flag_begin()) return e;
+  hipLaunchKernelGGL(boundary_check_kappa_kernel, bnd_grid(6 * n * n, 1), dim3(kBndThreads), 0, g_stream, kappa, n, robin_mask, g_bnd_flag);
+  return bnd_flag_end("boundary_check_kappa_kernel", status);
+}
+
+int hpgmg_hip_boundary_store_walls(const hpgmg_hip_level *L, const double *wall, const double *kappa, double h, int mask) {
+  if (mask < 0 || mask > 63 || !wall) return record_error(hipErrorInvalidValue, "boundary_store_walls: a wall mask without the wall betas");
+  if (!bnd_cube(L) || L->ghosts < 1) return record_error(hipErrorInvalidValue, "boundary_store_walls: the level is not a Dirichlet cube");
+  if (int e = hpgmg_hip_graph_flush()) return e;
+  if (L->num_boxes <= 0 || !mask) return 0;
+  hipLaunchKernelGGL(boundary_store_walls_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, wall, kappa, h, mask);
+  HPGMG_LAUNCH_CHECK("boundary_store_walls_kernel");
+  return 0;
 }
 
 int hpgmg_hip_boundary_restrict(double *g_c, const double *g_f, int n_c) {
@@ -278,14 +350,18 @@ int hpgmg_hip_boundary_interp(const hpgmg_hip_level *L, int id, const double *g_
 }
 
 int hpgmg_hip_boundary_interp_faces(const hpgmg_hip_level *L, int id, const hpgmg_hip_level *Lc, int boxes_per_side, const double *g_c, double h_c, int mask) {
+  return hpgmg_hip_boundary_interp_robin(L, id, Lc, boxes_per_side, g_c, h_c, mask, nullptr);
+}
+int hpgmg_hip_boundary_interp_robin(const hpgmg_hip_level *L, int id, const hpgmg_hip_level *Lc, int boxes_per_side, const double *g_c, double h_c, int mask,
+                                    const double *kappa_c) {
   HPGMG_SKIP_IF_REPLAY();
   if (!bnd_cube(L) || !bnd_cube(Lc) || 2 * Lc->dim_i != L->dim_i || mask < 0 || mask > 63 || Lc->num_boxes <= 0)
     return record_error(hipErrorInvalidValue, "boundary_interp_faces: the levels are not a Dirichlet cube and its coarsening");
   if (boxes_per_side > 0 && (boxes_per_side * Lc->dim != Lc->dim_i || boxes_per_side * boxes_per_side * boxes_per_side != Lc->num_boxes))
     return record_error(hipErrorInvalidValue, "boundary_interp_faces: the coarse boxes do not tile the cube");
   if (L->num_boxes <= 0) return 0;
-  hipLaunchKernelGGL(boundary_interp_faces_kernel, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, *Lc, boxes_per_side,
-                     g_c, h_c, mask);
+  hipLaunchKernelGGL(kappa_c ? boundary_interp_faces_kernel<true> : boundary_interp_faces_kernel<false>, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream, *L, id, *Lc, boxes_per_side,
+                     g_c, h_c, mask, kappa_c);
   HPGMG_LAUNCH_CHECK("boundary_interp_faces_kernel");
   return 0;
 }

@@ -19,6 +19,13 @@ and boundary=None is zero data on every face.  The beta arrays keep their Dirich
 Six Neumann faces without an a alpha term determine u up to a constant: the mean of f + T(boundary) is subtracted (mean_shift) and the
 mean-free u is returned.  Periodic cannot be mixed per face.  DESIGN.md §11.2.
 
+Robin (convective) walls: "convective" in the 6-tuple makes that face a Robin wall  du/dn + kappa u = g  (dn outward): a convective, impedance or
+surface-reaction wall.  kappa >= 0 comes with the coefficients, set_coefficients(alpha, beta_i, beta_j, beta_k, robin=kappa): a (6,N,N)
+array in `boundary`'s layout (the entries of faces that are not "convective" are not read) or six numbers, one per face.  The face's entry of
+`boundary` is g (None: zero data); boundary_from(fn, grad, robin=kappa) samples +-grad.n + kappa fn there.  kappa = 0 is the Neumann wall.
+The wall adds to the operator's diagonal on every level, with that level's own h.  Six Neumann / Robin faces without an a alpha term are
+singular only if kappa is 0 everywhere.  DESIGN.md §11.5.
+
 Coefficients with jumps: solve(f, method="pcg", rtol=..., max_iter=100) runs conjugate gradients preconditioned with one V-cycle per iteration
 where method="mg" (20 V-cycles at most) stalls; it reports through info.converged instead of raising.  DESIGN.md §11.3.
 method="fpcg" is its flexible form, for grids on which the V-cycle is not one fixed operator -- bc="periodic", or N / box_dim with an odd
@@ -38,7 +45,7 @@ import numpy as np
 import hpgmg_amd as H
 
 _BC = {"dirichlet": H.BC_DIRICHLET, "periodic": H.BC_PERIODIC}
-_FACE = {"dirichlet": H.FACE_DIRICHLET, "neumann": H.FACE_NEUMANN}
+_FACE = {"dirichlet": H.FACE_DIRICHLET, "neumann": H.FACE_NEUMANN, "convective": H.FACE_ROBIN}
 _SMOOTHER = {"cheby": H.SMOOTH_CHEBY, "chebyshev": H.SMOOTH_CHEBY, "gsrb": H.SMOOTH_GSRB, "jacobi": H.SMOOTH_JACOBI}
 _OPERATOR = {"7pt": H.OP_7PT, "27pt": H.OP_27PT, "fv4": H.OP_FV4, "fv2": H.OP_FV2}
 _METHOD = {"fmg": H.USER_FMG, "mg": H.USER_MG, "pcg": H.USER_PCG, "fpcg": H.USER_FPCG}
@@ -86,7 +93,7 @@ class Solver:
     """One user problem.  `lib` is the driver library to run on (default: the HIP build, hpgmg_amd.load_driver())."""
 
     def __init__(self, n, box_dim=None, bc="dirichlet", smoother="cheby", a=0.0, b=1.0, h=None, operator="7pt", lib=None, verbose=False):
-        faces = None                    # per-face kinds of a solver with at least one Neumann wall; None: the dirichlet / periodic solver
+        faces = None                    # per-face kinds of a solver with at least one Neumann or Robin wall; None: the dirichlet / periodic solver
         if isinstance(bc, str) and bc == "neumann":
             bc = ("neumann",) * 6
         if isinstance(bc, (tuple, list)):
@@ -97,7 +104,7 @@ class Solver:
                     raise ValueError("bc: periodic cannot be mixed per face (pass bc='periodic' for a periodic box)")
                 if not isinstance(kind, str) or kind not in _FACE:
                     raise ValueError(f"bc: {kind!r} is not one of {sorted(_FACE)}")
-            faces = tuple(bc) if "neumann" in bc else None
+            faces = tuple(bc) if ("neumann" in bc or "convective" in bc) else None
             bc = "dirichlet"            # the shapes and the level's boundary condition; six Dirichlet faces are the "dirichlet" solver
         elif not isinstance(bc, str) or bc not in _BC:
             raise ValueError(f"bc: {bc!r} is not one of {sorted(_BC) + ['neumann']} or a 6-tuple of {sorted(_FACE)}")
@@ -109,6 +116,7 @@ class Solver:
         self.hip = self.lib.hpgmg_backend_name() == b"hip"
         self.n, self.bc, self.faces, self.a, self.b = int(n), bc, faces, float(a), float(b)
         self.h = float(h) if h is not None and h > 0 else 1.0 / self.n
+        self.robin_faces = tuple(f for f in range(6) if faces is not None and faces[f] == "convective")
         self._ptr = None
         out = ctypes.c_void_p()
         if faces is None:
@@ -200,22 +208,63 @@ class Solver:
         return out
 
     # ---- the API
-    def set_coefficients(self, alpha, beta_i, beta_j, beta_k):
-        """alpha: (N,N,N) or None for Poisson (a = 0); beta_*: the face arrays described in the module docstring."""
+    def _kappa(self, robin, kind, like=None):
+        """robin= as the (6,N,N) array of `kind` ('numpy' / 'torch'; like: a tensor whose device a broadcast goes to): an array of that kind
+        is checked like the call's others, six numbers are broadcast per face."""
+        if _is_tensor(robin) or isinstance(robin, np.ndarray):
+            self._arg(robin, (6, self.n, self.n), "robin", kind)
+            return robin
+        try:
+            values = np.array([float(v) for v in robin], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"robin: expected a (6,N,N) array or 6 numbers, got {type(robin).__name__}") from None
+        if values.shape != (6,):
+            raise ValueError(f"robin: shape {values.shape}, expected (6, {self.n}, {self.n}) or 6 numbers (one per face)")
+        full = np.ascontiguousarray(np.broadcast_to(values[:, None, None], (6, self.n, self.n)))
+        if kind == "torch":
+            import torch
+            return torch.from_numpy(full).to(like.device)
+        return full
+
+    def _kappa_bad(self, robin):
+        """Whether the library refuses this kappa: a value that is not finite anywhere, or a negative one on a Robin face."""
+        v = robin.detach().cpu().numpy() if _is_tensor(robin) else robin
+        if not np.isfinite(v).all():
+            return "holds a value that is not finite"
+        if any((v[f] < 0.0).any() for f in self.robin_faces):
+            return "is out of range (kappa must be >= 0 on a Robin face)"
+        return None
+
+    def set_coefficients(self, alpha, beta_i, beta_j, beta_k, robin=None):
+        """alpha: (N,N,N) or None for Poisson (a = 0); beta_*: the face arrays described in the module docstring.
+        robin: kappa of the Robin faces, required exactly when a face is "convective": a (6,N,N) array of the same kind as the others, or 6
+        non-negative numbers, one per face (read on the Robin faces only)."""
         if (alpha is None) != (self.a == 0.0):
             raise ValueError("alpha: required when a != 0 (Helmholtz), must be None when a == 0 (Poisson)")
+        if robin is None and self.robin_faces:
+            raise ValueError("robin: required when a face is 'convective' (kappa of du/dn + kappa u = g: a (6,N,N) array or 6 numbers)")
+        if robin is not None and not self.robin_faces:
+            raise ValueError("robin: this solver has no 'convective' face (bc=)")
         pi, where, kind = self._arg(beta_i, self._face_shape(0), "beta_i")
         pj, _, _ = self._arg(beta_j, self._face_shape(1), "beta_j", kind)
         pk, _, _ = self._arg(beta_k, self._face_shape(2), "beta_k", kind)
         pa = self._arg(alpha, (self.n,) * 3, "alpha", kind)[0] if alpha is not None else None
+        if robin is not None:
+            robin = self._kappa(robin, kind, beta_i)
+            pr = self._arg(robin, (6, self.n, self.n), "robin", kind)[0]
         self._sync_torch(kind)
-        st = self.lib.hpgmg_user_set_coefficients(self._ptr, pa, pi, pj, pk, where)
+        if robin is None:
+            st = self.lib.hpgmg_user_set_coefficients(self._ptr, pa, pi, pj, pk, where)
+        else:
+            st = self.lib.hpgmg_user_set_coefficients_robin(self._ptr, pa, pi, pj, pk, pr, where)
+            if st in (H.USER_NOT_FINITE, H.USER_OUT_OF_RANGE) and self._kappa_bad(robin):      # the library checks kappa first
+                raise ValueError(f"robin: {self._kappa_bad(robin)}")
         if st in (H.USER_NOT_FINITE, H.USER_OUT_OF_RANGE):
             named = [("beta_i", beta_i, 0.0, True), ("beta_j", beta_j, 0.0, True), ("beta_k", beta_k, 0.0, True)]
             if alpha is not None:
                 named.append(("alpha", alpha, 0.0, False))
             self._check(st, self._first_bad(named, st))
-        self._check(st, "alpha, beta_i, beta_j, beta_k")
+        self._check(st, "alpha, beta_i, beta_j, beta_k" + (", robin" if robin is not None else ""))
 
     def _boundary(self, g, kind):
         """(pointer of) the boundary values g: (6,N,N), of the same kind as the call's other arrays; Dirichlet only."""
@@ -223,12 +272,18 @@ class Solver:
             raise ValueError(f"boundary: boundary values need a Dirichlet domain (this solver is {self.bc})")
         return self._arg(g, (6, self.n, self.n), "boundary", kind)[0]
 
-    def boundary_from(self, fn, grad=None):
+    def boundary_from(self, fn, grad=None, robin=None):
         """Boundary values sampled from fn(x, y, z) (NumPy arrays in, an array of their shape out) at the 6 N^2 face centres: cell (i,j,k) is
         centred at ((i+1/2)h, (j+1/2)h, (k+1/2)h), so the faces lie at 0 and N h.  Returns the (6,N,N) NumPy array that boundary= takes.
-        A Neumann face takes the outward normal derivative from grad(x, y, z), which returns the three components of grad u."""
+        A Neumann face takes the outward normal derivative from grad(x, y, z), which returns the three components of grad u; a Robin face
+        that derivative plus kappa fn, kappa from robin= (a (6,N,N) NumPy array or 6 numbers, as set_coefficients takes it)."""
         if self.faces is not None and grad is None:
-            raise ValueError("grad: required when a face is Neumann (grad(x, y, z) returns the three components of grad u)")
+            raise ValueError("grad: required when a face is Neumann or Robin (grad(x, y, z) returns the three components of grad u)")
+        if robin is None and self.robin_faces:
+            raise ValueError("robin: required when a face is 'convective' (kappa of du/dn + kappa u = g: a (6,N,N) array or 6 numbers)")
+        if robin is not None and not self.robin_faces:
+            raise ValueError("robin: this solver has no 'convective' face (bc=)")
+        kappa = self._kappa(robin, "numpy") if robin is not None else None
         n, h = self.n, self.h
         c = (np.arange(n) + 0.5) * h
         slow, fast = np.meshgrid(c, c, indexing="ij")          # entry [q][p]: p the faster index
@@ -241,9 +296,11 @@ class Solver:
                 x, y, z = fast, wall, slow                       # [k][i]
             else:
                 x, y, z = fast, slow, wall                       # [j][i]
-            if self.faces is not None and self.faces[face] == "neumann":
+            if self.faces is not None and self.faces[face] != "dirichlet":
                 normal = np.asarray(grad(x, y, z)[face // 2], dtype=np.float64)
                 g[face] = np.broadcast_to(normal if face & 1 else -normal, (n, n))
+                if self.faces[face] == "convective":
+                    g[face] = g[face] + kappa[face] * np.broadcast_to(np.asarray(fn(x, y, z), dtype=np.float64), (n, n))
             else:
                 g[face] = np.broadcast_to(np.asarray(fn(x, y, z), dtype=np.float64), (n, n))
         return g
@@ -273,7 +330,7 @@ class Solver:
         'fpcg': the same with the flexible beta = -(Ap.z / p.Ap), for bc='periodic' and N / box_dim with an odd factor, where the V-cycle
         varies between iterations and 'pcg' can fail to converge; same arguments and reporting.  DESIGN.md §11.4.
         u0: start from it ('pcg', 'fpcg': as the first iterate; else u = u0 + e, the correction solved with V-cycles, and method is not used).
-        boundary: Dirichlet values (module docstring); f then stands for f + T(boundary) throughout."""
+        boundary: Dirichlet values, Neumann / Robin data (module docstring); f then stands for f + T(boundary) throughout."""
         if method not in _METHOD:
             raise ValueError(f"method: {method!r} is not one of {sorted(_METHOD)}")
         if not rtol > 0.0:

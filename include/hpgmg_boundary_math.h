@@ -1,6 +1,6 @@
 /*
  * hpgmg_boundary_math.h -- INTERNAL: the arithmetic of the dense-array boundary hooks (include/hpgmg_operators.h hpgmg_dense_*, hpgmg_boundary_*;
- * DESIGN.md §11.1, §11.2), written once for the host defaults (host/hooks_host.inc), the HIP plugin (host/plugin_dense.c) and its kernels
+ * DESIGN.md §11.1, §11.2, §11.5), written once for the host defaults (host/hooks_host.inc), the HIP plugin (host/plugin_dense.c) and its kernels
  * (kernels/dense_boundary.hip).  Not part of the C ABI: it declares nothing extern and no caller of the library includes it.
  *
  * The GPU tests hold the HIP build to the host defaults bit for bit, and every build has -ffp-contract=off, so the written order of each
@@ -34,11 +34,25 @@ HPGMG_BND_FN int bnd_entry(int n, int face, int gi, int gj, int gk) {           
   return (face * n + q) * n + p;
 }
 /* BND_AT(face, i, j, k): the entry of `face` at the in-range cell (i, j, k) (its own axis not read) of the array g of an n-cube in scope */
-#define BND_AT(f, i, j, k) g[((f) * n + ((f) < 4 ? (k) : (j))) * n + ((f) < 2 ? (j) : (i))]
+#define BND_IDX(f, i, j, k) (((f) * n + ((f) < 4 ? (k) : (j))) * n + ((f) < 2 ? (j) : (i)))
+#define BND_AT(f, i, j, k) g[BND_IDX(f, i, j, k)]
 
 /* a Dirichlet face's entry of the lift is (w * beta) * g, a Neumann wall's (wn * wall beta) * gn (b the operator's b, h the level's h) */
 HPGMG_BND_FN double bnd_weight(double b, double h) { return (2.0 * b) * (1.0 / (h * h)); }
 HPGMG_BND_FN double bnd_weight_neumann(double b, double h) { return b * (1.0 / h); }
+/* A Robin wall du/dn + kappa u = g, t = kappa * h of the level: the level's beta on the wall is wall * (t / (2.0 + t)), under
+ * the kernels' Dirichlet wall term, and the wall's entry of the lift ((wn * wall) * g) * (2.0 / (2.0 + t)).  kappa = 0.0 is the Neumann wall bit
+ * for bit: +0.0, and a last factor of exactly 1.0. */
+HPGMG_BND_FN double bnd_wall_beta(double wall, double kappa, double h) { const double t = kappa * h; return wall * (t / (2.0 + t)); }
+HPGMG_BND_FN double bnd_wall_phi(double wn, double wall, double g, double kappa, double h) { const double t = kappa * h; return ((wn * wall) * g) * (2.0 / (2.0 + t)); }
+/* hpgmg_boundary_check_kappa's bits for entry e of a kappa array of an n-cube (robin_mask: bit f = face f is a Robin wall): the status bits
+ * of hpgmg_dense_pack (1 not finite, anywhere; 2 negative on a Robin face), and BND_KAPPA_POSITIVE: > 0 on a Robin face */
+#define BND_KAPPA_POSITIVE 4
+HPGMG_BND_FN int bnd_kappa_bits(int n, int robin_mask, int e, double v) {
+  if (!(v - v == 0.0)) return 1;
+  if (!((robin_mask >> (e / (n * n))) & 1)) return 0;
+  return v < 0.0 ? 2 : v > 0.0 ? BND_KAPPA_POSITIVE : 0;
+}
 
 /* S(c) of hpgmg_boundary_lift: the four finer entries under each face entry of coarse cell (gi,gj,gk) of an n-cube, faces in order */
 HPGMG_BND_FN double bnd_fine_sum(int n, const double *phi_f, int gi, int gj, int gk) {
@@ -84,11 +98,16 @@ HPGMG_BND_FN double bnd_ghost_delta(int n, const double *g, int ci, int cj, int 
   return ((c[0] + c[1]) + c[2]) * (2.0 / 3.0);
 }
 
-/* The same ghost with per-face kinds (hpgmg_boundary_interp_faces; bit f of mask: face f is a Neumann wall, hc the coarse h).
+/* The same ghost with per-face kinds (hpgmg_boundary_interp_faces / _robin; bit f of mask: face f is a Neumann or Robin
+ * wall, hc the coarse h, kappa the coarse level's kappa array, NULL: every masked wall is Neumann).
  * Its delta is  needs_u ? c * u + s : s  with u the coarse iterate at the in-range cell P, which the caller reads.  Between Dirichlet walls
- * alone (any ghost under mask 0) needs_u is 0 and s is bnd_ghost_delta: no 0 * u + s, which would turn an s of -0.0 into +0.0. */
+ * alone (any ghost under mask 0) needs_u is 0 and s is bnd_ghost_delta: no 0 * u + s, which would turn an s of -0.0 into +0.0.
+ * Else, m the number of outside axes: c = (1 - (-1)^m) + per outside axis in the order i, j, k (k_a - 1.0), s = 0.0 + per outside axis s_a, with
+ * Dirichlet k_a - 1.0 = -2.0, s_a = 2.0 * g;  Neumann 0, hc * gn;  Robin, t = kappa * hc: (2.0 - t) / (2.0 + t) - 1.0, (2.0 * hc / (2.0 + t)) * g.
+ * Without a Robin wall c is a small integer however it is summed (the bits of §11.2's 1 - 2 * dirichlet -+ 1), and kappa = 0.0 gives Neumann's
+ * terms bit for bit: 2.0 / 2.0 - 1.0 and (2.0 * hc / 2.0) * g. */
 typedef struct { int needs_u, P[3]; double c, s; } bnd_ghost;
-HPGMG_BND_FN bnd_ghost bnd_ghost_faces(int n, const double *g, double hc, int mask, int ci, int cj, int ck) {
+HPGMG_BND_FN bnd_ghost bnd_ghost_faces(int n, const double *g, double hc, int mask, const double *kappa, int ci, int cj, int ck) {
   const int q[3] = { ci, cj, ck };
   int out[3], face[3], a, m = 0, dirichlet = 0;
   bnd_ghost G;
@@ -102,16 +121,24 @@ HPGMG_BND_FN bnd_ghost bnd_ghost_faces(int n, const double *g, double hc, int ma
   G.needs_u = dirichlet != m;
   G.c = 0.0;
   if (!G.needs_u) { G.s = bnd_ghost_delta(n, g, ci, cj, ck); return G; }
-  double s = 0.0;
+  double s = 0.0, c = (m & 1) ? 2.0 : 0.0;
   for (a = 0; a < 3; a++) if (out[a]) {
-    const double ga = BND_AT(face[a], G.P[0], G.P[1], G.P[2]);
-    s = s + (((mask >> face[a]) & 1) ? hc * ga : 2.0 * ga);
+    const int e = BND_IDX(face[a], G.P[0], G.P[1], G.P[2]);
+    const double ga = g[e];
+    if (!((mask >> face[a]) & 1)) { c = c + -2.0; s = s + 2.0 * ga; }
+    else if (!kappa) s = s + hc * ga;
+    else {
+      const double t = kappa[e] * hc;
+      c = c + ((2.0 - t) / (2.0 + t) - 1.0);
+      s = s + (2.0 * hc / (2.0 + t)) * ga;
+    }
   }
-  G.c = (double)(1 - 2 * dirichlet + ((m & 1) ? 1 : -1));
+  G.c = c;
   G.s = s;
   return G;
 }
 #undef BND_AT
+#undef BND_IDX
 
 /* D(c) of hpgmg_boundary_interp / _interp_faces for a fine cell is the sum over t = 1 .. 7, in this order, of w * delta for the reads of
  * interpolation_p1 after the centre (dk, dj, dj+dk, di, di+dk, di+dj, di+dj+dk) that are ghosts of the coarse nc-cube; delta is bnd_ghost_delta

@@ -112,8 +112,18 @@ int  hpgmg_user_apply_dirichlet(hpgmg_user_solver *s, const double *x, const dou
  * beta arrays keep their Dirichlet shapes; a Neumann wall's beta (still > 0) weighs its data, phi = ((b * (1.0 / h)) * beta) * gn, and the operator
  * A_N has 0 there.  set_rhs on such a solver is set_rhs_dirichlet with zero data.  Six Neumann faces without an a alpha term: the constants are in
  * the null space, so set_rhs* subtracts the mean of f + T(g) (*mean_shift) and the solution is the mean-free one. */
-enum { HPGMG_FACE_DIRICHLET = 0, HPGMG_FACE_NEUMANN = 1 };
+/* bit 0: the wall is masked (its beta lives in the solver's wall array, not in the level's vector); bit 1: it carries a kappa.  2 alone is no kind. */
+enum { HPGMG_FACE_DIRICHLET = 0, HPGMG_FACE_NEUMANN = 1, HPGMG_FACE_ROBIN = 3 };
 int  hpgmg_user_create_faces(int n, int box_dim, const int face_bc[6], int op, int smoother, double a, double b, double h, hpgmg_user_solver **out);
+/* Robin (convective) walls: HPGMG_FACE_ROBIN in face_bc makes that face a wall  du/dn + kappa u = g  (dn outward): the entry of g that
+ * set_rhs_dirichlet / apply_dirichlet take for it is that g, and its ghost is ((2 - t) u + 2 h g) / (2 + t), t = kappa h.  kappa >= 0 comes with the
+ * coefficients: set_coefficients_robin takes it as (6,N,N) doubles in g's layout and memory (where), copies it (the entries of faces that are not
+ * Robin are not read: stored as 0) and keeps a restricted copy per level, since the wall's part of the diagonal depends on the level's h.  kappa not
+ * finite: HPGMG_USER_NOT_FINITE, negative on a Robin face: HPGMG_USER_OUT_OF_RANGE.  A solver with a Robin face refuses the plain set_coefficients
+ * (HPGMG_USER_BAD_ARGUMENT); one without takes set_coefficients_robin with kappa == NULL only, as set_coefficients.  kappa = 0 everywhere is the
+ * Neumann wall bit for bit.  Six Neumann or Robin faces without an a alpha term are singular only if kappa is 0 everywhere; else nothing is subtracted. */
+int  hpgmg_user_set_coefficients_robin(hpgmg_user_solver *s, const double *alpha, const double *beta_i, const double *beta_j, const double *beta_k,
+                                       const double *kappa, int where);
 
 /* ---- small accessors so a ctypes caller never needs the struct layouts ---- */
 enum { HPGMG_INFO_DIM = 0, HPGMG_INFO_BOX_DIM, HPGMG_INFO_GHOSTS, HPGMG_INFO_JSTRIDE, HPGMG_INFO_KSTRIDE,
@@ -122,6 +132,7 @@ enum { HPGMG_INFO_DIM = 0, HPGMG_INFO_BOX_DIM, HPGMG_INFO_GHOSTS, HPGMG_INFO_JST
 void   hpgmg_level_info(const level_type *level, int out[HPGMG_INFO_COUNT]);
 double hpgmg_level_h(const level_type *level);
 double hpgmg_level_eigenvalue(const level_type *level);
+int    hpgmg_level_must_subtract_mean(const level_type *level);      /* 1: the cycles keep this level's vectors mean-free (a singular operator); -1: not decided yet */
 void   hpgmg_level_set_eigenvalue(level_type *level, double dominant_eigenvalue_of_DinvA);   /* what rebuild_operator would have left (tests of a Chebyshev smoother on given coefficients) */
 void   hpgmg_level_box_low(const level_type *level, int box, int out[3]);
 int    hpgmg_level_list_counts(const level_type *level, int which, int shape_or_type, int out[3]);

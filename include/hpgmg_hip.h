@@ -379,6 +379,17 @@ int hpgmg_hip_dense_pack_lifted_faces(const hpgmg_hip_level *L, int id, const do
                                       double wn, int *status);
 int hpgmg_hip_boundary_flux_faces(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn, int *status);
 int hpgmg_hip_boundary_interp_faces(const hpgmg_hip_level *L, int id, const hpgmg_hip_level *Lc, int boxes_per_side, const double *g_c, double h_c, int mask);
+/* Robin walls (include/hpgmg_operators.h hpgmg_boundary_check_kappa / _store_walls / *_robin): kappa the level's kappa array
+ * (nullptr in a _robin form: its _faces form), h the level's h.  check_kappa: the 6 n^2 values of a DEVICE array; *status takes hpgmg_dense_pack's
+ * bits and BND_KAPPA_POSITIVE (include/hpgmg_boundary_math.h); synchronises.  store_walls only enqueues, one launch. */
+int hpgmg_hip_boundary_check_kappa(const double *kappa, int n, int robin_mask, int *status);
+int hpgmg_hip_boundary_store_walls(const hpgmg_hip_level *L, const double *wall, const double *kappa, double h, int mask);
+int hpgmg_hip_dense_pack_lifted_robin(const hpgmg_hip_level *L, int id, const double *src, const double *g, double w, int mask, const double *wall,
+                                      double wn, const double *kappa, double h, int *status);
+int hpgmg_hip_boundary_flux_robin(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn,
+                                  const double *kappa, double h, int *status);
+int hpgmg_hip_boundary_interp_robin(const hpgmg_hip_level *L, int id, const hpgmg_hip_level *Lc, int boxes_per_side, const double *g_c, double h_c, int mask,
+                                    const double *kappa_c);
 
 /* ---- operators/rebuild.c:47-208 black-box rebuild: accumulate one colouring (x = 0/1 pattern, ghosts
  *      already exchanged / BCs applied) into Aii and sum|Aij|, then turn them into Dinv, L1inv, lambda_max ---- */

@@ -31,6 +31,10 @@ void MGDestroy(mg_type *all_grids);
 /* MGBuild's last steps: rebuild_operator(level l, level l-1) for every coarser level, then must_subtract_mean of every level.  MGBuild runs it
  * once; a caller that gives the finest level new coefficients runs rebuild_operator(level 0, NULL) and then this. */
 void MGRebuildCoarse(mg_type *all_grids, double a, double b);
+/* MGRebuildCoarse for a caller whose walls need coefficients of the level's own (Robin walls: DESIGN.md §11.5).  Per level l >= 1, in order:
+ * rebuild_operator(level l, level l-1), store_walls(ctx, all_grids, l), which writes level l's wall coefficients, rebuild_operator(level l, NULL);
+ * level l+1 then restricts from the corrected level l.  Then must_subtract_mean of every level, as MGRebuildCoarse. */
+void MGRebuildCoarseWalls(mg_type *all_grids, double a, double b, void (*store_walls)(void *ctx, mg_type *all_grids, int level), void *ctx);
 void MGVCycle(mg_type *all_grids, int e_id, int R_id, double a, double b, int level);
 void MGSolve(mg_type *all_grids, int onLevel, int u_id, int F_id, double a, double b, double rtol);
 void FMGSolve(mg_type *all_grids, int onLevel, int u_id, int F_id, double a, double b, double rtol);

@@ -172,6 +172,24 @@ int     hpgmg_dense_pack_walls(level_type *level, int id, const double *src, int
 int     hpgmg_dense_pack_lifted_faces(level_type *level, int id, const double *f, int where, const double *g, double b, int mask, const double *wall);
 int     hpgmg_boundary_flux_faces(level_type *level, double *phi, const double *g, double b, int mask, const double *wall);
 void    hpgmg_boundary_interp_faces(level_type *fine, int id, level_type *coarse, const double *g_c, int mask);
+/* Robin walls  du/dn + kappa u = g  (DESIGN.md §11.5).  A Robin wall is a masked wall like a Neumann one, with a second boundary array kappa
+ * (6 n^2, >= 0, 0.0 on the faces that are not Robin; restricted with boundary_restrict) and t = kappa * h of the level.  Its ghost is
+ * c u + d g, c = (2 - t) / (2 + t), d = 2 h / (2 + t): a Neumann wall is kappa = 0.0, bit for bit in everything below.
+ *   check_kappa:        validates the 6 n^2 values of kappa (where: HPGMG_WHERE_*): finite everywhere, >= 0 on the faces of robin_mask.  Returns
+ *                       hpgmg_dense_pack's status bits, -1 for a refused argument; *any_positive = 1 if an entry of a Robin face is > 0, else 0.
+ *   store_walls:        the level's beta on the masked walls (index 0 of VECTOR_BETA_I/J/K of a box on a low wall, its high ghost layer dim on a high
+ *                       wall) := wall * (t / (2.0 + t)): the homogeneous Dirichlet wall term with that beta is the Robin wall's.  rebuild_operator
+ *                       (level, NULL, a, b) must follow.  kappa NULL: 0.0 everywhere.
+ *   pack_lifted_robin,  pack_lifted_faces / flux_faces with a masked face's entry  phi = ((b * (1.0 / h)) * wall) * g) * (2.0 / (2.0 + t));
+ *   flux_robin:         kappa NULL: the _faces forms themselves.
+ *   interp_robin:       interp_faces with, per outside axis that is masked, k_a = (2.0 - t) / (2.0 + t), s_a = (2.0 * h_c / (2.0 + t)) * g(P), t from
+ *                       kappa_c at P's wall entry:  delta = ((1 - (-1)^m) + sum (k_a - 1.0)) * u_c(P) + (0.0 + sum s_a), the sums in the order i, j, k,
+ *                       a Dirichlet axis adding -2.0 and 2.0 * g(P).  kappa_c NULL: interp_faces itself. */
+int     hpgmg_boundary_check_kappa(level_type *level, const double *kappa, int where, int robin_mask, int *any_positive);
+void    hpgmg_boundary_store_walls(level_type *level, const double *wall, const double *kappa, int mask);
+int     hpgmg_dense_pack_lifted_robin(level_type *level, int id, const double *f, int where, const double *g, double b, int mask, const double *wall, const double *kappa);
+int     hpgmg_boundary_flux_robin(level_type *level, double *phi, const double *g, double b, int mask, const double *wall, const double *kappa);
+void    hpgmg_boundary_interp_robin(level_type *fine, int id, level_type *coarse, const double *g_c, int mask, const double *kappa_c);
 /* The fine-level passes of the V-cycle-preconditioned CG of the user-problem API (MGPCGSolve, include/hpgmg_mg.h), 7-point operator:
  *   pcg_apply_dot: Ap = A p exactly as apply_op(level, Ap_id, p_id, a, b) leaves it (its ghost exchange and boundary conditions), and *dot = p . Ap
  *   pcg_update:    per interior cell  x = x + alpha * p ;  r = r - alpha * Ap  (the product first, then the sum / difference), *rmax = max |r| (0.0 <= it)

@@ -2,7 +2,9 @@
 """Times the boundary-value path of the user-problem API (hpgmg_user_set_rhs_dirichlet, HPGMG_USER_FMG after it) at 256^3, config 2's
 shape (7-pt Helmholtz, Chebyshev, 2^3 boxes of 128^3), against the homogeneous calls on the same solver: one pack against one lifted pack
 launch, set_rhs against set_rhs_dirichlet (which also builds every level's g_l and phi_l), and the homogeneous F-cycle against the boundary
-F-cycle.  Device arrays; hipEvent pairs on the library's launch stream around each call, the calls alternating.  One JSON line of medians in ms.
+F-cycle.  Then Robin walls next to Neumann ones on two solvers with Dirichlet i-walls: set_coefficients against
+set_coefficients_robin (which adds a kappa check, a store launch per level and a second rebuild per coarse level), and the two F-cycles.
+Device arrays; hipEvent pairs on the library's launch stream around each call, the calls alternating.  One JSON line of medians in ms.
 
     python tools/user_boundary_timing.py [--n 256] [--repeats 7]
 """
@@ -90,6 +92,28 @@ def main():
             tb.append(bnd())
         res["fmg_homogeneous_ms"], res["fmg_boundary_ms"] = statistics.median(tp), statistics.median(tb)
         res["fmg_boundary_over_homogeneous"] = res["fmg_boundary_ms"] / res["fmg_homogeneous_ms"]
+    neumann = ("dirichlet", "dirichlet") + ("neumann",) * 4
+    robin = ("dirichlet", "dirichlet") + ("convective",) * 4
+    with Solver(n, bc=neumann, smoother="cheby", a=1.0, b=1.0, lib=lib) as sn, Solver(n, bc=robin, smoother="cheby", a=1.0, b=1.0, lib=lib) as sr:
+        SN, SR, info, shift, w = sn._ptr, sr._ptr, H.UserInfo(), ctypes.c_double(), H.WHERE_PLUGIN
+        d_alpha, d_betas, d_kappa = put(alpha), [put(b) for b in betas], put(1.0 + rng.random((6, n, n)))
+        res["set_coefficients_neumann_ms"], res["set_coefficients_robin_ms"] = pair(
+            lambda: lib.hpgmg_user_set_coefficients(SN, d_alpha, *d_betas, w),
+            lambda: lib.hpgmg_user_set_coefficients_robin(SR, d_alpha, *d_betas, d_kappa, w))
+
+        def fmg_walls(P):
+            def run():
+                assert lib.hpgmg_user_set_rhs_dirichlet(P, d_f, d_g, w, ctypes.byref(shift)) == 0
+                return once(lambda: lib.hpgmg_user_solve(P, H.USER_FMG, 1e-10, None, w, ctypes.byref(info)))
+            return run
+        fn_, fr_ = fmg_walls(SN), fmg_walls(SR)
+        fn_(), fr_()
+        tn, tr = [], []
+        for _ in range(args.repeats):
+            tn.append(fn_())
+            tr.append(fr_())
+        res["fmg_neumann_ms"], res["fmg_robin_ms"] = statistics.median(tn), statistics.median(tr)
+        res["fmg_robin_over_neumann"] = res["fmg_robin_ms"] / res["fmg_neumann_ms"]
     for p in dev:
         K.hpgmg_hip_free(p)
     K.hpgmg_hip_event_destroy(e0)
