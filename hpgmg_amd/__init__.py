@@ -170,6 +170,9 @@ def _declare_driver_api(lib):
         "hpgmg_dense_pack_lifted_robin": (c_int, [vp, c_int, vp, c_int, vp, c_dbl, c_int, vp, vp]),
         "hpgmg_boundary_flux_robin": (c_int, [vp, vp, vp, c_dbl, c_int, vp, vp]),
         "hpgmg_boundary_interp_robin": (None, [vp, c_int, vp, vp, c_int, vp]),
+        # face fluxes of a solution
+        "hpgmg_user_flux": (c_int, [vp, vp, vp, vp, vp, vp, c_int]),
+        "hpgmg_dense_unpack_flux": (c_int, [vp, c_int, vp, c_dbl, c_int, vp, vp, vp, vp, vp, c_int]),
         # the fine-level passes of method="pcg" 
         "hpgmg_pcg_apply_dot": (c_int, [vp, c_int, c_int, c_dbl, c_dbl, P(c_dbl)]),
         "hpgmg_pcg_update": (c_int, [vp, c_int, c_int, c_int, c_int, c_dbl, P(c_dbl)]),

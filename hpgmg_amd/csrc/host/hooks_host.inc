@@ -1,7 +1,7 @@
 /*
  * hooks_host.inc -- the portable host forms of the dense-array, boundary-value and CG hooks (include/hpgmg_operators.h hpgmg_dense_*,
  * hpgmg_boundary_*, hpgmg_pcg_*): box by box through the plugin's hpgmg_vector_upload / download.  They are weak, so that a plugin with kernels
- * for them (the HIP plugin: host/plugin_dense.c, host/plugin_pcg.c) replaces them while one without (the CPU oracle, whose memory is host memory
+ * for them (the HIP plugin: host/plugin_dense.c, host/plugin_pcg.c; its kernels: kernels/dense_io.hip, dense_boundary.hip, dense_flux.hip, pcg.hip) replaces them while one without (the CPU oracle, whose memory is host memory
  * for either `where`) gets these.  The boundary arithmetic itself is include/hpgmg_boundary_math.h, shared with those kernels.
  * A part of host/driver.c's translation unit, included there.
  */
@@ -299,6 +299,55 @@ __attribute__((weak)) void hpgmg_boundary_interp(level_type *Lf, int id, level_t
 __attribute__((weak)) void hpgmg_boundary_interp_faces(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask) { boundary_interp_host(Lf, id, Lc, g_c, mask, NULL); }
 __attribute__((weak)) void hpgmg_boundary_interp_robin(level_type *Lf, int id, level_type *Lc, const double *g_c, int mask, const double *kappa_c) {
   boundary_interp_host(Lf, id, Lc, g_c, mask, kappa_c);
+}
+
+/* ------------------------------------------------------------------ face fluxes of a solution (include/hpgmg_operators.h; DESIGN.md §11.6)
+ * q of the wall face `face` of the cell with value uc and wall entry e; beta: the level's beta on that face (read on a Dirichlet wall) */
+static double flux_wall_host(int face, int e, double uc, double beta, double b, double wq, double h, int mask, const double *gh, const double *wh,
+                             const double *kh, int *bad) {
+  const double gv = gh ? gh[e] : 0.0;
+  if (!isfinite(gv)) *bad = 1;
+  if ((mask >> face) & 1) return bnd_flux_masked(b, wh[e], kh ? kh[e] : 0.0, h, uc, gv, face & 1);
+  return bnd_flux_dirichlet(wq, beta, uc, gv, face & 1);
+}
+__attribute__((weak)) int hpgmg_dense_unpack_flux(level_type *L, int x_id, const double *g, double b, int mask, const double *wall, const double *kappa,
+                                                  double *flux_i, double *flux_j, double *flux_k, int where) {
+  if (L->num_ranks != 1 || x_id < 0 || x_id >= L->numVectors || !flux_i || !flux_j || !flux_k) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  if (mask < 0 || mask > 63 || (mask && !wall) || L->dim.i != L->dim.j || L->dim.i != L->dim.k || L->box_ghosts < 1) return -1;
+  const int walls = L->boundary_condition.type == BC_DIRICHLET;
+  if (!walls && (g || mask)) return -1;
+  const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t len = (size_t)6 * n * n, vol = (size_t)L->box_volume;
+  const size_t ni = (size_t)dense_extent(n, walls), nn = (size_t)n;      /* flux_i is (n, n, ni), flux_j (n, ni, n), flux_k (ni, n, n) */
+  const double wq = bnd_weight_neumann(b, L->h), h = L->h;
+  double *gh = g ? bnd_download(g, len) : NULL, *wh = mask ? bnd_download(wall, len) : NULL, *kh = mask && kappa ? bnd_download(kappa, len) : NULL;
+  double *u = (double *)malloc(vol * 4 * sizeof(double)), *bi = u + vol, *bj = bi + vol, *bk = bj + vol;
+  int box, i, j, k, bad = 0;
+  for (box = 0; box < L->num_my_boxes; box++) {
+    const box_type *B = &L->my_boxes[box];
+    hpgmg_vector_download(u, B->vectors[x_id], vol);
+    hpgmg_vector_download(bi, B->vectors[VECTOR_BETA_I], vol);
+    hpgmg_vector_download(bj, B->vectors[VECTOR_BETA_J], vol);
+    hpgmg_vector_download(bk, B->vectors[VECTOR_BETA_K], vol);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      const double uc = u[ijk];
+      double *qi = flux_i + ((size_t)gk * nn + (size_t)gj) * ni + (size_t)gi, *qj = flux_j + ((size_t)gk * ni + (size_t)gj) * nn + (size_t)gi;
+      double *qk = flux_k + ((size_t)gk * nn + (size_t)gj) * nn + (size_t)gi;
+      if (walls && gi == 0) *qi = flux_wall_host(0, bnd_entry(n, 0, gi, gj, gk), uc, bi[ijk], b, wq, h, mask, gh, wh, kh, &bad);
+      else *qi = bnd_flux_interior(wq, bi[ijk], u[ijk - 1], uc);
+      if (walls && gi == n - 1) qi[1] = flux_wall_host(1, bnd_entry(n, 1, gi, gj, gk), uc, bi[ijk + 1], b, wq, h, mask, gh, wh, kh, &bad);
+      if (walls && gj == 0) *qj = flux_wall_host(2, bnd_entry(n, 2, gi, gj, gk), uc, bj[ijk], b, wq, h, mask, gh, wh, kh, &bad);
+      else *qj = bnd_flux_interior(wq, bj[ijk], u[ijk - jS], uc);
+      if (walls && gj == n - 1) qj[nn] = flux_wall_host(3, bnd_entry(n, 3, gi, gj, gk), uc, bj[ijk + jS], b, wq, h, mask, gh, wh, kh, &bad);
+      if (walls && gk == 0) *qk = flux_wall_host(4, bnd_entry(n, 4, gi, gj, gk), uc, bk[ijk], b, wq, h, mask, gh, wh, kh, &bad);
+      else *qk = bnd_flux_interior(wq, bk[ijk], u[ijk - kS], uc);
+      if (walls && gk == n - 1) qk[nn * nn] = flux_wall_host(5, bnd_entry(n, 5, gi, gj, gk), uc, bk[ijk + kS], b, wq, h, mask, gh, wh, kh, &bad);
+    }
+  }
+  free(u); free(gh); free(wh); free(kh);
+  return bad ? HPGMG_DENSE_NOT_FINITE : 0;
 }
 
 /* ------------------------------------------------------------------ the CG passes: portable forms (include/hpgmg_operators.h; DESIGN.md §11.3)

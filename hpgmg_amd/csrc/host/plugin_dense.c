@@ -1,6 +1,6 @@
 /*
- * plugin_dense.c -- hpgmg_dense_pack / hpgmg_dense_unpack of the operator plugin (include/hpgmg_operators.h): one launch of
- * kernels/dense_io.hip per array.  A device array is read / written in place; a host array is copied once into the level's staging buffer
+ * plugin_dense.c -- hpgmg_dense_pack / hpgmg_dense_unpack / hpgmg_dense_unpack_flux of the operator plugin (include/hpgmg_operators.h): one launch
+ * of kernels/dense_io.hip per array (the three flux arrays: one of kernels/dense_flux.hip).  A device array is read / written in place; a host array is copied once into the level's staging buffer
  * (allocated on first use, freed with the level) and packed from there, or unpacked into it and copied out once.  They replace the weak
  * host defaults of host/hooks_host.inc, which go box by box through hpgmg_vector_upload / download.  The boundary-value hooks below likewise
  * (their arithmetic: include/hpgmg_boundary_math.h, shared with the kernels and the host defaults).
@@ -54,6 +54,32 @@ int hpgmg_dense_unpack(level_type *L, int id, double *dst, int where) {
   HIP_OK(hpgmg_hip_dense_unpack(&B->dev, id, stage));
   HIP_OK(hpgmg_hip_memcpy_d2h(dst, stage, n * sizeof(double)));
   return 0;
+}
+
+/* face fluxes of vector x_id: one launch of kernels/dense_flux.hip for the three arrays, written in place when they are device
+ * arrays, else into the staging buffer (sized for the three) and copied out, one copy each */
+int hpgmg_dense_unpack_flux(level_type *L, int x_id, const double *g, double b, int mask, const double *wall, const double *kappa,
+                            double *flux_i, double *flux_j, double *flux_k, int where) {
+  int status = 0;
+  if (L->num_ranks != 1 || x_id < 0 || x_id >= L->numVectors || !flux_i || !flux_j || !flux_k) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  if (mask < 0 || mask > 63 || (mask && !wall) || L->dim.i != L->dim.j || L->dim.i != L->dim.k || L->box_ghosts < 1) return -1;
+  if (L->boundary_condition.type != BC_DIRICHLET && (g || mask)) return -1;
+  backend_t *B = hp_backend_of(L);
+  const double wq = bnd_weight_neumann(b, L->h);
+  if (where == HPGMG_WHERE_PLUGIN) {
+    HIP_OK(hpgmg_hip_dense_unpack_flux(&B->dev, x_id, g, b, wq, L->h, mask, wall, mask ? kappa : NULL, flux_i, flux_j, flux_k, &status));
+    return status;
+  }
+  size_t n[3];
+  dense_extents(L, HPGMG_DENSE_FACE_I, n);
+  const size_t len = n[0] * n[1] * n[2];          /* of each of the three: the level is a cube */
+  double *stage = dense_stage(B, 3 * len);
+  HIP_OK(hpgmg_hip_dense_unpack_flux(&B->dev, x_id, g, b, wq, L->h, mask, wall, mask ? kappa : NULL, stage, stage + len, stage + 2 * len, &status));
+  HIP_OK(hpgmg_hip_memcpy_d2h(flux_i, stage, len * sizeof(double)));
+  HIP_OK(hpgmg_hip_memcpy_d2h(flux_j, stage + len, len * sizeof(double)));
+  HIP_OK(hpgmg_hip_memcpy_d2h(flux_k, stage + 2 * len, len * sizeof(double)));
+  return status;
 }
 
 /* boundary values (include/hpgmg_operators.h): one launch of kernels/dense_boundary.hip each.  g, phi, wall are device arrays

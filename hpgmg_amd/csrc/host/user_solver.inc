@@ -422,3 +422,22 @@ int hpgmg_user_apply_dirichlet(hpgmg_user_solver *us, const double *x, const dou
   return st;
 }
 
+int hpgmg_user_flux(hpgmg_user_solver *us, const double *u, const double *g, double *flux_i, double *flux_j, double *flux_k, int where) {
+  hpgmg_solver *s = &us->s;
+  level_type *L = &s->level_h;
+  if (!u || !flux_i || !flux_j || !flux_k || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
+  if (g && us->bc != BC_DIRICHLET) return HPGMG_USER_UNSUPPORTED;
+  if (!us->operator_ok) return HPGMG_USER_NOT_READY;
+  if (!user_config_ok()) return HPGMG_USER_CONFLICT;
+  USER_QUIET(us);
+  int st = user_pack_status(hpgmg_dense_pack(L, us->x_id, u, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
+  if (st == HPGMG_USER_OK) {
+    if (g) { user_bnd_alloc(us); user_bnd_take(us, us->app_g, g, where); }
+    exchange_boundary(L, us->x_id, stencil_get_shape());      /* the neighbours across box faces and the periodic wrap; no ghost outside the domain is read */
+    st = user_pack_status(hpgmg_dense_unpack_flux(L, us->x_id, g ? us->app_g : NULL, s->b, us->mask, us->mask ? us->wall[0] : NULL, USER_KAPPA(us, 0),
+                                                  flux_i, flux_j, flux_k, where));
+  }
+  USER_LOUD();
+  return st;
+}
+

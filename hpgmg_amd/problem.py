@@ -32,6 +32,12 @@ method="fpcg" is its flexible form, for grids on which the V-cycle is not one fi
 factor, where BiCGStab solves the coarsest level to a tolerance: "pcg" can fail to converge there, "fpcg" does not rely on the symmetry it lacks.
 Elsewhere the two take the same iterations; "fpcg" pays one more fused inner product each.  DESIGN.md §11.4.
 
+Fluxes: flux(u, boundary=g) returns (flux_i, flux_j, flux_k), q = -b beta grad u on every face -- the heat flux, Darcy velocity or current
+density -- in the shapes of beta_i, beta_j, beta_k and positive towards increasing index: flux_i[k][j][i] on the face between cells i-1 and i
+(periodic: face 0 lies between cell N-1 and cell 0).  A wall face holds what the wall's ghost gives, with a Neumann or Robin wall's own beta and
+kappa, so that cell by cell  a alpha u + (1/h) sum_d (q_d[high face] - q_d[low face])  is apply(u, boundary=g).  wall_flux(fluxes) is the
+(6,N,N) OUTWARD flux through the walls in `boundary`'s layout; h^2 times its sum is what leaves the box.  DESIGN.md §11.6.
+
 NumPy arrays take the host path.  torch tensors on the library's GPU (float64, contiguous) are read and written in place, and results come
 back as tensors on that device.  torch must be imported before this package loads its libraries: both bring a HIP runtime
 (libamdhip64.so.7), and a device pointer is only valid inside the runtime that made it.  The C entry points are hpgmg_user_* of
@@ -376,6 +382,50 @@ class Solver:
             self._check(st, self._first_bad([("boundary", boundary, 0.0, False), ("x", x, 0.0, False)], st))
         self._check(st, "x, boundary")
         return out
+
+    def flux(self, u, boundary=None, out=None):
+        """(flux_i, flux_j, flux_k): q = -b beta grad u on every face, in the shapes of beta_i, beta_j, beta_k and positive towards increasing
+        index (module docstring).  boundary: the data u was solved with (None: zero data).  out: an optional triple of arrays of
+        u's kind to write into.  NumPy arrays or tensors according to u."""
+        pu, where, kind = self._arg(u, (self.n,) * 3, "u")
+        pg = self._boundary(boundary, kind) if boundary is not None else None
+        shapes = [self._face_shape(axis) for axis in range(3)]
+        if out is None:
+            if kind == "torch":
+                import torch
+                out = tuple(torch.empty(shape, dtype=torch.float64, device=u.device) for shape in shapes)
+            else:
+                out = tuple(np.empty(shape, dtype=np.float64) for shape in shapes)
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 3:
+                raise ValueError("out: expected a triple (flux_i, flux_j, flux_k) of arrays")
+            out = tuple(out)
+        po = [self._arg(q, shape, f"out[{axis}]", kind)[0] for axis, (q, shape) in enumerate(zip(out, shapes))]
+        self._sync_torch(kind)
+        st = self.lib.hpgmg_user_flux(self._ptr, pu, pg, po[0], po[1], po[2], where)
+        if st == H.USER_NOT_FINITE:
+            named = [("u", u, 0.0, False)] + ([("boundary", boundary, 0.0, False)] if boundary is not None else [])
+            self._check(st, self._first_bad(named, st))
+        self._check(st, "u, boundary" if boundary is not None else "u")
+        return out
+
+    def wall_flux(self, fluxes):
+        """The OUTWARD flux through the six walls as a (6,N,N) array in `boundary`'s layout, from the triple flux() returned: the wall entries
+        of the three arrays, those of the low walls negated.  Its sum times h^2 is what leaves the box."""
+        if self.bc != "dirichlet":
+            raise ValueError(f"fluxes: a {self.bc} solver has no walls")
+        if not isinstance(fluxes, (tuple, list)) or len(fluxes) != 3:
+            raise ValueError("fluxes: expected the triple (flux_i, flux_j, flux_k) of flux()")
+        kind = None
+        for axis, q in enumerate(fluxes):
+            kind = self._arg(q, self._face_shape(axis), f"fluxes[{axis}]", kind)[2]
+        qi, qj, qk = fluxes
+        n = self.n
+        faces = [-qi[:, :, 0], qi[:, :, n], -qj[:, 0, :], qj[:, n, :], -qk[0], qk[n]]
+        if kind == "torch":
+            import torch
+            return torch.stack(faces).contiguous()
+        return np.ascontiguousarray(np.stack(faces))
 
     def close(self):
         if self._ptr is not None:

@@ -1,7 +1,7 @@
 /*
  * hpgmg_boundary_math.h -- INTERNAL: the arithmetic of the dense-array boundary hooks (include/hpgmg_operators.h hpgmg_dense_*, hpgmg_boundary_*;
- * DESIGN.md §11.1, §11.2, §11.5), written once for the host defaults (host/hooks_host.inc), the HIP plugin (host/plugin_dense.c) and its kernels
- * (kernels/dense_boundary.hip).  Not part of the C ABI: it declares nothing extern and no caller of the library includes it.
+ * DESIGN.md §11.1, §11.2, §11.5, §11.6), written once for the host defaults (host/hooks_host.inc), the HIP plugin (host/plugin_dense.c) and its kernels
+ * (kernels/dense_boundary.hip, kernels/dense_flux.hip).  Not part of the C ABI: it declares nothing extern and no caller of the library includes it.
  *
  * The GPU tests hold the HIP build to the host defaults bit for bit, and every build has -ffp-contract=off, so the written order of each
  * floating-point expression here IS the contract: change one and both sides change together.  Whatever reads a vector of the level (the coarse
@@ -52,6 +52,21 @@ HPGMG_BND_FN int bnd_kappa_bits(int n, int robin_mask, int e, double v) {
   if (!(v - v == 0.0)) return 1;
   if (!((robin_mask >> (e / (n * n))) & 1)) return 0;
   return v < 0.0 ? 2 : v > 0.0 ? BND_KAPPA_POSITIVE : 0;
+}
+
+/* Face fluxes of a solution (hpgmg_dense_unpack_flux): q = -b beta du/dx_d on a face of axis d, positive towards increasing
+ * index, wq = bnd_weight_neumann(b, h).  Between two cells (a periodic wrap included) it is bnd_flux_interior.  On a Dirichlet wall the ghost is
+ * 2 g - u_c and beta the level's; `high`: the wall is the high one of its axis.  On a masked wall (Neumann or Robin; wall, kappa the entries of
+ * the solver's arrays, t = kappa * h) the OUTWARD flux is Q = ((b * wall) * (2.0 / (2.0 + t))) * (kappa * u_c - g): q = Q on a high wall, -Q on
+ * a low one.  kappa = 0.0 is the Neumann wall bit for bit: a factor of exactly 1.0 and +-0.0 - g. */
+HPGMG_BND_FN double bnd_flux_interior(double wq, double beta, double u_lo, double u_hi) { return (wq * beta) * (u_lo - u_hi); }
+HPGMG_BND_FN double bnd_flux_dirichlet(double wq, double beta, double u_c, double g, int high) {
+  return high ? (wq * beta) * (2.0 * (u_c - g)) : (wq * beta) * (2.0 * (g - u_c));
+}
+HPGMG_BND_FN double bnd_flux_masked(double b, double wall, double kappa, double h, double u_c, double g, int high) {
+  const double t = kappa * h;
+  const double Q = ((b * wall) * (2.0 / (2.0 + t))) * (kappa * u_c - g);
+  return high ? Q : -Q;
 }
 
 /* S(c) of hpgmg_boundary_lift: the four finer entries under each face entry of coarse cell (gi,gj,gk) of an n-cube, faces in order */

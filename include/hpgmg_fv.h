@@ -124,6 +124,15 @@ int  hpgmg_user_create_faces(int n, int box_dim, const int face_bc[6], int op, i
  * Neumann wall bit for bit.  Six Neumann or Robin faces without an a alpha term are singular only if kappa is 0 everywhere; else nothing is subtracted. */
 int  hpgmg_user_set_coefficients_robin(hpgmg_user_solver *s, const double *alpha, const double *beta_i, const double *beta_j, const double *beta_k,
                                        const double *kappa, int where);
+/* Face fluxes of u: q = -b beta grad u on every face -- the heat flux, Darcy velocity or current density -- into three arrays of
+ * the shapes of beta_i / beta_j / beta_k, positive towards increasing index: flux_i[k][j][i] on the face between cells i-1 and i, entries 0 and N of a
+ * Dirichlet-shaped solver being the domain walls (periodic: face 0 lies between cell N-1 and cell 0).  With wq = b * (1.0 / h) an inner face holds
+ * (wq * beta) * (u_lo - u_hi); a wall face what the wall's ghost gives (2 g - u on a Dirichlet wall, u + h g on a Neumann one, the Robin ghost), with
+ * the wall's own beta and kappa on a Neumann / Robin wall, so that cell by cell  a alpha u + (1/h) sum_d (q_d[high face] - q_d[low face])  is what
+ * apply_dirichlet(u, g) returns.  u, g and the outputs are in the same memory (where); g == NULL: zero data (a periodic solver takes no other:
+ * HPGMG_USER_UNSUPPORTED).  u or a g entry not finite: HPGMG_USER_NOT_FINITE; after a refused set_coefficients: HPGMG_USER_NOT_READY.  Only the
+ * solver's operand vector (apply's) is written: the solution, the right-hand side and the state of the last set_rhs stay as they were. */
+int  hpgmg_user_flux(hpgmg_user_solver *s, const double *u, const double *g, double *flux_i, double *flux_j, double *flux_k, int where);
 
 /* ---- small accessors so a ctypes caller never needs the struct layouts ---- */
 enum { HPGMG_INFO_DIM = 0, HPGMG_INFO_BOX_DIM, HPGMG_INFO_GHOSTS, HPGMG_INFO_JSTRIDE, HPGMG_INFO_KSTRIDE,

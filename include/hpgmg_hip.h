@@ -390,6 +390,13 @@ int hpgmg_hip_boundary_flux_robin(const hpgmg_hip_level *L, double *phi, const d
                                   const double *kappa, double h, int *status);
 int hpgmg_hip_boundary_interp_robin(const hpgmg_hip_level *L, int id, const hpgmg_hip_level *Lc, int boxes_per_side, const double *g_c, double h_c, int mask,
                                     const double *kappa_c);
+/* face fluxes of vector id (include/hpgmg_operators.h hpgmg_dense_unpack_flux; kernels/dense_flux.hip): ONE launch writes the three
+ * DEVICE arrays flux_i / j / k (each one longer along its axis unless the level is periodic).  The level is a cube with ghost zones whose box-to-box
+ * part holds id's neighbours; g, wall, kappa are DEVICE boundary arrays (g nullptr: zero data; wall, kappa read under mask only; kappa nullptr:
+ * Neumann walls); b the operator's b, wq = b * (1.0 / h), h the level's.  Validates the g values read (HPGMG_DENSE_NOT_FINITE in *status) and
+ * synchronises. */
+int hpgmg_hip_dense_unpack_flux(const hpgmg_hip_level *L, int id, const double *g, double b, double wq, double h, int mask, const double *wall,
+                                const double *kappa, double *flux_i, double *flux_j, double *flux_k, int *status);
 
 /* ---- operators/rebuild.c:47-208 black-box rebuild: accumulate one colouring (x = 0/1 pattern, ghosts
  *      already exchanged / BCs applied) into Aii and sum|Aij|, then turn them into Dinv, L1inv, lambda_max ---- */

@@ -190,6 +190,19 @@ void    hpgmg_boundary_store_walls(level_type *level, const double *wall, const 
 int     hpgmg_dense_pack_lifted_robin(level_type *level, int id, const double *f, int where, const double *g, double b, int mask, const double *wall, const double *kappa);
 int     hpgmg_boundary_flux_robin(level_type *level, double *phi, const double *g, double b, int mask, const double *wall, const double *kappa);
 void    hpgmg_boundary_interp_robin(level_type *fine, int id, level_type *coarse, const double *g_c, int mask, const double *kappa_c);
+/* Face fluxes of vector x_id: q = -b beta du/dx_d on every face of axis d, positive towards increasing index, into three dense
+ * arrays of the shapes of the beta arrays (FACE_I / J / K: one longer along their axis on a Dirichlet level, (N,N,N) on a periodic one, whose
+ * face 0 lies between cell N-1 and cell 0).  With wq = b * (1.0 / h), between cells lo and hi = lo + 1:  q = (wq * beta) * (u_lo - u_hi), beta the
+ * level's; on a Dirichlet wall (ghost 2 g - u_c)  q = (wq * beta) * (2.0 * (g - u_c)) low, (wq * beta) * (2.0 * (u_c - g)) high; on a masked wall
+ * (mask, wall, kappa as above; t = kappa * h)  Q = ((b * wall) * (2.0 / (2.0 + t))) * (kappa * u_c - g),  q = Q high, -Q low.  Then cell by cell
+ * a alpha u + (1/h) sum_d (q_d[high face] - q_d[low face])  is  A0 u - T(g).  A box writes its dim low faces along each axis and face dim where that
+ * is the domain's high wall, so every entry is written once.  g, wall, kappa: boundary arrays in the plugin's memory; g NULL: zero data (required on
+ * a periodic level); wall is required when mask != 0; kappa NULL: every masked wall is Neumann.  The outputs are host or plugin memory (where).  The
+ * caller has filled x_id's box-to-box ghost zones (exchange_boundary); no ghost outside the domain is read.  Returns hpgmg_dense_pack's status bits
+ * (HPGMG_DENSE_NOT_FINITE: an entry of g that was read is not finite), -1 for a refused argument.  Weak host default in host/hooks_host.inc; the HIP
+ * plugin overrides it with one launch for the three arrays (kernels/dense_flux.hip). */
+int     hpgmg_dense_unpack_flux(level_type *level, int x_id, const double *g, double b, int mask, const double *wall, const double *kappa,
+                                double *flux_i, double *flux_j, double *flux_k, int where);
 /* The fine-level passes of the V-cycle-preconditioned CG of the user-problem API (MGPCGSolve, include/hpgmg_mg.h), 7-point operator:
  *   pcg_apply_dot: Ap = A p exactly as apply_op(level, Ap_id, p_id, a, b) leaves it (its ghost exchange and boundary conditions), and *dot = p . Ap
  *   pcg_update:    per interior cell  x = x + alpha * p ;  r = r - alpha * Ap  (the product first, then the sum / difference), *rmax = max |r| (0.0 <= it)
