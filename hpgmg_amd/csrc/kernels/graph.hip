@@ -7,10 +7,18 @@
 // created device mirrors exist), captured into a hipGraph the second time, and from then on
 // REPLAYED: while a replay segment is open every launcher in this library returns at once
 // (nothing is enqueued), and closing the segment launches the instantiated graph.  Kernel
-// arguments are baked into the graph, which is valid because a segment's operation sequence,
-// vector ids and coefficients are fixed after MGBuild; the cache is dropped whenever a level is
-// released or the configuration changes.  Reductions / copies that synchronise with the host
-// close the open segment first (they cannot be part of a graph).
+// arguments are baked into the graph: device pointers (a level's vectors, the boundary arrays
+// of a user solver) and scalars (a, b, h, the Chebyshev coefficients).  A replay is valid as
+// long as the same launches with the same arguments would be issued again.  Every scalar and
+// everything that decides the launch sequence is part of the key (mg.c seg_reset: hierarchy,
+// start level, vector ids, a, b, the F-cycle hook, every level's eigenvalue bound), and the
+// cache is dropped whenever plugin memory is released (hpgmg_vector_free, a level's release:
+// also when a level grows by vectors) or the configuration changes, so no baked pointer
+// outlives what it points to.  The coefficients themselves are NOT fixed after MGBuild
+// (hpgmg_user_set_coefficients): they are only pointed to and read anew by every replay, so new
+// values in the same vectors need no new graph, and a rebuilt operator with other eigenvalue
+// bounds gets another key.  Reductions / copies that synchronise with the host close the open
+// segment first (they cannot be part of a graph).
 #include <stdio.h>
 #include <stdlib.h>
 #include <unordered_map>
