@@ -28,6 +28,7 @@
 /* ---------------------------------------------------------------- restriction.c:104-212 */
 void hp_do_restriction(level_type *Lc, int id_c, level_type *Lf, int id_f, int type) {
   TICK(Lf, restriction_total, "restriction");
+  hp_coef_written(Lc, id_c);                           /* (a restriction into a coefficient vector: VECTOR_DINV no longer follows from them) */
   communicator_type *S = &Lf->restriction[type], *R = &Lc->restriction[type];
   backend_t *Bc = hp_backend_of(Lc), *Bf = hp_backend_of(Lf);
   HIP_OK(hpgmg_hip_restrict_blocks(&Bc->dev, id_c, &Bf->dev, id_f, hp_mirror(Lf, S->blocks[0], S->num_blocks[0]), S->num_blocks[0], type));
@@ -232,6 +233,7 @@ int hpgmg_residual_norm_fused(level_type *L, int res_id, int x_id, int rhs_id, d
 
 static void interpolation_lists(level_type *Lf, int id_f, double prescale, level_type *Lc, int id_c, int order, int tagbits) {
   TICK(Lf, interpolation_total, "interpolation");
+  hp_coef_written(Lf, id_f);
   communicator_type *S = &Lc->interpolation, *R = &Lf->interpolation;
   backend_t *Bc = hp_backend_of(Lc), *Bf = hp_backend_of(Lf);
   HIP_OK(hpgmg_hip_interpolate_blocks(&Bf->dev, id_f, 0.0, &Bc->dev, id_c, hp_mirror(Lc, S->blocks[0], S->num_blocks[0]), S->num_blocks[0], order));
@@ -307,15 +309,15 @@ void interpolation_fcycle(level_type *Lf, int id_f, double prescale, level_type 
 }
 
 /* ---------------------------------------------------------------- misc.c */
-void hp_do_zero_vector(level_type *L, int id) { BLAS1(hpgmg_hip_fill(&hp_backend_of(L)->dev, id, 0.0)); }
-void init_vector(level_type *L, int id, double s) { BLAS1(hpgmg_hip_fill(&hp_backend_of(L)->dev, id, s)); }
-void hp_do_add_vectors(level_type *L, int c, double sa, int a, double sb, int b) { BLAS1(hpgmg_hip_axpby(&hp_backend_of(L)->dev, c, sa, a, sb, b)); }
-void hp_do_mul_vectors(level_type *L, int c, double s, int a, int b) { BLAS1(hpgmg_hip_mul(&hp_backend_of(L)->dev, c, s, a, b)); }
-void invert_vector(level_type *L, int c, double s, int a) { BLAS1(hpgmg_hip_invert(&hp_backend_of(L)->dev, c, s, a)); }
-void hp_do_scale_vector(level_type *L, int c, double s, int a) { BLAS1(hpgmg_hip_scale(&hp_backend_of(L)->dev, c, s, a)); }
-void shift_vector(level_type *L, int c, int a, double shift) { BLAS1(hpgmg_hip_shift(&hp_backend_of(L)->dev, c, a, shift)); }
-void color_vector(level_type *L, int id, int colors, int ic, int jc, int kc) { BLAS1(hpgmg_hip_color(&hp_backend_of(L)->dev, id, colors, ic, jc, kc)); }
-void random_vector(level_type *L, int id) { BLAS1(hpgmg_hip_random(&hp_backend_of(L)->dev, id)); }
+void hp_do_zero_vector(level_type *L, int id) { hp_coef_written(L, id); BLAS1(hpgmg_hip_fill(&hp_backend_of(L)->dev, id, 0.0)); }
+void init_vector(level_type *L, int id, double s) { hp_coef_written(L, id); BLAS1(hpgmg_hip_fill(&hp_backend_of(L)->dev, id, s)); }
+void hp_do_add_vectors(level_type *L, int c, double sa, int a, double sb, int b) { hp_coef_written(L, c); BLAS1(hpgmg_hip_axpby(&hp_backend_of(L)->dev, c, sa, a, sb, b)); }
+void hp_do_mul_vectors(level_type *L, int c, double s, int a, int b) { hp_coef_written(L, c); BLAS1(hpgmg_hip_mul(&hp_backend_of(L)->dev, c, s, a, b)); }
+void invert_vector(level_type *L, int c, double s, int a) { hp_coef_written(L, c); BLAS1(hpgmg_hip_invert(&hp_backend_of(L)->dev, c, s, a)); }
+void hp_do_scale_vector(level_type *L, int c, double s, int a) { hp_coef_written(L, c); BLAS1(hpgmg_hip_scale(&hp_backend_of(L)->dev, c, s, a)); }
+void shift_vector(level_type *L, int c, int a, double shift) { hp_coef_written(L, c); BLAS1(hpgmg_hip_shift(&hp_backend_of(L)->dev, c, a, shift)); }
+void color_vector(level_type *L, int id, int colors, int ic, int jc, int kc) { hp_coef_written(L, id); BLAS1(hpgmg_hip_color(&hp_backend_of(L)->dev, id, colors, ic, jc, kc)); }
+void random_vector(level_type *L, int id) { hp_coef_written(L, id); BLAS1(hpgmg_hip_random(&hp_backend_of(L)->dev, id)); }
 
 /* A launch of bricks (kernels/brick_visit.hip, brick_wide.hip) whose workgroups could not all run gives up after 2 s and raises an error word; every scalar the
  * host waits for passes hp_allreduce_scalar, which is where it learns of it.  Inside a solve the driver can repeat (hpgmg_solve_attempt_begin / _end, one

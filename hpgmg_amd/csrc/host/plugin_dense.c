@@ -40,6 +40,7 @@ int hpgmg_dense_pack(level_type *L, int id, const double *src, int where, int la
   if (layout < HPGMG_DENSE_CELL || layout > HPGMG_DENSE_FACE_K) return -1;
   dense_extents(L, layout, n);
   if (!(src = dense_source(L, id, src, where, n[0] * n[1] * n[2]))) return -1;
+  hp_coef_written(L, id);
   HIP_OK(hpgmg_hip_dense_pack(&hp_backend_of(L)->dev, id, src, (int)n[0], (int)n[1], (int)n[2], check, &status));
   return status;
 }
@@ -91,6 +92,7 @@ int hpgmg_dense_pack_walls(level_type *L, int id, const double *src, int where, 
   if (mask < 0 || mask > 63 || L->boundary_condition.type != BC_DIRICHLET || L->dim.i != L->dim.j || L->dim.i != L->dim.k) return -1;
   dense_extents(L, layout, n);
   if (!(src = dense_source(L, id, src, where, n[0] * n[1] * n[2]))) return -1;
+  hp_coef_written(L, id);
   HIP_OK(hpgmg_hip_dense_pack_walls(&hp_backend_of(L)->dev, id, src, layout - HPGMG_DENSE_FACE_I, check, mask, wall, &status));
   return status;
 }
@@ -99,6 +101,7 @@ int hpgmg_dense_pack_lifted_robin(level_type *L, int id, const double *f, int wh
   int status = 0;
   if (!g || L->boundary_condition.type != BC_DIRICHLET || mask < 0 || mask > 63 || (mask && !wall)) return -1;
   if (!(f = dense_source(L, id, f, where, (size_t)L->dim.i * L->dim.j * L->dim.k))) return -1;
+  hp_coef_written(L, id);
   HIP_OK(hpgmg_hip_dense_pack_lifted_robin(&hp_backend_of(L)->dev, id, f, g, bnd_weight(b, L->h), mask, wall, bnd_weight_neumann(b, L->h),
                                            mask ? kappa : NULL, L->h, &status));
   return status;
@@ -128,6 +131,7 @@ void hpgmg_boundary_restrict(level_type *Lc, double *g_c, level_type *Lf, const 
 }
 
 void hpgmg_boundary_lift(level_type *L, int id, const double *phi, const double *phi_fine, double sign) {
+  hp_coef_written(L, id);
   HIP_OK(hpgmg_hip_boundary_lift(&hp_backend_of(L)->dev, id, phi, phi_fine, sign));
 }
 
@@ -160,5 +164,6 @@ int hpgmg_boundary_check_kappa(level_type *L, const double *kappa, int where, in
 }
 void hpgmg_boundary_store_walls(level_type *L, const double *wall, const double *kappa, int mask) {
   if (!mask || !wall) return;
+  hp_dinv_record_clear(L);                             /* the wall betas change: VECTOR_DINV is stale until the next rebuild_operator */
   HIP_OK(hpgmg_hip_boundary_store_walls(&hp_backend_of(L)->dev, wall, kappa, L->h, mask));
 }

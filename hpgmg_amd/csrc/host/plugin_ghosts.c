@@ -16,6 +16,7 @@ void hp_transport_phase(const communicator_type *recv_side, const communicator_t
 /* ---------------------------------------------------------------- exchange_boundary.c:12-117 */
 void exchange_boundary(level_type *L, int id, int shape) {
   TICK(L, ghostZone_total, "exchange_boundary");
+  hp_coef_written(L, id);                              /* (ghost zones count: the high faces of the betas are read there) */
   if (shape >= STENCIL_MAX_SHAPES) shape = STENCIL_SHAPE_BOX;
   communicator_type *C = &L->exchange_ghosts[shape];
   backend_t *B = hp_backend_of(L);
@@ -150,6 +151,7 @@ void apply_BCs_p1(level_type *L, int x_id, int shape) {
   if (shape >= STENCIL_MAX_SHAPES) shape = STENCIL_SHAPE_BOX;
   if (L->boundary_condition.type == BC_PERIODIC) return;
   TICK(L, boundary_conditions, "apply_BCs_p1");
+  hp_coef_written(L, x_id);
   backend_t *B = hp_backend_of(L);
   const int n = L->boundary_condition.num_blocks[shape];
   HIP_OK(hpgmg_hip_apply_bc_p1(&B->dev, x_id, hp_mirror(L, L->boundary_condition.blocks[shape], n), n));
@@ -280,6 +282,7 @@ void apply_BCs_v4(level_type *L, int x_id, int shape) {                         
 void extrapolate_betas(level_type *L) {                                                    /* boundary_fv.c:573-681 */
   if (L->boundary_condition.type == BC_PERIODIC) return;
   TICK(L, boundary_conditions, "extrapolate_betas");
+  hp_dinv_record_clear(L);
   const int n = L->boundary_condition.num_blocks[STENCIL_SHAPE_BOX];
   HIP_OK(hpgmg_hip_extrapolate_betas(&hp_backend_of(L)->dev, hp_mirror(L, L->boundary_condition.blocks[STENCIL_SHAPE_BOX], n), n));
   TOCK();

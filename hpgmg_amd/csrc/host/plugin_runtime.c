@@ -52,8 +52,8 @@ double *hpgmg_vector_alloc(size_t n) {
 /* a postponed operator may still hold this storage, and so may a captured launch graph (create_vectors() growing a level after solves have run:
  * FMGSolve -> MGPCG -> FMGSolve would otherwise replay graphs over the freed slab) */
 void hpgmg_vector_free(double *p) { hp_lazy_flush(); hpgmg_hip_graph_reset(); hpgmg_hip_free(p); }
-void hpgmg_vector_copy(double *d, const double *s, size_t n) { HIP_OK(hpgmg_hip_memcpy_d2d(d, s, n * sizeof(double))); }
-void hpgmg_vector_upload(double *d, const double *s, size_t n) { HIP_OK(hpgmg_hip_memcpy_h2d(d, s, n * sizeof(double))); }
+void hpgmg_vector_copy(double *d, const double *s, size_t n) { hp_dinv_record_written(d, n); HIP_OK(hpgmg_hip_memcpy_d2d(d, s, n * sizeof(double))); }
+void hpgmg_vector_upload(double *d, const double *s, size_t n) { hp_dinv_record_written(d, n); HIP_OK(hpgmg_hip_memcpy_h2d(d, s, n * sizeof(double))); }
 void hpgmg_vector_download(double *d, const double *s, size_t n) { HIP_OK(hpgmg_hip_memcpy_d2h(d, s, n * sizeof(double))); }
 
 /* ---------------------------------------------------------------- transport selection
@@ -196,6 +196,7 @@ void hpgmg_level_release(level_type *L) {
   hpgmg_level_ext *X = hpgmg_level_ext_get(L);
   backend_t *B = (backend_t *)X->backend;
   int s;
+  hp_dinv_record_forget(L);
   if (!B) return;
   hpgmg_hip_pair_packed_forget(&B->dev);
   hp_images_release(B);

@@ -343,7 +343,43 @@ static const float *const *coef32_of(level_type *L) {
   if (!B->coef32_valid) { HIP_OK(hpgmg_hip_coef32_refresh(&B->dev, (float *const *)B->d_coef32_base, L->numVectors)); B->coef32_valid = 1; }
   return (const float *const *)B->d_coef32_base;
 }
-void hp_coef32_invalidate(level_type *L) { backend_t *B = hp_backend_of(L); B->coef32_valid = 0; if (B->halo) B->halo->coef_valid = 0; hp_images_invalidate_coefficients(B); hpgmg_hip_pair_packed_invalidate(&B->dev); }
+void hp_coef32_invalidate(level_type *L) { backend_t *B = hp_backend_of(L); B->coef32_valid = 0; hp_dinv_record_clear(L); if (B->halo) B->halo->coef_valid = 0; hp_images_invalidate_coefficients(B); hpgmg_hip_pair_packed_invalidate(&B->dev); }
+
+/* ---- the record "VECTOR_DINV is rebuild_operator's" (plugin_internal.h: backend_t.dinv_rebuilt).  The levels that hold it are listed, so that a raw copy into
+ * device storage (hpgmg_vector_upload / _copy know a pointer, not a level) can find the level it touches; a level the list has no room for never gets the record. */
+enum { DINV_RECORDS = 64 };
+static level_type *dinv_recorded[DINV_RECORDS];
+void hp_dinv_record_forget(level_type *L) { int q; for (q = 0; q < DINV_RECORDS; q++) if (dinv_recorded[q] == L) dinv_recorded[q] = NULL; }
+void hp_dinv_record_clear(level_type *L) {
+  hpgmg_level_ext *X = hpgmg_level_ext_get(L);
+  if (X->backend) ((backend_t *)X->backend)->dinv_rebuilt = 0;
+  hp_dinv_record_forget(L);
+}
+void hp_dinv_record_set(level_type *L, double a, double b, double h2inv) {
+  backend_t *B = hp_backend_of(L);
+  int q, slot = -1;
+  for (q = 0; q < DINV_RECORDS; q++) { if (dinv_recorded[q] == L) { slot = q; break; } if (slot < 0 && !dinv_recorded[q]) slot = q; }
+  if (slot < 0) return;
+  dinv_recorded[slot] = L;
+  B->dinv_rebuilt = 1; B->dinv_a = a; B->dinv_b = b; B->dinv_h2inv = h2inv;
+}
+void hp_dinv_record_written(const double *dst, size_t n) {
+  int q, bx;
+  for (q = 0; q < DINV_RECORDS; q++) {
+    level_type *L = dinv_recorded[q];
+    if (!L) continue;
+    for (bx = 0; bx < L->num_my_boxes; bx++) {
+      const double *lo = L->my_boxes[bx].vectors[0] + (size_t)VECTOR_DINV * (size_t)L->box_volume, *hi = L->my_boxes[bx].vectors[0] + (size_t)(VECTOR_ALPHA + 1) * (size_t)L->box_volume;
+      if (dst < hi && dst + n > lo) { hp_dinv_record_clear(L); break; }
+    }
+  }
+}
+/* may this launch form Dinv?  The record holds, it was made with exactly these a, b, h2inv (bit for bit), and the switch is on; the kernel library adds: an instance that can */
+void hpgmg_set_pair_form_dinv(int on) { hp_switch_set(SW_PAIR_FORM_DINV, on ? 1 : 0); }
+long long hpgmg_pair_formed_dinv_launches(void) { hp_lazy_flush(); return hpgmg_hip_pair_formed_dinv_launches(); }
+static int dinv_formable(const backend_t *B, double a, double b, double h2inv) {
+  return hp_switch(SW_PAIR_FORM_DINV) && B->dinv_rebuilt && memcmp(&a, &B->dinv_a, sizeof a) == 0 && memcmp(&b, &B->dinv_b, sizeof b) == 0 && memcmp(&h2inv, &B->dinv_h2inv, sizeof h2inv) == 0;
+}
 
 static long long pair_remote_smooths = 0, fp32_pair_smooths = 0;
 long long hpgmg_pair_remote_smooths(void) { return pair_remote_smooths; }   /* smooth() calls done as sweep pairs with remote faces (tests) */
@@ -406,7 +442,7 @@ long long hpgmg_interp_folded_remote(void) { return interp_folded_remote; }     
 /* the first pair of a smooth() with the fold requested first: the request is consumed per launch, and a two-part launch is two launches */
 static int first_pair_folded(const hpgmg_hip_level *fold_Lc, backend_t *B, int v, int x_id, int rhs_id, double a, double b, double h2inv, const double *c1, const double *c2) {
   hpgmg_hip_pair_fold_interpolation(fold_Lc, x_id, 1.0);
-  return hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, 0, x_id, 0, VECTOR_TEMP, 1, 0, 1, 1, rhs_id, a, b, h2inv, c1[0], c2[0], c1[1], c2[1]);
+  return hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, 0, x_id, 0, VECTOR_TEMP, 1, 0, 1, 1, rhs_id, a, b, h2inv, c1[0], c2[0], c1[1], c2[1], dinv_formable(B, a, b, h2inv));
 }
 static int smooth_cheby_pairs_fold(level_type *L, int x_id, int rhs_id, double a, double b, const double *c1, const double *c2, int sweeps, int temp_dead, const hpgmg_hip_level *fold_Lc) {
   if (!pair_kernel_ready(L, x_id, rhs_id, sweeps)) return 0;
@@ -424,15 +460,15 @@ static int smooth_cheby_pairs_fold(level_type *L, int x_id, int rhs_id, double a
   }
   { TICK(L, smooth, "smooth (Chebyshev sweeps 1+2)");
     if (remote && fold_Lc) PAIR_REMOTE_LAUNCH(over, 0, first_pair_folded(fold_Lc, B, v, x_id, rhs_id, a, b, h2inv, c1, c2));
-    else if (remote) PAIR_REMOTE_LAUNCH(over, 0, hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, c32, 0, x_id, 0, VECTOR_TEMP, 1, 0, 1, 1, rhs_id, a, b, h2inv, c1[0], c2[0], c1[1], c2[1]));
-    else HIP_OK(hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, c32, 0, x_id, 0, VECTOR_TEMP, 1, 0, 1, 1, rhs_id, a, b, h2inv, c1[0], c2[0], c1[1], c2[1]));
+    else if (remote) PAIR_REMOTE_LAUNCH(over, 0, hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, c32, 0, x_id, 0, VECTOR_TEMP, 1, 0, 1, 1, rhs_id, a, b, h2inv, c1[0], c2[0], c1[1], c2[1], dinv_formable(B, a, b, h2inv)));
+    else HIP_OK(hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, c32, 0, x_id, 0, VECTOR_TEMP, 1, 0, 1, 1, rhs_id, a, b, h2inv, c1[0], c2[0], c1[1], c2[1], dinv_formable(B, a, b, h2inv)));
     TOCK(); }
   if (remote) over = hp_pair_halo_begin(L, B, 0, 1, 1, 1, 0, rhs_id);
   { TICK(L, smooth, "smooth (Chebyshev sweeps 3+4)");
-    if (remote) PAIR_REMOTE_LAUNCH(over, temp_dead, hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, c32, 1, 1, 1, 0, 0, VECTOR_TEMP, 0, x_id, rhs_id, a, b, h2inv, c1[2], c2[2], c1[3], c2[3]));
+    if (remote) PAIR_REMOTE_LAUNCH(over, temp_dead, hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, c32, 1, 1, 1, 0, 0, VECTOR_TEMP, 0, x_id, rhs_id, a, b, h2inv, c1[2], c2[2], c1[3], c2[3], dinv_formable(B, a, b, h2inv)));
     else {
       if (temp_dead) hpgmg_hip_pair_discard_x1();
-      HIP_OK(hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, c32, 1, 1, 1, 0, 0, VECTOR_TEMP, 0, x_id, rhs_id, a, b, h2inv, c1[2], c2[2], c1[3], c2[3]));
+      HIP_OK(hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, c32, 1, 1, 1, 0, 0, VECTOR_TEMP, 0, x_id, rhs_id, a, b, h2inv, c1[2], c2[2], c1[3], c2[3], dinv_formable(B, a, b, h2inv)));
     }
     TOCK(); }
   return 1;
@@ -451,13 +487,13 @@ static int smooth_gsrb_pairs(level_type *L, int x_id, int rhs_id, double a, doub
   int over = 0;
   if (remote) { pair_remote_smooths++; over = hp_pair_halo_begin(L, B, 1, 0, x_id, 0, x_id, rhs_id); }
   { TICK(L, smooth, "smooth (GSRB half sweeps 1+2)");
-    if (remote) PAIR_REMOTE_LAUNCH(over, 0, hpgmg_hip_smooth_gsrb_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, 0, x_id, 0, 1, 1, rhs_id, a, b, h2inv, 0));
-    else HIP_OK(hpgmg_hip_smooth_gsrb_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, 0, x_id, 0, 1, 1, rhs_id, a, b, h2inv, 0));
+    if (remote) PAIR_REMOTE_LAUNCH(over, 0, hpgmg_hip_smooth_gsrb_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, 0, x_id, 0, 1, 1, rhs_id, a, b, h2inv, 0, dinv_formable(B, a, b, h2inv)));
+    else HIP_OK(hpgmg_hip_smooth_gsrb_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, 0, x_id, 0, 1, 1, rhs_id, a, b, h2inv, 0, dinv_formable(B, a, b, h2inv)));
     TOCK(); }
   if (remote) over = hp_pair_halo_begin(L, B, 0, 1, 1, 1, 1, rhs_id);
   { TICK(L, smooth, "smooth (GSRB half sweeps 3+4)");
-    if (remote) PAIR_REMOTE_LAUNCH(over, 0, hpgmg_hip_smooth_gsrb_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, 1, 1, 0, 0, x_id, rhs_id, a, b, h2inv, 2));
-    else HIP_OK(hpgmg_hip_smooth_gsrb_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, 1, 1, 0, 0, x_id, rhs_id, a, b, h2inv, 2));
+    if (remote) PAIR_REMOTE_LAUNCH(over, 0, hpgmg_hip_smooth_gsrb_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, 1, 1, 0, 0, x_id, rhs_id, a, b, h2inv, 2, dinv_formable(B, a, b, h2inv)));
+    else HIP_OK(hpgmg_hip_smooth_gsrb_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, 1, 1, 0, 0, x_id, rhs_id, a, b, h2inv, 2, dinv_formable(B, a, b, h2inv)));
     TOCK(); }
   return 1;
 }

@@ -33,6 +33,9 @@ struct PairArgs {
   int rhs_id;
   double a, b, h2inv, c1a, c2a, c1b, c2b;           // Chebyshev coefficients of the two sweeps
   int sweep_a;                                      // GSRB: number of the first half sweep (its colour; the second is sweep_a + 1)
+  int form_dinv;                                    // 1: the launch runs a FORM instance -- Dinv is not read but formed per cell from the coefficients of the step, as rebuild7_kernel
+                                                    // (blas1.hip) stored it.  Set by the launcher only when the caller vouches that VECTOR_DINV is that kernel's output for these a, b,
+                                                    // h2inv, and only where a FORM instance exists (fp64 coefficient streams, one rank, variable coefficients, 10 or 12 waves)
   int keep_x1;                                      // 0: x1 is not stored (only its tile-edge columns exist, from the pre-pass): the caller declared out1 scratch
   // INTERP variants: x0 is not read as stored but as  prescale * x0 + (coarse parent)  -- interpolation_vcycle
   // (interpolation_p0.c:43) folded into the first sweep pair of the smooth() that follows it in MGVCycle (mg.c:1160-1161)
@@ -124,14 +127,35 @@ __device__ __forceinline__ p2 pair_update(p2 c, double left, double right, p2 jm
   return o;
 }
 
+// Dinv of a lane's two cells, formed as rebuild7_kernel (blas1.hip, operators.7pt.c:158-227) forms the stored vector: the same expression tree on the
+// same operands (the products and sums in its order, no contraction, a correctly rounded division), hence the same bits.  f* = (wall flag - 2.0) of the
+// six faces: -2.0 on a domain wall, -1.0 elsewhere; in i the low face of the first cell (lane 0 of the first tile) and the high face of the second one
+// (lane 63 of the last tile) can be walls, the face between the two cells never is.  nbh2 = (-b) * h2inv.
+template <int V>
+__device__ __forceinline__ p2 pair_form_dinv(const PlaneCoef<V> &q, double fil, double fih, double fjl, double fjh, double fkl, double fkh, double a, double nbh2) {
+  double d0 = q.bi.x * fil;     double d1 = q.bi.y * (1.0 - 2.0);
+  d0 = d0 + q.bjlo.x * fjl;     d1 = d1 + q.bjlo.y * fjl;
+  d0 = d0 + q.bk0.x * fkl;      d1 = d1 + q.bk0.y * fkl;
+  d0 = d0 + q.bi.y * (1.0 - 2.0); d1 = d1 + q.bir * fih;
+  d0 = d0 + q.bjhi.x * fjh;     d1 = d1 + q.bjhi.y * fjh;
+  d0 = d0 + q.bk1.x * fkh;      d1 = d1 + q.bk1.y * fkh;
+  double A0 = nbh2 * d0, A1 = nbh2 * d1;
+  if (V == HPGMG_HIP_7PT_VC_HELMHOLTZ) { A0 = A0 + a * q.al.x; A1 = A1 + a * q.al.y; }
+  return p2{1.0 / A0, 1.0 / A1};
+}
+
 constexpr int kPairMaxBoxes = 1024;       // boxes per rank the pair kernel takes (their base-pointer tables are copied into LDS, see below)
-template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP, bool REMOTE = false>
+template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP, bool REMOTE = false, bool FORM = false>
 __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_level L_in, const PairArgs A_in) {
   static_assert(!(REMOTE && C32) && !(REMOTE && NARROW && INTERP), "the multi-rank variant is built for fp64 coefficients; with narrow boxes the interpolation is not folded in");
   // REMOTE + INTERP: the parent is added to the cells of the brick only -- what arrives in ghost zones and deep planes was packed by its owner with ITS parents already added (pair_halo_kernel)
   constexpr bool kVC = (V != HPGMG_HIP_7PT_CC);
   constexpr bool kHelm = (V == HPGMG_HIP_7PT_VC_HELMHOLTZ);
   constexpr int NR = NW - 2;
+  // FORM: Dinv is formed in registers instead of read (PairArgs.form_dinv) -- a template parameter and not a flag tested in the loop: with the flag the instances ran
+  // 2 % slower than before whichever way it pointed.  fp64 coefficient streams of one rank; not the 16-wave instances: held to 128 registers
+  // they spill 7 as they are and 27 with the division.
+  static_assert(!FORM || (kVC && !C32 && !REMOTE && NW != 16), "no FORM instance of this kind");
   extern __shared__ p2 pair_lds[];                              // 3 x [2 buffers][NW rows][64 pairs] = NW x 6 KiB
   p2 (*slabX0)[NW][64] = reinterpret_cast<p2 (*)[NW][64]>(pair_lds);
   p2 (*slabX1)[NW][64] = reinterpret_cast<p2 (*)[NW][64]>(pair_lds + 2 * NW * 64);
@@ -289,16 +313,21 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
     const bool ghost_plane = REMOTE && (p < 0 || p >= A.Dk);
     // ---- loads: x0 / beta_j / far row one plane ahead, everything else for plane p
     if (row_x1) {
-      if (above_in) {
-        const int bn = box_of(bi_, bj_, p + 1), offn = row_off + plane_off(p + 1);
-        x0p = REMOTE ? x0_row(bj_, lj, p + 1) : x0_pair(bn, li, lj, p + 1);
-        if (have_next) {
-          if (kVC) bj_n = CoefStream<C32>(L, A, bn, VECTOR_BETA_J, C32_BETA_J, sh).pair(offn);
-          if (far_lo || far_hi) far_n = far_row(p + 1);
+      // (FORM instances issue the coefficient loads first and the iterate streams after them: the loads return in order, so Dinv -- two divisions --
+      // can be formed while the last of x0 / rhs / x_{n-1} are still on their way)
+      auto load_ahead = [&]() {
+        if (above_in) {
+          const int bn = box_of(bi_, bj_, p + 1), offn = row_off + plane_off(p + 1);
+          x0p = REMOTE ? x0_row(bj_, lj, p + 1) : x0_pair(bn, li, lj, p + 1);
+          if (have_next) {
+            if (kVC) bj_n = CoefStream<C32>(L, A, bn, VECTOR_BETA_J, C32_BETA_J, sh).pair(offn);
+            if (far_lo || far_hi) far_n = far_row(p + 1);
+          }
         }
-      }
-      qc.rhs = pld(vec_origin(L, box, A.rhs_id) + sh.lvl + off);
-      qc.dinv = CoefStream<C32>(L, A, box, VECTOR_DINV, C32_DINV, sh).pair(off);
+        qc.rhs = pld(vec_origin(L, box, A.rhs_id) + sh.lvl + off);
+      };
+      if (!FORM) load_ahead();
+      if (!FORM) qc.dinv = CoefStream<C32>(L, A, box, VECTOR_DINV, C32_DINV, sh).pair(off);
       if (kHelm) qc.al = CoefStream<C32>(L, A, box, VECTOR_ALPHA, C32_ALPHA, sh).pair(off);
       if (kVC) {
         const CoefStream<C32> bis(L, A, box, VECTOR_BETA_I, C32_BETA_I, sh), bks(L, A, box, VECTOR_BETA_K, C32_BETA_K, sh);
@@ -316,11 +345,15 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
         else if (w == NRs + 1 || gj + 1 >= jhi || ((lj + 1) == bd)) qc.bjhi = CoefStream<C32>(L, A, box, VECTOR_BETA_J, C32_BETA_J, sh).pair(off + jS);
         else qc.bjhi = slabBJ[p & 1][w + 1][lane];
       }
+      if (FORM) load_ahead();
       // x_{n-1} of the first sweep.  When its coefficient c1a is exactly 0 (the first Chebyshev sweep of every smooth(), chebyshev.c:30) the
       // stream is not read: x0 stands in, the term is c1a * 0 = +0, and x0 + (+0) = x0 as with any finite x_{n-1} (the one representable
       // difference: an x0 of exactly -0.0 could come out as +0.0)
       p2 xm1 = x0c;
       if (SM == PAIR_CHEBY && A.c1a != 0.0) xm1 = pld(pair_vec(L, A, A.xm1, box) + shift_of(sh, A.xm1) + off);
+      if (FORM)      // the wall flags are those of the in-register Dirichlet rule below (one rank: the brick is the domain)
+        qc.dinv = pair_form_dinv<V>(qc, (lane == 0 && left_dom) ? -2.0 : -1.0, (lane == 63 && right_dom) ? -2.0 : -1.0, (gj - 1 < 0) ? -2.0 : -1.0, (gj + 1 >= A.Dj) ? -2.0 : -1.0,
+                                    (p - 1 < 0) ? -2.0 : -1.0, (p + 1 >= A.Dk) ? -2.0 : -1.0, A.a, (-A.b) * A.h2inv);
 #ifdef HPGMG_EXP_TIMELINE
       if (probe) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
       TL_MARK();                                                 // 1: every load of the step has arrived

@@ -46,6 +46,20 @@ double *g_exp_timeline = nullptr;     // experiment build: where a kernel's chos
 }  // namespace hpgmg
 using namespace hpgmg;
 
+// one launch of the instance <V, NW, C32, SM, NARROW, INTERP> on one rank -- its FORM twin where A.form_dinv asks for it (smooth_pair sets that only where the twin exists)
+template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP, bool FORM>
+static int pair_launch_instance(int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A) {
+  static bool once = false;
+  if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)cheby_pair_kernel<V, NW, C32, SM, NARROW, INTERP, false, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NW * 6 * 64 * sizeof(p2)))); once = true; }
+  hipLaunchKernelGGL((cheby_pair_kernel<V, NW, C32, SM, NARROW, INTERP, false, FORM>), dim3(grid), dim3(64, NW), lds, g_stream, *L, A);
+  return 0;
+}
+template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP>
+static int pair_launch(int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A) {
+  if constexpr (V != HPGMG_HIP_7PT_CC && !C32 && NW != 16) { if (A.form_dinv) return pair_launch_instance<V, NW, C32, SM, NARROW, INTERP, true>(grid, lds, L, A); }
+  return pair_launch_instance<V, NW, C32, SM, NARROW, INTERP, false>(grid, lds, L, A);
+}
+
 extern "C" {
 int hpgmg_hip_graph_flush(void);
 
@@ -79,7 +93,7 @@ int hpgmg_hip_coef32_refresh(const hpgmg_hip_level *L, float *const *c32_base, i
 static bool g_pair_halo_set = false;
 static int g_pair_rem[6], g_pair_brick[3];
 static const double *g_pair_deep = nullptr, *g_pair_deep_beta = nullptr;
-static long long g_pair_launches = 0, g_pair_remote_launches = 0;
+static long long g_pair_launches = 0, g_pair_remote_launches = 0, g_pair_formed_launches = 0;
 static int g_pair_discard_x1 = 0;     // consumed by the next Chebyshev pair launch: its out1 vector is scratch, do not store x1
 static const hpgmg_hip_level *g_pair_interp_level = nullptr;
 static int g_pair_interp_id = 0;
@@ -136,7 +150,7 @@ static const PairOrder *pair_part_order(const PairArgs &A, int part) {
 }
 static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int sweep_a, double *const *scr_base, const float *const *c32_base,
                        int x0_scr, int x0_id, int xm1_scr, int xm1_id, int out1_scr, int out1_id, int out2_scr, int out2_id,
-                       int rhs_id, double a, double b, double h2inv, double c1a, double c2a, double c1b, double c2b) {
+                       int rhs_id, double a, double b, double h2inv, double c1a, double c2a, double c1b, double c2b, int dinv_is_rebuilt) {
   // the requests set for THIS launch (hpgmg_hip_pair_set_halo / _discard_x1 / _set_interp) are taken here, before any exit: whatever
   // happens below, none of them can stay pending and change a later launch
   const bool remote = g_pair_halo_set;
@@ -182,6 +196,9 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
   A.rhs_id = rhs_id; A.a = a; A.b = b; A.h2inv = h2inv; A.c1a = c1a; A.c2a = c2a; A.c1b = c1b; A.c2b = c2b;
   A.scr_base = scr_base; A.c32_base = c32_base; A.sweep_a = sweep_a;
   A.keep_x1 = discard_x1 ? 0 : 1;
+  // dinv_is_rebuilt: the caller vouches that VECTOR_DINV is what rebuild7_kernel made of the current coefficient vectors with these a, b, h2inv; the instances that
+  // can (cheby_pair.hpp: the FORM instances -- fp64 coefficient streams, one rank, variable coefficients, 10 or 12 waves) then form it instead of reading it
+  A.form_dinv = (dinv_is_rebuilt && !remote && !c32_base && variant != HPGMG_HIP_7PT_CC && nw != 16) ? 1 : 0;
   const bool interp = (interp_level != nullptr);
   if (interp) {
     const hpgmg_hip_level *C = interp_level;
@@ -226,8 +243,7 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
   // (the waves per workgroup are a template parameter of the kernel: one instance per candidate)
 #define PAIR_NW_SWITCH(...) switch (nw) { case 10: { constexpr int NWC = 10; __VA_ARGS__ } break; case 12: { constexpr int NWC = 12; __VA_ARGS__ } break; default: { constexpr int NWC = 16; __VA_ARGS__ } break; }
 #define PAIR_LAUNCH2(VAR, C32, SM, NARROW, INTERP) PAIR_NW_SWITCH( \
-      static bool once = false; if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)cheby_pair_kernel<VAR, NWC, C32, SM, NARROW, INTERP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NWC * 6 * 64 * sizeof(p2)))); once = true; } \
-      hipLaunchKernelGGL((cheby_pair_kernel<VAR, NWC, C32, SM, NARROW, INTERP>), dim3(grid), dim3(64, NWC), lds, g_stream, *L, A); )
+      { const int e_ = pair_launch<VAR, NWC, C32, SM, NARROW, INTERP>(grid, lds, L, A); if (e_) return e_; } )
 #define PAIR_LAUNCH_REMOTE_IP(VAR, SM, NRW, IP) { \
       const int ecols = 2 * (A.tiles_i - 1) + (A.rem[0] ? 1 : 0) + (A.rem[1] ? 1 : 0); \
       A.edge_blocks = ((A.Dj + 63) / 64) * A.Dk * ecols; const int egrid_r = grid_for(A.edge_blocks, &A.edge_per_xcd); \
@@ -261,15 +277,15 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
 #undef PAIR_NW_SWITCH
 #undef PAIR_LAUNCH_REMOTE
 #undef PAIR_LAUNCH_REMOTE_IP
-  if (part != 1) { g_pair_launches++; if (remote) g_pair_remote_launches++; }      // the two parts of a launch count once (part 2 is never empty: it holds the workgroups at the remote faces)
+  if (part != 1) { g_pair_launches++; if (remote) g_pair_remote_launches++; if (A.form_dinv) g_pair_formed_launches++; }      // the two parts of a launch count once (part 2 is never empty: it holds the workgroups at the remote faces)
   profile_end(prof, 2 * cells, part == 1);           // one launch = two sweeps over every cell
   HPGMG_LAUNCH_CHECK("cheby_pair_kernel");
   return 0;
 }
 int hpgmg_hip_smooth_cheby_pair(const hpgmg_hip_level *L, int variant, double *const *scr_base, const float *const *c32_base,
                                 int x0_scr, int x0_id, int xm1_scr, int xm1_id, int out1_scr, int out1_id, int out2_scr, int out2_id,
-                                int rhs_id, double a, double b, double h2inv, double c1a, double c2a, double c1b, double c2b) {
-  return smooth_pair(L, variant, 0, 0, scr_base, c32_base, x0_scr, x0_id, xm1_scr, xm1_id, out1_scr, out1_id, out2_scr, out2_id, rhs_id, a, b, h2inv, c1a, c2a, c1b, c2b);
+                                int rhs_id, double a, double b, double h2inv, double c1a, double c2a, double c1b, double c2b, int dinv_is_rebuilt) {
+  return smooth_pair(L, variant, 0, 0, scr_base, c32_base, x0_scr, x0_id, xm1_scr, xm1_id, out1_scr, out1_id, out2_scr, out2_id, rhs_id, a, b, h2inv, c1a, c2a, c1b, c2b, dinv_is_rebuilt);
 }
 void hpgmg_hip_pair_fold_interpolation(const hpgmg_hip_level *Lc, int coarse_id, double prescale) {
   g_pair_interp_level = Lc; g_pair_interp_id = coarse_id; g_pair_interp_prescale = prescale;
@@ -284,6 +300,7 @@ void hpgmg_hip_pair_discard_x1(void) { g_pair_discard_x1 = 1; }
 void hpgmg_hip_exp_timeline(void *buf) { g_exp_timeline = (double *)buf; }
 #endif
 void hpgmg_hip_pair_launch_counts(long long out[2]) { out[0] = g_pair_launches; out[1] = g_pair_remote_launches; }
+long long hpgmg_hip_pair_formed_dinv_launches(void) { return g_pair_formed_launches; }
 
 // ---- the halo of a sweep pair across rank boundaries: one pack launch, one grouped send/recv, one unpack launch ----
 static const hpgmg_hip_level *g_halo_fold_level = nullptr;      // consumed by the next pack (hpgmg_hip_pair_halo_fold_interpolation)
@@ -318,8 +335,8 @@ int hpgmg_hip_pair_halo_unpack(const hpgmg_hip_level *L, double *const *scr_base
 // few x1 values the kernel exchanges across 128-cell tile edges
 int hpgmg_hip_smooth_gsrb_pair(const hpgmg_hip_level *L, int variant, double *const *scr_base, const float *const *c32_base,
                                int x0_scr, int x0_id, int edge_scr_id, int out2_scr, int out2_id, int rhs_id,
-                               double a, double b, double h2inv, int sweep) {
-  return smooth_pair(L, variant, 1, sweep, scr_base, c32_base, x0_scr, x0_id, x0_scr, x0_id, 1, edge_scr_id, out2_scr, out2_id, rhs_id, a, b, h2inv, 0.0, 0.0, 0.0, 0.0);
+                               double a, double b, double h2inv, int sweep, int dinv_is_rebuilt) {
+  return smooth_pair(L, variant, 1, sweep, scr_base, c32_base, x0_scr, x0_id, x0_scr, x0_id, 1, edge_scr_id, out2_scr, out2_id, rhs_id, a, b, h2inv, 0.0, 0.0, 0.0, 0.0, dinv_is_rebuilt);
 }
 
 }  // extern "C"

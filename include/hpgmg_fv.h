@@ -186,6 +186,9 @@ void        hpgmg_set_brick_chains(int on);    /* 0: one launch per level visit 
 long long   hpgmg_pair_remote_smooths(void);   /* smooth() calls executed as sweep pairs with faces owned by other ranks (tests) */
 long long   hpgmg_fp32_pair_smooths(void);     /* smooth() calls run on fp32-rounded coefficients (smoother precision 32): HIP, as sweep pairs reading the fp32
                                                   copies; the CPU oracle, the same calls on rounded copies (tests) */
+void        hpgmg_set_pair_form_dinv(int on);  /* 7-pt sweep pairs: 1 = form Dinv in registers from the coefficient streams where VECTOR_DINV is known to be rebuild_operator's output for the
+                                                  same a, b (bit-identical; HPGMG_PAIR_FORM_DINV), 0 = always read the vector */
+long long   hpgmg_pair_formed_dinv_launches(void);     /* sweep-pair launches that formed Dinv so far (tests; a postponed smooth() is issued first) */
 long long   hpgmg_fused_residuals_remote(void); /* 7-point: fused residual passes (residual + restriction, residual + norm) run on levels with faces owned by other ranks (tests) */
 long long   hpgmg_fv4_rb_smooths(void);        /* fv4: smooth() calls run as one-pass red + black sweeps; hpgmg_rb27_passes(): such passes of the 27-point smoother (tests) */
 long long   hpgmg_rb27_passes(void);

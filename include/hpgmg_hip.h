@@ -215,7 +215,11 @@ int  hpgmg_hip_tile_kernel_applies(const hpgmg_hip_level *L, int variant, int ou
 int hpgmg_hip_smooth_cheby_pair_supported(const hpgmg_hip_level *L, int variant);
 int hpgmg_hip_smooth_cheby_pair(const hpgmg_hip_level *L, int variant, double *const *scr_base, const float *const *c32_base,
                                 int x0_scr, int x0_id, int xm1_scr, int xm1_id, int out1_scr, int out1_id, int out2_scr, int out2_id,
-                                int rhs_id, double a, double b, double h2inv, double c1a, double c2a, double c1b, double c2b);
+                                int rhs_id, double a, double b, double h2inv, double c1a, double c2a, double c1b, double c2b, int dinv_is_rebuilt);
+/* dinv_is_rebuilt (here and in _gsrb_pair): 1 = the caller vouches that VECTOR_DINV is what hpgmg_hip_rebuild_7pt made of the level's CURRENT coefficient vectors with
+ * exactly these a, b, h2inv.  The launch may then form Dinv per cell from the coefficient streams it reads anyway instead of reading the vector (same expression tree,
+ * same bits; one stream of ten less).  Taken by the fp64, one-rank, variable-coefficient instances of 10 and 12 waves; every other launch reads the vector as with 0. */
+long long hpgmg_hip_pair_formed_dinv_launches(void);      /* sweep-pair launches so far that formed Dinv (tests) */
 /* Sweep pairs across rank boundaries (boxes over the GPUs of a node, halo exchange over RCCL).  This rank's boxes form a
  * brick of brick_boxes[0..2] boxes (numbered lexicographically inside it); remote_face[f] (f = -i,+i,-j,+j,-k,+k) is 1 where the
  * brick face belongs to another rank, 0 where it is the (Dirichlet) domain boundary.  Before the launch the caller must have
@@ -251,7 +255,7 @@ int  hpgmg_hip_pair_halo_unpack(const hpgmg_hip_level *L, double *const *scr_bas
  * result to out2 (which must differ from x0); scratch vector edge_scr_id (0/1 behind scr_base) is clobbered. */
 int hpgmg_hip_smooth_gsrb_pair(const hpgmg_hip_level *L, int variant, double *const *scr_base, const float *const *c32_base,
                                int x0_scr, int x0_id, int edge_scr_id, int out2_scr, int out2_id, int rhs_id,
-                               double a, double b, double h2inv, int sweep);
+                               double a, double b, double h2inv, int sweep, int dinv_is_rebuilt);
 /* Fold interpolation_vcycle (interpolation_p0.c:43, f = prescale*f + parent) into the NEXT hpgmg_hip_smooth_cheby_pair /
  * _gsrb_pair launch: that launch reads its x0 as prescale*x0 + coarse parent (vector coarse_id of Lc, same box numbering,
  * boxes half the size) instead of x0 as stored, which is never materialised.  Consumed by that one launch.
