@@ -173,6 +173,13 @@ def _declare_driver_api(lib):
         # face fluxes of a solution
         "hpgmg_user_flux": (c_int, [vp, vp, vp, vp, vp, vp, c_int]),
         "hpgmg_dense_unpack_flux": (c_int, [vp, c_int, vp, c_dbl, c_int, vp, vp, vp, vp, vp, c_int]),
+        # implicit time stepping
+        "hpgmg_user_set_shift": (c_int, [vp, c_dbl]),
+        "hpgmg_user_start": (c_int, [vp, vp, vp, vp, c_int, c_dbl, c_dbl]),
+        "hpgmg_user_step": (c_int, [vp, vp, vp, c_int, c_dbl, c_dbl, c_dbl, P(UserInfo), P(c_dbl)]),
+        "hpgmg_user_get_rate": (c_int, [vp, vp, c_int]),
+        "hpgmg_step_rhs": (None, [vp, c_int, c_int, c_int, c_int, c_dbl, c_dbl]),
+        "hpgmg_step_rate": (None, [vp, c_int, c_int, c_int, c_int, c_dbl, c_dbl, P(c_dbl)]),
         # the fine-level passes of method="pcg" 
         "hpgmg_pcg_apply_dot": (c_int, [vp, c_int, c_int, c_dbl, c_dbl, P(c_dbl)]),
         "hpgmg_pcg_update": (c_int, [vp, c_int, c_int, c_int, c_int, c_dbl, P(c_dbl)]),

@@ -1,6 +1,6 @@
 /*
- * hooks_host.inc -- the portable host forms of the dense-array, boundary-value and CG hooks (include/hpgmg_operators.h hpgmg_dense_*,
- * hpgmg_boundary_*, hpgmg_pcg_*): box by box through the plugin's hpgmg_vector_upload / download.  They are weak, so that a plugin with kernels
+ * hooks_host.inc -- the portable host forms of the dense-array, boundary-value, time-march and CG hooks (include/hpgmg_operators.h hpgmg_dense_*,
+ * hpgmg_boundary_*, hpgmg_step_*, hpgmg_pcg_*): box by box through the plugin's hpgmg_vector_upload / download.  They are weak, so that a plugin with kernels
  * for them (the HIP plugin: host/plugin_dense.c, host/plugin_pcg.c; its kernels: kernels/dense_io.hip, dense_boundary.hip, dense_flux.hip, pcg.hip) replaces them while one without (the CPU oracle, whose memory is host memory
  * for either `where`) gets these.  The boundary arithmetic itself is include/hpgmg_boundary_math.h, shared with those kernels.
  * A part of host/driver.c's translation unit, included there.
@@ -10,6 +10,7 @@
 #include <math.h>
 #include "hpgmg_fv.h"
 #include "hpgmg_boundary_math.h"
+#include "hpgmg_step_math.h"
 
 /* ------------------------------------------------------------------ dense arrays <-> boxes (include/hpgmg_operators.h) */
 /* mask, wall: hpgmg_dense_pack_walls (0, NULL: hpgmg_dense_pack) */
@@ -348,6 +349,57 @@ __attribute__((weak)) int hpgmg_dense_unpack_flux(level_type *L, int x_id, const
   }
   free(u); free(gh); free(wh); free(kh);
   return bad ? HPGMG_DENSE_NOT_FINITE : 0;
+}
+
+/* ------------------------------------------------------------------ the implicit time march (include/hpgmg_operators.h; DESIGN.md §11.8)
+ * The two cell expressions of include/hpgmg_step_math.h over the interior cells, box by box; weak like the dense pair above (the HIP plugin:
+ * host/plugin_step.c).  A box goes up whole, so a vector that is only written (u_old) is downloaded first: its ghost and padding cells keep
+ * their content. */
+static double *step_boxes(const level_type *L, int n) {      /* room for n padded boxes */
+  double *v = (double *)malloc((size_t)n * (size_t)L->box_volume * sizeof(double));
+  if (!v) { fprintf(stderr, "hpgmg: time march: no memory for %d boxes of %d doubles\n", n, L->box_volume); abort(); }
+  return v;
+}
+__attribute__((weak)) void hpgmg_step_rhs(level_type *L, int F_id, int u_id, int uold_id, int w_id, double a, double c) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t vol = (size_t)L->box_volume;
+  double *v = step_boxes(L, 5), *F = v, *al = v + vol, *u = v + 2 * vol, *w = v + 3 * vol, *uold = v + 4 * vol;
+  int bx, i, j, k;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    const box_type *B = &L->my_boxes[bx];
+    hpgmg_vector_download(F, B->vectors[F_id], vol); hpgmg_vector_download(al, B->vectors[VECTOR_ALPHA], vol);
+    hpgmg_vector_download(u, B->vectors[u_id], vol); hpgmg_vector_download(w, B->vectors[w_id], vol);
+    hpgmg_vector_download(uold, B->vectors[uold_id], vol);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+      F[ijk] = step_rhs_cell(F[ijk], al[ijk], u[ijk], w[ijk], a, c);
+      uold[ijk] = u[ijk];
+    }
+    hpgmg_vector_upload(B->vectors[F_id], F, vol); hpgmg_vector_upload(B->vectors[uold_id], uold, vol);
+  }
+  free(v);
+}
+__attribute__((weak)) void hpgmg_step_rate(level_type *L, int w_id, int r_id, int u_id, int uold_id, double a, double c, double *max_abs) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t vol = (size_t)L->box_volume;
+  double *v = step_boxes(L, 5), *w = v, *al = v + vol, *r = v + 2 * vol, *u = v + 3 * vol, *uold = v + 4 * vol;
+  double best = 0.0;
+  int bx, i, j, k;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    const box_type *B = &L->my_boxes[bx];
+    hpgmg_vector_download(w, B->vectors[w_id], vol); hpgmg_vector_download(al, B->vectors[VECTOR_ALPHA], vol);
+    hpgmg_vector_download(r, B->vectors[r_id], vol); hpgmg_vector_download(u, B->vectors[u_id], vol);
+    hpgmg_vector_download(uold, B->vectors[uold_id], vol);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+      w[ijk] = step_rate_cell(r[ijk], al[ijk], u[ijk], uold[ijk], w[ijk], a, c);
+      const double f = fabs(w[ijk]);
+      if (f > best) best = f;
+    }
+    hpgmg_vector_upload(B->vectors[w_id], w, vol);
+  }
+  free(v);
+  *max_abs = best;
 }
 
 /* ------------------------------------------------------------------ the CG passes: portable forms (include/hpgmg_operators.h; DESIGN.md §11.3)

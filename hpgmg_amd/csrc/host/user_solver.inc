@@ -1,7 +1,7 @@
 /*
  * user_solver.inc -- user problems on dense arrays (include/hpgmg_fv.h hpgmg_user_*): a 7-point variable-coefficient solver whose coefficients,
  * right-hand side and boundary values come from the caller's arrays, around the hierarchy of host/mg.c.  It reaches the arrays through the
- * dense-array and boundary hooks of include/hpgmg_operators.h (host defaults: host/hooks_host.inc; HIP: host/plugin_dense.c, host/plugin_pcg.c).
+ * dense-array and boundary hooks of include/hpgmg_operators.h (host defaults: host/hooks_host.inc; HIP: host/plugin_dense.c, host/plugin_pcg.c, host/plugin_step.c).
  * DESIGN.md §11.  A part of host/driver.c's translation unit, included there.
  */
 #include <stdlib.h>
@@ -25,6 +25,9 @@ struct hpgmg_user_solver {
   int robin_mask;              /* bit f: face f is a Robin wall (a subset of mask) */
   int kappa_positive;          /* some kappa of a Robin face is > 0: six masked walls are then not singular */
   double **kappa;              /* robin_mask != 0: per level, kappa of the Robin walls (a boundary array, 0.0 on the other faces), allocated and freed with wall */
+  int march;                   /* 1: a time march is live (hpgmg_user_start; DESIGN.md §11.8): VECTOR_U holds its state u, w_id its rate w = alpha du/dt */
+  int uold_id, w_id;           /* the finest level's two vectors of a march (0 until the first hpgmg_user_start creates them) */
+  double dt, theta;            /* of the last start / step */
 };
 static int user_live = 0;              /* user solvers alive: the process-wide configuration belongs to them */
 static hpgmg_config user_cfg;
@@ -77,6 +80,22 @@ static void user_store_walls(void *ctx, mg_type *G, int l) {
   hpgmg_boundary_restrict(G->levels[l], us->wall[l], G->levels[l - 1], us->wall[l - 1]);
   hpgmg_boundary_restrict(G->levels[l], us->kappa[l], G->levels[l - 1], us->kappa[l - 1]);
   hpgmg_boundary_store_walls(G->levels[l], us->wall[l], us->kappa[l], us->mask);
+}
+
+/* every level's operator from the finest level's coefficient vectors (and wall[0], kappa[0]) with the solver's a, b: what follows the packs of
+ * set_coefficients, and all of set_shift */
+static void user_rebuild(hpgmg_user_solver *us) {
+  hpgmg_solver *s = &us->s;
+  level_type *L = &s->level_h;
+  if (us->robin_mask) {                  /* the wall's part of the diagonal depends on each level's own h (DESIGN.md §11.5) */
+    hpgmg_boundary_store_walls(L, us->wall[0], us->kappa[0], us->mask);
+    rebuild_operator(L, NULL, s->a, s->b);
+    MGRebuildCoarseWalls(&s->mg, s->a, s->b, user_store_walls, us);
+  } else {
+    rebuild_operator(L, NULL, s->a, s->b);
+    MGRebuildCoarse(&s->mg, s->a, s->b);
+  }
+  user_walls_rebuilt(us, us->robin_mask != 0);
 }
 
 static int user_create(int n, int box_dim, int bc, int mask, int robin_mask, int op, int smoother, double a, double b, double h, hpgmg_user_solver **out);
@@ -204,6 +223,7 @@ int hpgmg_user_set_coefficients_robin(hpgmg_user_solver *us, const double *alpha
   int st = 0, e;
   USER_QUIET(us);
   us->operator_ok = 0;
+  us->march = 0;
   if (us->bnd) us->rhs_ok = 0;           /* the lifted f and every phi_l were made with the old beta: a new set_rhs_dirichlet is needed */
   if (kappa) {
     if ((e = user_take_kappa(us, kappa, where)) < 0) goto refused;
@@ -218,15 +238,7 @@ int hpgmg_user_set_coefficients_robin(hpgmg_user_solver *us, const double *alpha
   if (helmholtz && (e = hpgmg_dense_pack(L, VECTOR_ALPHA, alpha, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_NONNEGATIVE)) < 0) goto refused;
   if (helmholtz) st |= e;
   if (st) { USER_LOUD(); return user_pack_status(st); }
-  if (us->robin_mask) {                  /* the wall's part of the diagonal depends on each level's own h (DESIGN.md §11.5) */
-    hpgmg_boundary_store_walls(L, us->wall[0], us->kappa[0], us->mask);
-    rebuild_operator(L, NULL, s->a, s->b);
-    MGRebuildCoarseWalls(&s->mg, s->a, s->b, user_store_walls, us);
-  } else {
-    rebuild_operator(L, NULL, s->a, s->b);
-    MGRebuildCoarse(&s->mg, s->a, s->b);
-  }
-  user_walls_rebuilt(us, us->robin_mask != 0);
+  user_rebuild(us);
   us->operator_ok = 1;
   USER_LOUD();
   return HPGMG_USER_OK;
@@ -235,10 +247,12 @@ refused:
   return HPGMG_USER_BAD_ARGUMENT;
 }
 
-int hpgmg_user_set_rhs(hpgmg_user_solver *us, const double *f, int where, double *mean_shift) {
+/* the bodies of set_rhs / set_rhs_dirichlet: a march packs its F = f + T(g) through them too, and goes on (DESIGN.md §11.8) */
+static int user_rhs_lifted(hpgmg_user_solver *us, const double *f, const double *g, int where, double *mean_shift);
+static int user_rhs_plain(hpgmg_user_solver *us, const double *f, int where, double *mean_shift) {
   level_type *L = &us->s.level_h;
   if (!f) return HPGMG_USER_BAD_ARGUMENT;
-  if (us->mask) return hpgmg_user_set_rhs_dirichlet(us, f, NULL, where, mean_shift);     /* Neumann walls: zero data on every face, the F-cycle keeps its hook */
+  if (us->mask) return user_rhs_lifted(us, f, NULL, where, mean_shift);     /* Neumann walls: zero data on every face, the F-cycle keeps its hook */
   USER_QUIET(us);
   const int st = user_pack_status(hpgmg_dense_pack(L, VECTOR_F, f, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
   us->rhs_ok = (st == HPGMG_USER_OK);
@@ -278,7 +292,16 @@ static void user_bnd_take(hpgmg_user_solver *us, double *dst, const double *g, i
   else hpgmg_vector_copy(dst, g, len);
 }
 
+int hpgmg_user_set_rhs(hpgmg_user_solver *us, const double *f, int where, double *mean_shift) {
+  us->march = 0;
+  return user_rhs_plain(us, f, where, mean_shift);
+}
 int hpgmg_user_set_rhs_dirichlet(hpgmg_user_solver *us, const double *f, const double *g, int where, double *mean_shift) {
+  us->march = 0;
+  return user_rhs_lifted(us, f, g, where, mean_shift);
+}
+
+static int user_rhs_lifted(hpgmg_user_solver *us, const double *f, const double *g, int where, double *mean_shift) {
   hpgmg_solver *s = &us->s;
   level_type *L = &s->level_h;
   int l;
@@ -333,6 +356,7 @@ int hpgmg_user_solve(hpgmg_user_solver *us, int method, double rtol, const doubl
   if (!us->operator_ok || !us->rhs_ok) return HPGMG_USER_NOT_READY;
   if (!user_config_ok()) return HPGMG_USER_CONFLICT;
   USER_QUIET(us);
+  us->march = 0;
   const int v0 = L->vcycles_from_this_level;
   double norm_of_F, r;
   if (method == HPGMG_USER_PCG || method == HPGMG_USER_FPCG) {    /* CG around the V-cycle, from u0 or from 0 (DESIGN.md §11.3, §11.4) */
@@ -441,3 +465,110 @@ int hpgmg_user_flux(hpgmg_user_solver *us, const double *u, const double *g, dou
   return st;
 }
 
+
+/* ---- implicit time stepping (DESIGN.md §11.8):  alpha du/dt = b div(beta grad u) + f  by the theta scheme.  With L(u; g) = A0 u - T(g) - a alpha u
+ * (the operator without its a alpha term), the rate w = f - L(u; g) = alpha du/dt, a = 1 / (theta dt) and c = (1 - theta) / theta one step is the solve
+ *   A0 u1 = f1 + T(g1) + a alpha u0 + c w0                                                                                      (1)
+ * and, r being the residual of (1) the solve stopped at,
+ *   w1 = r + a alpha (u1 - u0) - c w0                                                                                           (2)
+ * exactly, whatever the tolerance.  The state u (VECTOR_U), u0 (uold_id) and w (w_id) stay on the finest level in the box layout between calls. */
+static int user_theta_ok(double dt, double theta) { return isfinite(dt) && dt > 0.0 && theta >= 0.5 && theta <= 1.0 && isfinite(1.0 / (theta * dt)); }
+static int user_march_rhs(hpgmg_user_solver *us, const double *f, const double *g, int where) {      /* VECTOR_F = f + T(g), under set_rhs's rules for g */
+  return (g || us->mask) ? user_rhs_lifted(us, f, g, where, NULL) : user_rhs_plain(us, f, where, NULL);
+}
+
+int hpgmg_user_set_shift(hpgmg_user_solver *us, double a) {
+  if (!us || us->s.a == 0.0 || !isfinite(a) || !(a > 0.0)) return HPGMG_USER_BAD_ARGUMENT;      /* a Poisson solver stays one: the helmholtz flag is process-wide */
+  if (!us->operator_ok) return HPGMG_USER_NOT_READY;
+  if (!user_config_ok()) return HPGMG_USER_CONFLICT;
+  USER_QUIET(us);
+  us->s.a = a;
+  user_rebuild(us);                      /* no pack: the coefficient vectors, wall[0] and kappa[0] are the ones set_coefficients left; F and every phi_l do not depend on a */
+  USER_LOUD();
+  return HPGMG_USER_OK;
+}
+
+int hpgmg_user_start(hpgmg_user_solver *us, const double *u, const double *f, const double *g, int where, double dt, double theta) {
+  if (!us || !u || !f || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
+  hpgmg_solver *s = &us->s;
+  level_type *L = &s->level_h;
+  if (s->a == 0.0 || !user_theta_ok(dt, theta)) return HPGMG_USER_BAD_ARGUMENT;
+  if (g && us->bc != BC_DIRICHLET) return HPGMG_USER_UNSUPPORTED;
+  if (!us->operator_ok) return HPGMG_USER_NOT_READY;
+  if (!user_config_ok()) return HPGMG_USER_CONFLICT;
+  if (L->must_subtract_mean == 1) return HPGMG_USER_UNSUPPORTED;      /* alpha is 0 everywhere: there is no du/dt term to march */
+  us->march = 0;
+  USER_QUIET(us);
+  if (!us->uold_id) {                    /* the first march: two more vectors on the finest level (a solver that never starts keeps its count) */
+    us->uold_id = L->numVectors; us->w_id = L->numVectors + 1;
+    create_vectors(L, L->numVectors + 2);
+  }
+  const double a = 1.0 / (theta * dt), c = (1.0 - theta) / theta;
+  int st = user_pack_status(hpgmg_dense_pack(L, VECTOR_U, u, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
+  if (st == HPGMG_USER_OK) st = user_march_rhs(us, f, g, where);
+  if (st == HPGMG_USER_OK && a != s->a) st = hpgmg_user_set_shift(us, a);      /* after the packs: a refused array leaves the operator as it was */
+  if (st == HPGMG_USER_OK) {           /* (2) with u0 = 0, w0 = 0: w = r + a alpha u = f - L(u; g) */
+    double rate;
+    residual(L, VECTOR_TEMP, VECTOR_U, VECTOR_F, s->a, s->b);
+    zero_vector(L, us->uold_id);
+    zero_vector(L, us->w_id);
+    hpgmg_step_rate(L, us->w_id, VECTOR_TEMP, VECTOR_U, us->uold_id, s->a, c, &rate);
+    us->dt = dt; us->theta = theta;
+    us->march = 1;
+  }
+  USER_LOUD();
+  return st;
+}
+
+int hpgmg_user_step(hpgmg_user_solver *us, const double *f, const double *g, int where, double dt, double theta, double rtol, hpgmg_user_info *info,
+                    double *rate) {
+  if (!us || !f || !(rtol > 0.0) || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
+  hpgmg_solver *s = &us->s;
+  level_type *L = &s->level_h;
+  if (!us->march || !us->operator_ok) return HPGMG_USER_NOT_READY;
+  if (!(dt > 0.0)) dt = us->dt;          /* <= 0: as before */
+  if (!(theta > 0.0)) theta = us->theta;
+  if (!user_theta_ok(dt, theta)) return HPGMG_USER_BAD_ARGUMENT;
+  if (g && us->bc != BC_DIRICHLET) return HPGMG_USER_UNSUPPORTED;
+  if (!user_config_ok()) return HPGMG_USER_CONFLICT;
+  USER_QUIET(us);
+  const int st = user_march_rhs(us, f, g, where);      /* F = f + T(g), g_l and phi_l: a refusal (f or g not finite) ends here, u, w and the march intact */
+  if (st != HPGMG_USER_OK) { USER_LOUD(); return st; }
+  const double a = 1.0 / (theta * dt), c = (1.0 - theta) / theta;
+  if (a != s->a) {                       /* w does not depend on a: it stays valid across the change */
+    const int e = hpgmg_user_set_shift(us, a);
+    if (e != HPGMG_USER_OK) { USER_LOUD(); return e; }
+  }
+  us->dt = dt; us->theta = theta;
+  const int v0 = L->vcycles_from_this_level;
+  double w_max;
+  hpgmg_step_rhs(L, VECTOR_F, VECTOR_U, us->uold_id, us->w_id, s->a, c);      /* (1)'s right-hand side; u_old = u */
+  us->rhs_ok = 0;                        /* VECTOR_F is no longer the caller's f + T(g): a solve needs its own set_rhs */
+  /* the warm start of hpgmg_user_solve from the state the library holds: u = u_old + e with A e = F - A u_old */
+  residual(L, us->x_id, VECTOR_U, VECTOR_F, s->a, s->b);
+  const double norm_of_F = norm(L, VECTOR_F), norm_of_r0 = norm(L, us->x_id);
+  if (norm_of_r0 > 0.0) {
+    MGSolve(&s->mg, 0, VECTOR_U, us->x_id, s->a, s->b, rtol * norm_of_F / norm_of_r0);
+    add_vectors(L, VECTOR_U, 1.0, VECTOR_U, 1.0, us->uold_id);
+  }
+  residual(L, VECTOR_TEMP, VECTOR_U, VECTOR_F, s->a, s->b);
+  const double r = norm(L, VECTOR_TEMP);
+  hpgmg_step_rate(L, us->w_id, VECTOR_TEMP, VECTOR_U, us->uold_id, s->a, c, &w_max);      /* (2) */
+  USER_LOUD();
+  if (info) {
+    info->norm_of_residual = r; info->norm_of_f = norm_of_F; info->mean_shift = 0.0;
+    info->vcycles = L->vcycles_from_this_level - v0;
+    info->converged = (r == 0.0) || (r < rtol * norm_of_F);
+  }
+  if (rate) *rate = w_max;
+  return HPGMG_USER_OK;
+}
+
+int hpgmg_user_get_rate(hpgmg_user_solver *us, double *out, int where) {
+  if (!us || !out) return HPGMG_USER_BAD_ARGUMENT;
+  if (!us->march) return HPGMG_USER_NOT_READY;
+  USER_QUIET(us);
+  const int st = hpgmg_dense_unpack(&us->s.level_h, us->w_id, out, where);
+  USER_LOUD();
+  return st < 0 ? HPGMG_USER_BAD_ARGUMENT : HPGMG_USER_OK;
+}

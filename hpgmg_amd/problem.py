@@ -38,6 +38,15 @@ density -- in the shapes of beta_i, beta_j, beta_k and positive towards increasi
 kappa, so that cell by cell  a alpha u + (1/h) sum_d (q_d[high face] - q_d[low face])  is apply(u, boundary=g).  wall_flux(fluxes) is the
 (6,N,N) OUTWARD flux through the walls in `boundary`'s layout; h^2 times its sum is what leaves the box.  DESIGN.md §11.6.
 
+Time stepping: start(u, f, boundary=g, dt=..., theta=1.0) begins a march of  alpha du/dt = b div(beta grad u) + f  by the theta scheme
+alpha (u1 - u0) / dt = theta w1 + (1 - theta) w0,  w = alpha du/dt  (theta = 1: backward Euler, 0.5: Crank-Nicolson; 0.5 <= theta <= 1), on a
+solver created with a != 0: one step is one solve with a = 1 / (theta dt), which the march sets (set_shift(a) does so by hand: every level's
+diagonal is rebuilt, no coefficient array is packed).  step(f, boundary=g) advances to the next time, f and g being those of that time, with
+V-cycles warm-started from the state; dt= / theta= change the step.  The state u and the rate w stay in the library, on the device, between
+calls: get_solution() and rate() return them, StepInfo.rate is max |w| and StepInfo.t the time since start().  The rate is exact for the state
+the solve stopped at, whatever rtol.  set_coefficients, set_rhs and solve end a march; get_solution, rate, apply, flux and set_shift do not.
+DESIGN.md §11.8.
+
 NumPy arrays take the host path.  torch tensors on the library's GPU (float64, contiguous) are read and written in place, and results come
 back as tensors on that device.  torch must be imported before this package loads its libraries: both bring a HIP runtime
 (libamdhip64.so.7), and a device pointer is only valid inside the runtime that made it.  The C entry points are hpgmg_user_* of
@@ -69,6 +78,13 @@ class SolveInfo:
     vcycles: int         # V-cycles run from the finest level (an F-cycle ends with one; methods "pcg" and "fpcg": one per iteration)
     converged: bool      # residual < rtol * norm_f
     mean_shift: float    # subtracted from f (periodic without an a alpha term), else 0.0
+
+
+@dataclass
+class StepInfo(SolveInfo):
+    """Of one time step (Solver.step): SolveInfo of the step's solve, whose right-hand side is f + T(g) + a alpha u0 + c w0."""
+    rate: float          # max |alpha du/dt| at the new time
+    t: float             # time since start()
 
 
 def hip_runtimes_mapped():
@@ -124,6 +140,8 @@ class Solver:
         self.h = float(h) if h is not None and h > 0 else 1.0 / self.n
         self.robin_faces = tuple(f for f in range(6) if faces is not None and faces[f] == "convective")
         self._ptr = None
+        self._dt = self._theta = None       # of the last start() / step()
+        self._t = 0.0                       # time since start()
         out = ctypes.c_void_p()
         if faces is None:
             st = self.lib.hpgmg_user_create(self.n, int(box_dim or 0), _BC[bc], _OPERATOR[operator], _SMOOTHER[smoother], self.a, self.b,
@@ -407,6 +425,85 @@ class Solver:
             named = [("u", u, 0.0, False)] + ([("boundary", boundary, 0.0, False)] if boundary is not None else [])
             self._check(st, self._first_bad(named, st))
         self._check(st, "u, boundary" if boundary is not None else "u")
+        return out
+
+    # ---- implicit time stepping (module docstring)
+    def set_shift(self, a):
+        """A new a (> 0) for a Helmholtz solver: every level's operator is rebuilt from the coefficients already set, without packing an array.
+        Afterwards the solver is, bit for bit, one created with that a and given the same coefficients."""
+        if self.a == 0.0:
+            raise ValueError("a: this solver is Poisson (a = 0) and stays so (create it with a != 0)")
+        if isinstance(a, bool) or not isinstance(a, (int, float, np.integer, np.floating)) or not np.isfinite(a) or not a > 0.0:
+            raise ValueError(f"a: {a!r} must be a finite number > 0")
+        self._check(self.lib.hpgmg_user_set_shift(self._ptr, float(a)), "a")
+        self.a = float(a)
+
+    def _march_args(self, dt, theta):
+        if self.a == 0.0:
+            raise ValueError("a: time stepping needs a Helmholtz solver (create it with a != 0 and set alpha; a is then set from dt and theta)")
+        for name, v in (("dt", dt), ("theta", theta)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+                raise ValueError(f"{name}: {v!r} must be a finite number")
+        if not dt > 0.0:
+            raise ValueError(f"dt: {dt!r} must be > 0")
+        if not 0.5 <= theta <= 1.0:
+            raise ValueError(f"theta: {theta!r} must lie in [0.5, 1] (1: backward Euler, 0.5: Crank-Nicolson)")
+        return float(dt), float(theta)
+
+    def start(self, u, f, boundary=None, dt=None, theta=1.0):
+        """Begins a march of  alpha du/dt = b div(beta grad u) + f  at the state u, with the source f and the wall data `boundary` of that time
+        (as set_rhs takes them).  Sets a = 1 / (theta dt) and the rate w = alpha du/dt = f - L(u; boundary).  theta = 1: backward Euler,
+        0.5: Crank-Nicolson.  The state and the rate stay in the library; step() advances them, get_solution() and rate() return them."""
+        if dt is None:
+            raise ValueError("dt: required (the time step, > 0)")
+        dt, theta = self._march_args(dt, theta)
+        pu, where, kind = self._arg(u, (self.n,) * 3, "u")
+        pf = self._arg(f, (self.n,) * 3, "f", kind)[0]
+        pg = self._boundary(boundary, kind) if boundary is not None else None
+        self._sync_torch(kind)
+        st = self.lib.hpgmg_user_start(self._ptr, pu, pf, pg, where, dt, theta)
+        if st == H.USER_NOT_FINITE:
+            named = [("u", u, 0.0, False), ("f", f, 0.0, False)] + ([("boundary", boundary, 0.0, False)] if boundary is not None else [])
+            self._check(st, self._first_bad(named, st))
+        if st == H.USER_UNSUPPORTED:
+            raise ValueError("alpha: zero everywhere, so there is no du/dt term to march")
+        self._check(st, "u, f, boundary, dt or theta")
+        self.a, self._dt, self._theta, self._t = 1.0 / (theta * dt), dt, theta, 0.0
+
+    def step(self, f, boundary=None, dt=None, theta=None, rtol=1e-8):
+        """One theta step to the next time; f and `boundary` are those of the NEW time.  dt, theta None: as in the call before (a change rebuilds
+        the operator's diagonals, nothing else).  V-cycles from the state run until the residual of the step's equation is below rtol times its
+        right-hand side (20 at most).  Returns StepInfo: SolveInfo's fields for that solve, rate = max |alpha du/dt| at the new time and t, the
+        time since start().  The rate is exact for the state the solve stopped at, whatever rtol."""
+        if self._dt is None:
+            raise ValueError("step: no march is live (start() begins one; set_coefficients, set_rhs and solve end it)")
+        if not rtol > 0.0:
+            raise ValueError(f"rtol: {rtol!r} must be > 0")
+        dt, theta = self._march_args(self._dt if dt is None else dt, self._theta if theta is None else theta)
+        pf, where, kind = self._arg(f, (self.n,) * 3, "f")
+        pg = self._boundary(boundary, kind) if boundary is not None else None
+        self._sync_torch(kind)
+        info, rate = H.UserInfo(), ctypes.c_double(0.0)
+        st = self.lib.hpgmg_user_step(self._ptr, pf, pg, where, dt, theta, float(rtol), ctypes.byref(info), ctypes.byref(rate))
+        if st == H.USER_NOT_FINITE:
+            named = [("f", f, 0.0, False)] + ([("boundary", boundary, 0.0, False)] if boundary is not None else [])
+            self._check(st, self._first_bad(named, st))
+        if st == H.USER_NOT_READY:
+            raise ValueError("step: no march is live (start() begins one; set_coefficients, set_rhs and solve end it)")
+        self._check(st, "f, boundary, dt or theta")
+        self.a, self._dt, self._theta, self._t = 1.0 / (theta * dt), dt, theta, self._t + dt
+        return StepInfo(info.norm_of_residual, info.norm_of_f, info.vcycles, bool(info.converged), info.mean_shift, rate.value, self._t)
+
+    def rate(self, out=None):
+        """The rate w = alpha du/dt of the march's state into `out` (NumPy array or tensor), or a new NumPy array."""
+        if out is None:
+            out = np.empty((self.n,) * 3, dtype=np.float64)
+        p, where, kind = self._arg(out, (self.n,) * 3, "out")
+        self._sync_torch(kind)
+        st = self.lib.hpgmg_user_get_rate(self._ptr, p, where)
+        if st == H.USER_NOT_READY:
+            raise ValueError("rate: no march is live (start() begins one; set_coefficients, set_rhs and solve end it)")
+        self._check(st, "out")
         return out
 
     def wall_flux(self, fluxes):

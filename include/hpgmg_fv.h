@@ -133,6 +133,29 @@ int  hpgmg_user_set_coefficients_robin(hpgmg_user_solver *s, const double *alpha
  * HPGMG_USER_UNSUPPORTED).  u or a g entry not finite: HPGMG_USER_NOT_FINITE; after a refused set_coefficients: HPGMG_USER_NOT_READY.  Only the
  * solver's operand vector (apply's) is written: the solution, the right-hand side and the state of the last set_rhs stay as they were. */
 int  hpgmg_user_flux(hpgmg_user_solver *s, const double *u, const double *g, double *flux_i, double *flux_j, double *flux_k, int where);
+/* Implicit time stepping:  alpha du/dt = b div(beta grad u) + f  with the walls and data g of the solver, by the theta scheme
+ *   alpha (u1 - u0) / dt = theta w1 + (1 - theta) w0,   w = f - L(u; g) = alpha du/dt,   L(u; g) = apply_dirichlet(u, g) - a alpha u,
+ * 1/2 <= theta <= 1 (1: backward Euler, 1/2: Crank-Nicolson).  One step is one solve with the operator for a = 1 / (theta dt).  The library keeps the
+ * state u and the rate w on the device between calls; only f (and g) come in per step.
+ * set_shift: a new a (> 0, finite) for a solver created with a != 0 (else HPGMG_USER_BAD_ARGUMENT): every level's operator is rebuilt from the
+ *   coefficients set_coefficients left, without packing one; then as a solver created with that a and given the same coefficients, bit for bit.
+ *   A right-hand side set before stays valid.
+ * start: begins a march at u with the source f and data g of that time (g NULL as set_rhs allows it), sets a = 1 / (theta dt) and w = f - L(u; g).
+ *   dt <= 0, theta outside [1/2, 1], a Poisson solver: HPGMG_USER_BAD_ARGUMENT; alpha zero everywhere: HPGMG_USER_UNSUPPORTED.  The first start gives
+ *   the finest level two more vectors.  A start ends the march before it, also when it is refused (the state vector is packed first): after a
+ *   refused start there is no march until one succeeds.
+ * step: one step to the next time, f and g being those of the NEW time; dt, theta <= 0: as in the call before (a change sets the shift; w stays
+ *   valid).  V-cycles from the state run until |F - A u| < rtol |F| (20 at most), F the right-hand side f + T(g) + a alpha u0 + c w0, c = (1 - theta) / theta;
+ *   info as hpgmg_user_solve fills it (norm_of_f = |F|), *rate = max |w|.  w is exact for the u the solve stopped at, whatever rtol.  f or g not finite:
+ *   HPGMG_USER_NOT_FINITE, and u, w and the march are as before the call.  Without a live march: HPGMG_USER_NOT_READY.
+ * get_rate: w into an (N,N,N) array.  get_solution returns the state u.
+ * set_coefficients*, set_rhs* and solve end a march (step: HPGMG_USER_NOT_READY until the next start); get_solution, apply*, flux and set_shift do
+ * not.  After a step the solver holds no right-hand side of the caller's: solve needs a set_rhs first. */
+int  hpgmg_user_set_shift(hpgmg_user_solver *s, double a);
+int  hpgmg_user_start(hpgmg_user_solver *s, const double *u, const double *f, const double *g, int where, double dt, double theta);
+int  hpgmg_user_step(hpgmg_user_solver *s, const double *f, const double *g, int where, double dt, double theta, double rtol, hpgmg_user_info *info,
+                     double *rate);
+int  hpgmg_user_get_rate(hpgmg_user_solver *s, double *out, int where);
 
 /* ---- small accessors so a ctypes caller never needs the struct layouts ---- */
 enum { HPGMG_INFO_DIM = 0, HPGMG_INFO_BOX_DIM, HPGMG_INFO_GHOSTS, HPGMG_INFO_JSTRIDE, HPGMG_INFO_KSTRIDE,

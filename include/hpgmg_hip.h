@@ -401,6 +401,12 @@ int hpgmg_hip_boundary_interp_robin(const hpgmg_hip_level *L, int id, const hpgm
  * synchronises. */
 int hpgmg_hip_dense_unpack_flux(const hpgmg_hip_level *L, int id, const double *g, double b, double wq, double h, int mask, const double *wall,
                                 const double *kappa, double *flux_i, double *flux_j, double *flux_k, int *status);
+/* the two passes of the implicit time march (include/hpgmg_operators.h hpgmg_step_rhs / hpgmg_step_rate; kernels/dense_step.hip), one
+ * launch each over the interior cells of every box; num_vectors: the vectors a box of the level holds (the ids and VECTOR_ALPHA are checked against
+ * it).  step_rhs: F = F + ((a alpha) u + c w), u_old = u.  step_rate: w = (r + (a alpha) (u - u_old)) - c w, and *max_abs = max |w| (0.0 <= it; a
+ * NaN is skipped), folded by a second tiny launch and waited for. */
+int hpgmg_hip_step_rhs(const hpgmg_hip_level *L, int num_vectors, int F_id, int u_id, int uold_id, int w_id, double a, double c);
+int hpgmg_hip_step_rate(const hpgmg_hip_level *L, int num_vectors, int w_id, int r_id, int u_id, int uold_id, double a, double c, double *max_abs);
 
 /* ---- operators/rebuild.c:47-208 black-box rebuild: accumulate one colouring (x = 0/1 pattern, ghosts
  *      already exchanged / BCs applied) into Aii and sum|Aij|, then turn them into Dinv, L1inv, lambda_max ---- */

@@ -203,6 +203,15 @@ void    hpgmg_boundary_interp_robin(level_type *fine, int id, level_type *coarse
  * plugin overrides it with one launch for the three arrays (kernels/dense_flux.hip). */
 int     hpgmg_dense_unpack_flux(level_type *level, int x_id, const double *g, double b, int mask, const double *wall, const double *kappa,
                                 double *flux_i, double *flux_j, double *flux_k, int where);
+/* The two streaming passes of the implicit time march of the user-problem API (hpgmg_user_start / hpgmg_user_step, include/hpgmg_fv.h)
+ * over the interior cells of every box of a Helmholtz level (alpha = VECTOR_ALPHA); ghost and padding cells are neither read nor written:
+ *   step_rhs:   F = F + ((a * alpha) * u + c * w) ;  u_old = u              (F holds f + T(g) on entry; a = 1 / (theta dt), c = (1 - theta) / theta)
+ *   step_rate:  w = (r + (a * alpha) * (u - u_old)) - c * w ;  *max_abs = max |w| over the level (0.0 <= it; a NaN never becomes the maximum)
+ * in exactly that written order (include/hpgmg_step_math.h, which the host defaults and the kernels both compile).  The ids are distinct vectors of
+ * the level.  Weak host defaults in host/hooks_host.inc (box by box: the CPU oracle); the HIP plugin overrides them with one launch each
+ * (host/plugin_step.c, kernels/dense_step.hip). */
+void    hpgmg_step_rhs(level_type *level, int F_id, int u_id, int uold_id, int w_id, double a, double c);
+void    hpgmg_step_rate(level_type *level, int w_id, int r_id, int u_id, int uold_id, double a, double c, double *max_abs);
 /* The fine-level passes of the V-cycle-preconditioned CG of the user-problem API (MGPCGSolve, include/hpgmg_mg.h), 7-point operator:
  *   pcg_apply_dot: Ap = A p exactly as apply_op(level, Ap_id, p_id, a, b) leaves it (its ghost exchange and boundary conditions), and *dot = p . Ap
  *   pcg_update:    per interior cell  x = x + alpha * p ;  r = r - alpha * Ap  (the product first, then the sum / difference), *rmax = max |r| (0.0 <= it)

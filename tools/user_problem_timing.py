@@ -4,6 +4,12 @@ Chebyshev, 2^3 boxes of 128^3): set_coefficients, set_rhs, solve (one F-cycle) a
 one pack and one unpack launch alone.  hipEvent pairs on the library's launch stream around each call; every call synchronises before it
 returns, so the pair brackets all of its device work.  Prints one JSON line of medians in ms.
 
+The time march, device arrays only: one step() of a backward-Euler and of a Crank-Nicolson march; the only route to the
+backward-Euler update without a march -- a torch-formed right-hand side a alpha u + f, then solve(rhs, u0=u) into u, from the same state (skipped
+without torch).  These three are timed alike, with the host clock between device synchronisations, since torch works on a stream of its own.  Then
+the two passes of kernels/dense_step.hip alone (hook calls in a row between an event pair: step_rate's figure includes its fold launch and the
+host's wait for the value) as ms and as 48 B per cell per second; set_shift.
+
     python tools/user_problem_timing.py [--n 256] [--repeats 5]
 """
 import argparse
@@ -12,8 +18,14 @@ import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
+
+try:                      # before the project's libraries load: one HIP runtime per process (hpgmg_amd/problem.py)
+    import torch
+except ImportError:
+    torch = None
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hpgmg_amd as H  # noqa: E402
@@ -70,11 +82,72 @@ def main():
             res[f"pack_one_field_{where}_ms"] = timed(lambda: lib.hpgmg_dense_pack(L, H.VECTOR_F, F, w, H.DENSE_CELL, H.DENSE_CHECK_FINITE))
             res[f"unpack_one_field_{where}_ms"] = timed(lambda: lib.hpgmg_dense_unpack(L, H.VECTOR_U, U, w))
         res["fmg_residual"] = "%1.15e" % info.norm_of_residual
+        march_timing(args, lib, K, s, res, timed, d_f, d_u, f, alpha)
     for p in dev:
         K.hpgmg_hip_free(p)
     K.hpgmg_hip_event_destroy(e0)
     K.hpgmg_hip_event_destroy(e1)
     print(json.dumps(res))
+
+
+def march_timing(args, lib, K, s, res, timed, d_f, d_u, f, alpha):
+    """The time march on the solver whose coefficients are set from device arrays (module docstring)."""
+    n, S, W = s.n, s._ptr, H.WHERE_PLUGIN
+    dt, rtol = 1e-3, 1e-6
+    L = lib.hpgmg_solver_level(lib.hpgmg_user_solver_of(S), 0)
+    info, rate = H.UserInfo(), ctypes.c_double()
+    assert K.hpgmg_hip_memcpy_h2d(d_u, f.ctypes.data, f.nbytes) == 0                      # the state to start from: any finite field
+    res["step_rtol"], res["step_dt"] = rtol, dt
+    for theta in (0.5, 1.0):               # theta = 1 (backward Euler) last: the one update the route without a march can also make
+        assert lib.hpgmg_user_start(S, d_u, d_f, None, W, dt, theta) == H.USER_OK
+        out, cycles = [], []
+        for _ in range(args.repeats + 1):                                                   # the first is the warm-up
+            K.hpgmg_hip_sync()
+            t0 = time.perf_counter()
+            assert lib.hpgmg_user_step(S, d_f, None, W, 0.0, 0.0, rtol, ctypes.byref(info), ctypes.byref(rate)) == H.USER_OK
+            K.hpgmg_hip_sync()
+            out.append((time.perf_counter() - t0) * 1e3)
+            cycles.append(info.vcycles)
+        res[f"step_theta_{theta}_ms"] = statistics.median(out[1:])
+        res[f"step_theta_{theta}_vcycles"] = cycles[1:]
+    # the two passes alone, on the march's own vectors (their values do not matter to the time)
+    nv = (ctypes.c_int * H.INFO_COUNT)()
+    lib.hpgmg_level_info(L, nv)
+    uold_id, w_id, calls = nv[H.INFO_NUM_VECTORS] - 2, nv[H.INFO_NUM_VECTORS] - 1, 20
+    a, c = 1.0 / (theta * dt), (1.0 - theta) / theta
+
+    def rhs_calls():
+        for _ in range(calls):
+            lib.hpgmg_step_rhs(L, H.VECTOR_F, H.VECTOR_U, uold_id, w_id, a, 0.0)
+        K.hpgmg_hip_sync()
+
+    def rate_calls():
+        for _ in range(calls):
+            lib.hpgmg_step_rate(L, w_id, H.VECTOR_TEMP, H.VECTOR_U, uold_id, a, c, ctypes.byref(rate))
+    for name, fn in (("step_rhs", rhs_calls), ("step_rate", rate_calls)):
+        fn()
+        ms = timed(fn) / calls
+        res[f"{name}_call_ms"] = ms
+        res[f"{name}_TB_per_s"] = 48.0 * n ** 3 / (ms * 1e-3) / 1e12
+    shifts = iter(range(1, 1000))
+    res["set_shift_ms"] = timed(lambda: lib.hpgmg_user_set_shift(S, a + next(shifts)))
+    if torch is None:
+        res["torch_route_ms"] = None
+        return
+    dev = torch.device("cuda", torch.cuda.current_device())
+    t_alpha, t_f, t_u = torch.from_numpy(alpha).to(dev), torch.from_numpy(f).to(dev), torch.from_numpy(f).to(dev)
+    s.set_shift(1.0 / dt)
+    out, cycles = [], []
+    for _ in range(args.repeats + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rhs = s.a * t_alpha * t_u + t_f
+        _, i = s.solve(rhs, rtol=rtol, u0=t_u, out=t_u)
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+        cycles.append(i.vcycles)
+    res["torch_route_ms"] = statistics.median(out[1:])
+    res["torch_route_vcycles"] = cycles[1:]
 
 
 if __name__ == "__main__":
