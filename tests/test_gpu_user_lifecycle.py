@@ -6,6 +6,7 @@ to a fresh solver per step.  What lives across calls on the HIP side only, and w
   fp32 coefficient copies (plugin_smooth.c coef32_of)                      test_sweep_pair_level_*: 128^3 in boxes of 64, the smallest sweep-pair level
   packed edge coefficients of the sweep-pair pre-pass (pair.hip EdgePack)  test_packed_edge_coefficients_*: 256^3 in boxes of 128 (two 128-cell i tiles)
   staging buffer, lazy queue, one-shot statics, two live solvers           test_reused_solver_*, test_two_live_solvers_*
+  all of these across the first start()'s new storage of the finest level  test_a_marching_solver_*, test_packed_edge_coefficients_across_the_storage_*
 
 Every comparison is bitwise.  The switches are the library's own setters; the fixture puts them back (graphs 0, precision 64, fused sweeps 1).
 """
@@ -17,8 +18,8 @@ import pytest
 import hpgmg_amd as H
 from hpgmg_testlib import Backend
 from test_gpu_user_problem import DeviceArrays
-from user_lifecycle_lib import (PAIR, SPECS, Player, assert_same, coefficients, differences, doubled, interleave, refused_then_recovered, run,
-                                sequence, spec_id)
+from user_lifecycle_lib import (MARCH_DT, MARCH_RTOL, MARCH_THETA, PAIR, SPECS, Player, assert_same, coefficients, differences, doubled, interleave,
+                                issued_thrice, march_sequence, refused_then_recovered, run, sequence, spec_id)
 
 pytestmark = pytest.mark.gpu
 
@@ -315,3 +316,61 @@ def test_a_refused_set_coefficients_is_recovered_from(libs, switches, graphs):
     switches.graphs(graphs)
     got, fresh = refused_then_recovered(hip, SPECS[0])
     assert not differences(got, want) and not differences(fresh, want)
+
+
+# ---------------------------------------------------------------- time marches in the lifecycle
+@pytest.mark.parametrize("graphs", [0, 1])
+@pytest.mark.parametrize("k", range(len(PAIR)), ids=[spec_id(s) for s in PAIR])
+def test_a_marching_solver_equals_the_oracle_at_every_step(libs, switches, device, k, graphs):
+    """user_lifecycle_lib.march_sequence on one live HIP solver.  Its first start() comes after a solve and gives the finest level new storage
+    and a new device box table, under everything the solve left: halo images, the Dinv record and, with graphs on, segments captured and
+    replayed over the old storage (every solve is issued three times, every march step followed by two more)."""
+    hip, oracle, _ = libs
+    spec, steps = PAIR[k], march_sequence(PAIR[k])
+    if graphs:
+        steps, of = issued_thrice(steps)
+    stats = [switches.graph_stats()]
+    switches.graphs(graphs)
+    got = run(hip, spec, steps, *_entry(k + graphs, device), after=lambda i, step, out: stats.append(switches.graph_stats()))
+    switches.graphs(0)
+    assert_same(got, run(oracle, spec, steps), spec_id(spec))
+    first = [s[0] for s in steps].index("start")              # stats[i]: before step i
+    if graphs:
+        assert stats[first][1] > stats[0][1] and stats[first][2] > stats[0][2], "nothing was captured and replayed before the first start"
+        assert stats[-1][2] > stats[first + 1][2], "nothing was replayed after the first start"
+    else:
+        assert stats[-1][1:] == stats[0][1:]
+
+
+@pytest.mark.parametrize("graphs", [0, 1])
+def test_a_marching_solver_interleaved_with_another_equals_the_oracle(libs, switches, device, graphs):
+    """Two live solvers, one of which marches: its new storage and its set_shift rebuilds come between the other's solves."""
+    hip, oracle, _ = libs
+    sequences = [march_sequence(PAIR[0]), sequence(oracle, PAIR[1])] if graphs == 0 else [sequence(oracle, PAIR[0]), march_sequence(PAIR[1])]
+    ref = [run(oracle, spec, steps) for spec, steps in zip(PAIR, sequences)]
+    switches.graphs(graphs)
+    entry = ("host", None) if graphs else ("device", [device(), device()])
+    for spec, got, want in zip(PAIR, interleave(hip, PAIR, sequences, *entry), ref):
+        assert_same(got, want, spec_id(spec))
+
+
+def test_packed_edge_coefficients_across_the_storage_of_a_first_start(libs, switches, packed):
+    """Solver A (Helmholtz) makes its packs in a solve, then start() gives its finest level new storage and a new box table, the key of the
+    packs; A steps once and is closed.  Solver B (the fixture's) then gives what it gave.  (By reading: if the new table gets the old address the
+    entry is found again and set_shift's rebuild re-packs it; if not it is left behind under the old key, where a later table can meet it only
+    after its own rebuild_operator has invalidated that key -- stale values are never read, the buffer stays allocated.)"""
+    hip = libs[0]
+    spec_a = PACKED[:4] + (1.0,)
+    n = spec_a[0]
+    rng = np.random.default_rng(259)
+    u0, f2 = rng.random((n, n, n)) * 2.0 - 1.0, rng.random((n, n, n)) * 4.0 - 2.0
+    fmg = ("solve", packed["f"], "fmg", {})
+    pairs = {}
+    before, after = _count_pairs(switches, pairs)
+    a_steps = [("coef", coefficients(spec_a, 257)), fmg, ("start", u0, packed["f"], None, MARCH_DT, MARCH_THETA), ("step", f2, None, None, None, MARCH_RTOL)]
+    got_a = run(hip, spec_a, a_steps, before=before, after=after)
+    assert pairs[1] > 0 and pairs[3] > 0, pairs
+    assert got_a[3]["converged"] and got_a[3]["rate"] == abs(got_a[3]["w"]).max() > 0.0
+    got_b = run(hip, PACKED, [("coef", packed["c2"]), fmg], before=before, after=after)
+    assert pairs[1] > 0, pairs
+    assert got_b[1]["u"].tobytes() == packed["u_ref"].tobytes()

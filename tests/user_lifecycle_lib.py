@@ -7,6 +7,9 @@ A spec is (n, box_dim, bc, smoother, a).  A sequence is a list of steps:
     ("apply", x, g)                                         g: boundary data or None
     ("flux", u, g)
     ("close_reopen",)                                       close the solver and create one of the same spec (a "coef" step follows)
+    ("start", u0, f, g, dt, theta)                          begin a time march; g: boundary data or None
+    ("step", f, g, dt, theta, rtol)                         one step of it; dt, theta None: as before.  Outputs u, the rate array w, the info, rate
+    ("shift", a)                                            set_shift
 Every array of a step is a concrete NumPy array, so a step means the same on any library and on a fresh solver.  Only bits are compared, so the
 coefficients are plain rng.random fields (beta in [0.5, 3], alpha in [0.5, 1.5]): nothing here needs a solve to converge.
 """
@@ -62,9 +65,10 @@ def doubled(coef):
     return (coef[0],) + tuple(2.0 * c for c in coef[1:])
 
 
-def new_solver(lib, spec):
-    n, box_dim, bc, smoother, a = spec
-    return Solver(n, box_dim=box_dim, bc=bc, smoother=smoother, a=a, b=1.0, lib=lib)
+def new_solver(lib, spec, a=None):
+    """a: another a than the spec's (a fresh solver for one that marched or had set_shift)"""
+    n, box_dim, bc, smoother, a0 = spec
+    return Solver(n, box_dim=box_dim, bc=bc, smoother=smoother, a=a0 if a is None else a, b=1.0, lib=lib)
 
 
 class _DeviceBuffers:
@@ -95,11 +99,11 @@ class Player:
     """One live Solver that plays steps.  entry "host": NumPy arrays through the Solver's methods; "device": device memory through the C entry
     points (device = a DeviceArrays)."""
 
-    def __init__(self, lib, spec, entry="host", device=None):
+    def __init__(self, lib, spec, entry="host", device=None, a=None):
         assert entry in ("host", "device") and (entry == "host" or device is not None)
         self.lib, self.spec, self.entry = lib, spec, entry
         self.buf = _DeviceBuffers(device) if entry == "device" else None
-        self.s = new_solver(lib, spec)
+        self.s = new_solver(lib, spec, a)
 
     def close(self):
         self.s.close()
@@ -126,6 +130,18 @@ class Player:
 
     def _flux_host(self, u, g):
         return dict(zip(("qi", "qj", "qk"), self.s.flux(u, boundary=g)))
+
+    def _start_host(self, u0, f, g, dt, theta):
+        self.s.start(u0, f, boundary=g, dt=dt, theta=theta)
+        return {}
+
+    def _step_host(self, f, g, dt, theta, rtol):
+        info = self.s.step(f, boundary=g, dt=dt, theta=theta, rtol=rtol)
+        return dict(u=self.s.get_solution(), w=self.s.rate(), rate=info.rate, **{k: getattr(info, k) for k in INFO})
+
+    def _shift_host(self, a):
+        self.s.set_shift(a)
+        return {}
 
     # ---- device: the C entry points on device memory
     def _coef_device(self, coef, robin=None):
@@ -167,11 +183,30 @@ class Player:
         assert self.lib.hpgmg_user_flux(self.s._ptr, self.buf.put("x", u), self.buf.put("g", g), *po, H.WHERE_PLUGIN) == 0
         return {name: self.buf.get(name, shape) for name, shape in zip(("qi", "qj", "qk"), shapes)}
 
+    def _start_device(self, u0, f, g, dt, theta):
+        p = [self.buf.put(name, v) for name, v in (("u0", u0), ("f", f), ("g", g))]
+        assert self.lib.hpgmg_user_start(self.s._ptr, *p, H.WHERE_PLUGIN, dt, theta) == 0
+        return {}
 
-def run(lib, spec, steps, entry="host", device=None, before=None, after=None):
+    def _step_device(self, f, g, dt, theta, rtol):
+        lib, S, w = self.lib, self.s._ptr, H.WHERE_PLUGIN
+        info, rate = H.UserInfo(), ctypes.c_double(-1.0)
+        assert lib.hpgmg_user_step(S, self.buf.put("f", f), self.buf.put("g", g), w, dt or 0.0, theta or 0.0, rtol, ctypes.byref(info),
+                                   ctypes.byref(rate)) == 0                      # 0: as before
+        assert lib.hpgmg_user_get_solution(S, self.buf.out("u", f.nbytes), w) == 0
+        assert lib.hpgmg_user_get_rate(S, self.buf.out("w", f.nbytes), w) == 0
+        return dict(u=self.buf.get("u", f.shape), w=self.buf.get("w", f.shape), rate=rate.value, residual=info.norm_of_residual,
+                    norm_f=info.norm_of_f, vcycles=info.vcycles, converged=bool(info.converged), mean_shift=info.mean_shift)
+
+    def _shift_device(self, a):
+        assert self.lib.hpgmg_user_set_shift(self.s._ptr, a) == 0
+        return {}
+
+
+def run(lib, spec, steps, entry="host", device=None, before=None, after=None, a=None):
     """Plays `steps` on one Solver; returns every step's outputs (a dict of arrays and of the SolveInfo fields; {} for a step without any).
-    before(i, step) / after(i, step, out): called around step i (switches, counters)."""
-    p = Player(lib, spec, entry, device)
+    before(i, step) / after(i, step, out): called around step i (switches, counters).  a: the solver is created with this a, not the spec's."""
+    p = Player(lib, spec, entry, device, a)
     outs = []
     try:
         for i, step in enumerate(steps):
@@ -185,10 +220,32 @@ def run(lib, spec, steps, entry="host", device=None, before=None, after=None):
     return outs
 
 
+def shift_before(spec, steps, i):
+    """The a of the live solver when step i begins: the spec's, then whatever the last start / step with a dt / shift made it."""
+    a, dt, theta = spec[4], None, None
+    for step in steps[:i]:
+        if step[0] == "close_reopen":
+            a = spec[4]
+        elif step[0] == "shift":
+            a = step[1]
+        elif step[0] in ("start", "step"):
+            new_dt, new_theta = (step[4], step[5]) if step[0] == "start" else (step[3], step[4])
+            dt, theta = new_dt or dt, new_theta or theta
+            a = 1.0 / (theta * dt)
+    return a
+
+
 def fresh(lib, spec, steps, i, entry="host", device=None):
-    """Step i alone on a new solver that has only seen the last "coef" step before it (the same arrays, u0 included)."""
+    """Step i alone on a new solver that has only seen the last "coef" step before it (the same arrays, u0 included) and the live solver's
+    current a.  A "step" of a march: the new solver has also seen the last "start" and the march's steps since, and nothing between them (a
+    march restarted from a fetched state agrees to rounding only, DESIGN.md §11.8: so it is replayed from its start)."""
     coef = [s for s in steps[:i] if s[0] == "coef"][-1]
-    return run(lib, spec, [coef, steps[i]], entry, device)[1]
+    if steps[i][0] == "step":
+        first = max(j for j in range(i) if steps[j][0] == "start")
+        assert not any(s[0] in ("coef", "solve", "close_reopen", "shift") for s in steps[first:i]), "the march of step i ended before it"
+        replay = [coef, steps[first]] + [s for s in steps[first + 1:i + 1] if s[0] == "step"]
+        return run(lib, spec, replay, entry, device)[-1]
+    return run(lib, spec, [coef, steps[i]], entry, device, a=shift_before(spec, steps, i))[1]
 
 
 def differences(got, ref):
@@ -254,6 +311,70 @@ def sequence(lib, spec):
                     arr.setflags(write=False)
     _SEQ[key] = steps
     return steps
+
+
+MARCH_DT, MARCH_THETA, MARCH_RTOL = 2e-3, 0.5, 1e-6
+_MARCH = {}
+
+
+def march_sequence(spec):
+    """The sequence with time marches, for a spec with a != 0 (1-based, as DESIGN.md §11.7 counts): 3 is the solver's FIRST start, after a solve
+    has run -- the finest level gets two more vectors, so new storage (create_vectors); 5 and 6 use the operator and its scratch vectors in the
+    middle of a march; 8 changes dt; 9 ends the march and may take its two vectors; 12 and 16 put new coefficients under a solver that
+    marched; 19 and 20 are set_shift and a solve on it.  Every array is random and independent of any output, so nothing has to be played to
+    build it.  Cached per spec; the arrays are never written to."""
+    key = spec_id(spec)
+    if key in _MARCH:
+        return _MARCH[key]
+    assert spec[4] != 0.0
+    n = spec[0]
+    rng = np.random.default_rng(6000 + n)
+    walls = shape_bc(spec) == "dirichlet"
+
+    def cells(lo=-1.0, hi=1.0):
+        return lo + (hi - lo) * rng.random((n, n, n))
+
+    def g():
+        return rng.random((6, n, n)) * 4.0 - 2.0 if walls else None
+
+    def coef(seed):
+        return ("coef", coefficients(spec, seed)) + ((kappa(spec, seed + 1),) if has_robin(spec) else ())
+
+    def start():
+        return ("start", cells(), cells(-2.0, 2.0), g(), MARCH_DT, MARCH_THETA)
+
+    def step(dt=None):
+        return ("step", cells(-2.0, 2.0), g(), dt, None, MARCH_RTOL)
+
+    f1 = cells(-0.3, 0.7)
+    steps = [coef(7000 + n), ("solve", f1, "fmg", {"boundary": g()}),
+             start(), step(), ("apply", cells(), g()), ("flux", cells(), g()), step(), step(MARCH_DT / 4.0),
+             ("solve", f1, "pcg", {"rtol": 1e-8, "max_iter": 2}),
+             start(), step(),
+             coef(8000 + n), start(), step(),
+             ("close_reopen",), coef(9000 + n), start(), step(),
+             ("shift", 2.5), ("solve", f1, "fmg", {"boundary": g()})]
+    assert [s[0] for s in steps] == ["coef", "solve", "start", "step", "apply", "flux", "step", "step", "solve", "start", "step", "coef", "start",
+                                     "step", "close_reopen", "coef", "start", "step", "shift", "solve"]
+    for s in steps:
+        for v in s[1:]:
+            for arr in (v if isinstance(v, tuple) else v.values() if isinstance(v, dict) else (v,)):
+                if isinstance(arr, np.ndarray):
+                    arr.setflags(write=False)
+    _MARCH[key] = steps
+    return steps
+
+
+def issued_thrice(steps):
+    """(steps with every solve issued three times in a row and every march step followed by two more of the same data, for each the index of the
+    step it came from).  With graphs on, the three issues of a solve are eager, captured and replayed; the repeated steps of a march are further
+    time steps, and only a run of the same expanded sequence is their reference."""
+    out, of = [], []
+    for i, step in enumerate(steps):
+        for _ in range(3 if step[0] in ("solve", "step") else 1):
+            out.append(step)
+            of.append(i)
+    return out, of
 
 
 def interleave(lib, specs, sequences, entry="host", devices=None):

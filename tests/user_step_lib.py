@@ -3,6 +3,7 @@ operator L(u; g) = apply(u, boundary=g) - a alpha u from the public API, the rou
 points that takes its arrays from the host or from device memory.
 """
 import ctypes
+import hashlib
 
 import numpy as np
 
@@ -56,15 +57,25 @@ def rounding_gate(s, coef, *us):
     return ROUNDING_FACTOR * ROUNDING_MEASURED * rounding_scale(s, coef, *us)
 
 
+def digests(steps):
+    """One sha256 per step of march()'s result over u, the rate array, the info fields and the rate: what a worker process prints of its march."""
+    return [hashlib.sha256(s[1].tobytes() + s[2].tobytes() + repr((s[0], s[3], s[4])).encode()).hexdigest() for s in steps]
+
+
 def host_arrays():
     return (lambda v: None if v is None else v.ctypes.data), H.WHERE_HOST
 
 
-def march(lib, n, box_dim, name, seed, theta, dts, rtol, device=None, spoil=None):
+def march(lib, n, box_dim, name, seed, theta, dts, rtol, device=None, spoil=None, watch=None, coef=None):
     """start at time level 0, then one step per entry of `dts` (time level k = 1, 2, ...) through the C entry points; device = DeviceArrays: every
     array lives in device memory.  spoil = (k, "f" | "g"): before step k a step with a NaN in that array is tried, and its status recorded.
+    watch(k, done): called right before (done = 0) and right after (done = 1) the hpgmg_user_step call of step k (counters).
+    coef: (alpha, beta_i, beta_j, beta_k) in the place of problem()'s smooth fields, which take seconds to make at 256^3.
     Returns [(status, u, rate array, info fields, rate)] per step, with ("refused", status) entries where a spoiled step was tried."""
-    bc, coef, kappa = problem(name, n, seed)
+    if coef is None:
+        bc, coef, kappa = problem(name, n, seed)
+    else:
+        bc, kappa = SOLVERS[name], kappa_for(name, n)
     put, w = host_arrays() if device is None else (device.put, H.WHERE_PLUGIN)
     out = []
 
@@ -95,8 +106,13 @@ def march(lib, n, box_dim, name, seed, theta, dts, rtol, device=None, spoil=None
                 else:
                     bad_g[3, n - 1, 1] = np.nan
                 out.append(("refused", lib.hpgmg_user_step(s._ptr, put(bad_f), put(bad_g), w, dt, theta, rtol, ctypes.byref(info), ctypes.byref(rate))))
-            st = lib.hpgmg_user_step(s._ptr, put(f), put(g), w, dt if k == 1 or dt != dts[k - 2] else 0.0, theta if k == 1 else 0.0, rtol,
+            pf, pg = put(f), put(g)
+            if watch:
+                watch(k, 0)
+            st = lib.hpgmg_user_step(s._ptr, pf, pg, w, dt if k == 1 or dt != dts[k - 2] else 0.0, theta if k == 1 else 0.0, rtol,
                                      ctypes.byref(info), ctypes.byref(rate))
+            if watch:
+                watch(k, 1)
             fields = (info.norm_of_residual, info.norm_of_f, info.mean_shift, info.vcycles, info.converged)
             out.append((st, fetch(s, lib.hpgmg_user_get_solution), fetch(s, lib.hpgmg_user_get_rate), fields, rate.value))
             if device is not None:
