@@ -8,7 +8,7 @@
 // per dim x 8 x 8 tile accumulated in k,j,i order, partials added in tile-list
 // order (misc.c:261-269).  They are only ever called on the coarsest level
 // (BiCGStab) and in untimed setup, so one lane per tile is enough.
-#include "common.hpp"
+#include "reduce.hpp"
 
 namespace hpgmg {
 
@@ -71,32 +71,11 @@ __global__ __launch_bounds__(256) void fill_kernel(const hpgmg_hip_level L, int 
   }
 }
 
-// ---- max reductions ------------------------------------------------------------------
-__device__ __forceinline__ double wave_max(double v) {
-  for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(v, off, 64); v = (o > v) ? o : v; }
-  return v;
-}
-__device__ __forceinline__ void block_max_store_at(double v, double *partials, int slot) {
+// ---- max reductions (wave_max, block_max, block_max_store: reduce.hpp) -----------------------------
+// a workgroup's maximum -> partials[index], through LDS of the helper's own
+__device__ __forceinline__ void block_max_store(double v, double *partials, int index) {
   __shared__ double smem[kRowsPerBlock];
-  v = wave_max(v);
-  if (threadIdx.x % 64 == 0) smem[threadIdx.x / 64] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double m = smem[0];
-    for (int w = 1; w < kRowsPerBlock; w++) m = (smem[w] > m) ? smem[w] : m;
-    partials[slot] = m;
-  }
-}
-__device__ __forceinline__ void block_max_store(double v, double *partials) {
-  __shared__ double smem[kRowsPerBlock];
-  v = wave_max(v);
-  if (threadIdx.x % 64 == 0) smem[threadIdx.x / 64] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double m = smem[0];
-    for (int w = 1; w < kRowsPerBlock; w++) m = (smem[w] > m) ? smem[w] : m;
-    partials[blockIdx.x] = m;
-  }
+  block_max_store<kRowsPerBlock>(v, smem, partials, index);
 }
 
 // grid = (workgroups per box, boxes); each wave strides over the rows of its box with four rows in flight;
@@ -127,10 +106,8 @@ __device__ __forceinline__ double absmax_rows(const hpgmg_hip_level &L, int id) 
   return m;
 }
 
-// Scalar results go straight to a pinned host slot {value, sequence}: the last lane stores the value,
-// fences at system scope, then stores the launch's sequence number; the host polls the sequence
-// instead of paying a full stream synchronisation (reductions gate the host-driven BiCGStab).
-// (ResultSlot and publish(): common.hpp)
+// Scalar results go straight to a pinned host record and the host waits on the launch's ticket:
+// ResultSlot, publish(), Scalar, scalar_begin() / scalar_wait() and max_of_partials() are reduce.hpp's.
 
 // small levels: one workgroup walks every row and stores the final max itself
 __global__ __launch_bounds__(256) void absmax_small_kernel(const hpgmg_hip_level L, int id, ResultSlot *result, unsigned long long seq) {
@@ -143,34 +120,14 @@ __global__ __launch_bounds__(256) void absmax_small_kernel(const hpgmg_hip_level
     const double *p = vec_origin(L, r.box, id) + r.j * L.jStride + r.k * L.kStride;
     for (int i = lane; i < L.dim; i += 64) { const double f = fabs(p[i]); m = (f > m) ? f : m; }
   }
-  m = wave_max(m);
-  if (lane == 0) smem[threadIdx.x / 64] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) { for (int w = 1; w < 4; w++) m = (smem[w] > m) ? smem[w] : m; publish(result, m, seq); }
+  m = block_max<4>(m, smem);
+  if (threadIdx.x == 0) publish(result, m, seq);
 }
 
 // (a single-launch "last workgroup folds" variant was measured 4x slower: the agent-scope fence each
 // workgroup needs before signalling costs an L2 write-back on a multi-XCD part; a second tiny launch is cheaper)
 __global__ __launch_bounds__(256) void absmax_kernel(const hpgmg_hip_level L, int id, double *partials) {
-  block_max_store_at(absmax_rows(L, id), partials, blockIdx.x + gridDim.x * blockIdx.y);
-}
-
-__global__ __launch_bounds__(256) void final_max_kernel(const double *partials, int n, double init, ResultSlot *result, unsigned long long seq) {
-  __shared__ double smem[4];
-  double m = init;
-  // four loads in flight per lane: the chain of one load per iteration made 8192 partials a 10 us launch (a maximum is exact under any order)
-  double m1 = init, m2 = init, m3 = init;
-  int t = threadIdx.x;
-  for (; t + 768 < n; t += 1024) {
-    const double a0 = partials[t], a1 = partials[t + 256], a2 = partials[t + 512], a3 = partials[t + 768];
-    m = (a0 > m) ? a0 : m; m1 = (a1 > m1) ? a1 : m1; m2 = (a2 > m2) ? a2 : m2; m3 = (a3 > m3) ? a3 : m3;
-  }
-  for (; t < n; t += 256) m = (partials[t] > m) ? partials[t] : m;
-  m = (m1 > m) ? m1 : m; m2 = (m3 > m2) ? m3 : m2; m = (m2 > m) ? m2 : m;
-  m = wave_max(m);
-  if (threadIdx.x % 64 == 0) smem[threadIdx.x / 64] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) { for (int w = 1; w < 4; w++) m = (smem[w] > m) ? smem[w] : m; publish(result, (smem[0] > m) ? smem[0] : m, seq); }
+  block_max_store(absmax_rows(L, id), partials, blockIdx.x + gridDim.x * blockIdx.y);
 }
 
 // norm(F) ; scale_vector(R, 1.0, F) ; restriction(coarse R <- R, RESTRICT_CELL) -- the first three operators of FMGSolve (mg.c:1262-1270)
@@ -210,7 +167,7 @@ __global__ __launch_bounds__(256) void norm_copy_restrict_kernel(const hpgmg_hip
       q = fabs(cc.x); m = (q > m) ? q : m; q = fabs(cc.y); m = (q > m) ? q : m; q = fabs(d.x); m = (q > m) ? q : m;  q = fabs(d.y); m = (q > m) ? q : m;
     }
   }
-  block_max_store(m, partials);
+  block_max_store(m, partials, blockIdx.x);
 }
 
 // ---- ordered sums ----------------------------------------------------------------------
@@ -368,7 +325,7 @@ __global__ __launch_bounds__(256) void rebuild7_kernel(const hpgmg_hip_level L, 
       if (l1inv) l1inv[i] = (Aii >= 1.5 * sumAbsAij) ? 1.0 / (Aii) : 1.0 / (Aii + 0.5 * sumAbsAij);
     }
   }
-  block_max_store(best, partials);
+  block_max_store(best, partials, blockIdx.x);
 }
 
 // operators/rebuild.c:139-181: from the accumulated Aii and sum|Aij| form Dinv, L1inv and the Gershgorin bound
@@ -389,44 +346,7 @@ __global__ __launch_bounds__(256) void blackbox_finalize_kernel(const hpgmg_hip_
       Aii[i] = 1.0 / d;
     }
   }
-  block_max_store(best, partials);
-}
-
-// scratch for partial results + a pinned host word the final kernels write to
-static double *g_scratch = nullptr;  static int g_scratch_len = 0;
-static ResultSlot *g_result_dev = nullptr;   // pinned, device-visible host slot: kernels publish the scalar here directly
-static unsigned long long g_seq = 0;
-static int ensure_scratch(int n) {
-  if (!g_result_dev) { HPGMG_CHECK(hipHostMalloc((void **)&g_result_dev, 64, hipHostMallocDefault)); for (int q_ = 0; q_ < 4; q_++) { g_result_dev[q_].value = 0.0; g_result_dev[q_].seq = 0; } }      // [0]: the slot (+ a second value behind it); [2]: the slot of a deferred scalar
-  if (n > g_scratch_len) {
-    if (g_scratch) { hipStreamSynchronize(g_stream); (void)hipFree(g_scratch); }
-    int want = n < 65536 ? 65536 : n;
-    HPGMG_CHECK(hipMalloc((void **)&g_scratch, (size_t)want * sizeof(double)));
-    g_scratch_len = want;
-  }
-  return 0;
-}
-static int fetch_result(double *out) {
-  volatile ResultSlot *slot = g_result_dev;
-  for (long spins = 0; slot->seq != g_seq; spins++) {
-    __builtin_ia32_pause();
-    if (spins > 20000000L) { HPGMG_CHECK(hipStreamSynchronize(g_stream)); if (slot->seq != g_seq) return record_error(hipErrorUnknown, "reduction result never arrived"); }
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  *out = slot->value;
-  return 0;
-}
-
-// for kernels of other translation units that publish a scalar themselves (stencil.hip: small_ops_kernel)
-ResultSlot *reduction_slot_next(unsigned long long *seq_out) { if (ensure_scratch(1)) return nullptr; *seq_out = ++g_seq; return g_result_dev; }
-int reduction_fetch(double *out) { return fetch_result(out); }
-double reduction_second_value(void) { return reinterpret_cast<volatile double *>(g_result_dev)[2]; }
-// for kernels of other translation units that leave one partial maximum per workgroup (stencil.hip: residual + norm fused)
-double *reduction_scratch(int n) { return ensure_scratch(n) ? nullptr : g_scratch; }
-int finish_max_reduction(int n, double init, double *out) {
-  hipLaunchKernelGGL(final_max_kernel, dim3(1), dim3(256), 0, g_stream, (const double *)g_scratch, n, init, g_result_dev, ++g_seq);
-  HPGMG_LAUNCH_CHECK("final_max_kernel");
-  return fetch_result(out);
+  block_max_store(best, partials, blockIdx.x);
 }
 
 template <int OP>
@@ -477,22 +397,15 @@ int hpgmg_hip_random(const hpgmg_hip_level *L, int id) {
 
 // A scalar the caller needs only LATER (norm(F) at the start of FMGSolve is used in the convergence check at its end, mg.c:1262,1323) goes to a slot of
 // its own, so the host does not wait for the pass that forms it and keeps the stream full behind it; hpgmg_hip_deferred_fetch() collects it.
-static unsigned long long g_seq_deferred = 0;
+static Scalar g_deferred = { nullptr, 0 };      // the ticket of the newest deferred launch
 static int norm_copy_restrict(const hpgmg_hip_level *L, int f_id, int r_id, const hpgmg_hip_level *Lc, int rc_id, const int *map, double *norm_out, bool deferred);
 int hpgmg_hip_norm_copy_restrict_deferred(const hpgmg_hip_level *L, int f_id, int r_id, const hpgmg_hip_level *Lc, int rc_id, const int *map) {
   double unused = 0.0;
   return norm_copy_restrict(L, f_id, r_id, Lc, rc_id, map, &unused, true);
 }
 int hpgmg_hip_deferred_fetch(double *out) {
-  if (!g_result_dev || g_seq_deferred == 0) return record_error(hipErrorInvalidValue, "deferred_fetch: nothing was deferred");
-  volatile ResultSlot *slot = g_result_dev + 2;
-  for (long spins = 0; slot->seq != g_seq_deferred; spins++) {
-    __builtin_ia32_pause();
-    if (spins > 20000000L) { HPGMG_CHECK(hipStreamSynchronize(g_stream)); if (slot->seq != g_seq_deferred) return record_error(hipErrorUnknown, "deferred reduction result never arrived"); }
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  *out = slot->value;
-  return 0;
+  if (!g_deferred.slot) return record_error(hipErrorInvalidValue, "deferred_fetch: nothing was deferred");
+  return scalar_wait(g_deferred, out);
 }
 int hpgmg_hip_norm_copy_restrict(const hpgmg_hip_level *L, int f_id, int r_id, const hpgmg_hip_level *Lc, int rc_id, const int *map, double *norm_out) {
   return norm_copy_restrict(L, f_id, r_id, Lc, rc_id, map, norm_out, false);
@@ -503,61 +416,64 @@ static int norm_copy_restrict(const hpgmg_hip_level *L, int f_id, int r_id, cons
   if (L->num_boxes <= 0 || Lc->num_boxes <= 0 || (L->dim & 1) || !(L->flags & 1) || (L->jStride & 1) || (L->kStride & 1) || (L->volume & 1) || f_id == r_id)
     return record_error(hipErrorInvalidValue, "norm_copy_restrict: level not supported");
   const int nblk = rows_grid(L->num_boxes * (L->dim / 2) * (L->dim / 2));
-  if (int e = ensure_scratch(nblk)) return e;
+  double *partials = reduction_scratch(nblk);
+  if (!partials) return record_error(hipErrorOutOfMemory, "norm_copy_restrict: no scratch");
   static const bool nt_allowed = [] { const char *e = getenv("HPGMG_TUNE_COPY_NT"); return !(e && *e == '0'); }();
   if (nt_allowed && (double)L->num_boxes * L->dim * L->dim * L->dim * sizeof(double) > 256e6)
-    hipLaunchKernelGGL(norm_copy_restrict_kernel<true>, dim3(nblk), dim3(256), 0, g_stream, *L, f_id, r_id, *Lc, rc_id, map, g_scratch);
-  else hipLaunchKernelGGL(norm_copy_restrict_kernel<false>, dim3(nblk), dim3(256), 0, g_stream, *L, f_id, r_id, *Lc, rc_id, map, g_scratch);
-  if (!norm_out) { HPGMG_LAUNCH_CHECK("norm_copy_restrict (copy + restriction only)"); return 0; }     // the norm is not wanted: nothing to reduce, nothing to wait for
-  if (deferred) {
-    hipLaunchKernelGGL(final_max_kernel, dim3(1), dim3(256), 0, g_stream, (const double *)g_scratch, nblk, 0.0, g_result_dev + 2, ++g_seq_deferred);
-    HPGMG_LAUNCH_CHECK("norm_copy_restrict (norm deferred)");
-    return 0;
-  }
-  hipLaunchKernelGGL(final_max_kernel, dim3(1), dim3(256), 0, g_stream, (const double *)g_scratch, nblk, 0.0, g_result_dev, ++g_seq);
+    hipLaunchKernelGGL(norm_copy_restrict_kernel<true>, dim3(nblk), dim3(256), 0, g_stream, *L, f_id, r_id, *Lc, rc_id, map, partials);
+  else hipLaunchKernelGGL(norm_copy_restrict_kernel<false>, dim3(nblk), dim3(256), 0, g_stream, *L, f_id, r_id, *Lc, rc_id, map, partials);
   HPGMG_LAUNCH_CHECK("norm_copy_restrict");
-  return fetch_result(norm_out);
+  if (!norm_out) return 0;                          // the norm is not wanted: nothing to reduce, nothing to wait for
+  if (!deferred) return max_of_partials(nblk, 0.0, norm_out);
+  if (int e = scalar_begin(&g_deferred, true)) return e;
+  return max_of_partials(nblk, 0.0, g_deferred);
 }
 int hpgmg_hip_norm_max(const hpgmg_hip_level *L, int id, double *out) {
   if (int e = hpgmg_hip_graph_flush()) return e;
   *out = 0.0;
   if (L->num_boxes <= 0) return 0;
   const int nblk = rows_grid(L->num_boxes * L->dim * L->dim);
-  if (int e = ensure_scratch(nblk)) return e;
   if (nblk <= 64) {
-    hipLaunchKernelGGL(absmax_small_kernel, dim3(1), dim3(256), 0, g_stream, *L, id, g_result_dev, ++g_seq);
-  } else {
-    // ~16 workgroups per CU over the whole level, each wave streaming several rows of one box
-    int per_box = rows_grid(L->dim * L->dim);
-    while (per_box > 1 && (long long)per_box * L->num_boxes > 4096) per_box = (per_box + 1) / 2;
-    hipLaunchKernelGGL(absmax_kernel, dim3(per_box, L->num_boxes), dim3(256), 0, g_stream, *L, id, g_scratch);
-    hipLaunchKernelGGL(final_max_kernel, dim3(1), dim3(256), 0, g_stream, (const double *)g_scratch, per_box * L->num_boxes, 0.0, g_result_dev, ++g_seq);
+    Scalar t;
+    if (int e = scalar_begin(&t)) return e;
+    hipLaunchKernelGGL(absmax_small_kernel, dim3(1), dim3(256), 0, g_stream, *L, id, t.slot, t.seq);
+    HPGMG_LAUNCH_CHECK("norm_max");
+    return scalar_wait(t, out);
   }
+  // ~16 workgroups per CU over the whole level, each wave streaming several rows of one box
+  int per_box = rows_grid(L->dim * L->dim);
+  while (per_box > 1 && (long long)per_box * L->num_boxes > 4096) per_box = (per_box + 1) / 2;
+  double *partials = reduction_scratch(per_box * L->num_boxes);
+  if (!partials) return record_error(hipErrorOutOfMemory, "norm_max: no scratch");
+  hipLaunchKernelGGL(absmax_kernel, dim3(per_box, L->num_boxes), dim3(256), 0, g_stream, *L, id, partials);
   HPGMG_LAUNCH_CHECK("norm_max");
-  return fetch_result(out);
+  return max_of_partials(per_box * L->num_boxes, 0.0, out);
 }
 static int ordered_sum(const hpgmg_hip_level *L, int id_a, int id_b, double *out) {
   if (int e = hpgmg_hip_graph_flush()) return e;
   *out = 0.0;
   if (L->num_boxes <= 0) return 0;
   const int side = (L->dim + BLOCKCOPY_TILE_J - 1) / BLOCKCOPY_TILE_J, ntiles = side * side * L->num_boxes;
-  if (int e = ensure_scratch(ntiles)) return e;
+  double *partials = reduction_scratch(ntiles);
+  if (!partials) return record_error(hipErrorOutOfMemory, "ordered_sum: no scratch");
+  Scalar t;
+  if (int e = scalar_begin(&t)) return e;
   if (ntiles <= 64) {
-    hipLaunchKernelGGL((tile_sum_kernel<true>), dim3(1), dim3(64), 0, g_stream, *L, id_a, id_b, g_scratch, g_result_dev, ++g_seq);
+    hipLaunchKernelGGL((tile_sum_kernel<true>), dim3(1), dim3(64), 0, g_stream, *L, id_a, id_b, partials, t.slot, t.seq);
   } else {
     const size_t lds = (size_t)2 * kSumGroup * L->dim * sizeof(double);
-    if (L->dim <= 128)      hipLaunchKernelGGL((tile_sum_wave_kernel<2>), dim3(ntiles), dim3(64), lds, g_stream, *L, id_a, id_b, g_scratch);
-    else if (L->dim <= 256) hipLaunchKernelGGL((tile_sum_wave_kernel<4>), dim3(ntiles), dim3(64), lds, g_stream, *L, id_a, id_b, g_scratch);
+    if (L->dim <= 128)      hipLaunchKernelGGL((tile_sum_wave_kernel<2>), dim3(ntiles), dim3(64), lds, g_stream, *L, id_a, id_b, partials);
+    else if (L->dim <= 256) hipLaunchKernelGGL((tile_sum_wave_kernel<4>), dim3(ntiles), dim3(64), lds, g_stream, *L, id_a, id_b, partials);
     else if (L->dim <= 64 * kSumMaxChunks) {
       static bool once = false;
       if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)tile_sum_wave_kernel<kSumMaxChunks>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)2 * kSumGroup * 64 * kSumMaxChunks * sizeof(double)))); once = true; }
-      hipLaunchKernelGGL((tile_sum_wave_kernel<kSumMaxChunks>), dim3(ntiles), dim3(64), lds, g_stream, *L, id_a, id_b, g_scratch);
+      hipLaunchKernelGGL((tile_sum_wave_kernel<kSumMaxChunks>), dim3(ntiles), dim3(64), lds, g_stream, *L, id_a, id_b, partials);
     }
-    else hipLaunchKernelGGL((tile_sum_kernel<false>), dim3((ntiles + 63) / 64), dim3(64), 0, g_stream, *L, id_a, id_b, g_scratch, g_result_dev, 0ULL);
-    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(64), 0, g_stream, (const double *)g_scratch, ntiles, g_result_dev, ++g_seq);
+    else hipLaunchKernelGGL((tile_sum_kernel<false>), dim3((ntiles + 63) / 64), dim3(64), 0, g_stream, *L, id_a, id_b, partials, t.slot, 0ULL);
+    hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(64), 0, g_stream, (const double *)partials, ntiles, t.slot, t.seq);
   }
   HPGMG_LAUNCH_CHECK("ordered_sum");
-  return fetch_result(out);
+  return scalar_wait(t, out);
 }
 int hpgmg_hip_dot(const hpgmg_hip_level *L, int id_a, int id_b, double *out) { return ordered_sum(L, id_a, id_b, out); }
 int hpgmg_hip_sum(const hpgmg_hip_level *L, int id, double *out) { return ordered_sum(L, id, -1, out); }
@@ -567,11 +483,11 @@ int hpgmg_hip_blackbox_finalize(const hpgmg_hip_level *L, int Aii_id, int sumAbs
   *lambda_max_out = -1e9;
   if (L->num_boxes <= 0) return 0;
   const int nblk = rows_grid(L->num_boxes * L->dim * L->dim);
-  if (int e = ensure_scratch(nblk)) return e;
-  hipLaunchKernelGGL(blackbox_finalize_kernel, dim3(nblk), dim3(256), 0, g_stream, *L, Aii_id, sumAbs_id, a, b, h2inv, g_scratch);
-  hipLaunchKernelGGL(final_max_kernel, dim3(1), dim3(256), 0, g_stream, (const double *)g_scratch, nblk, -1e9, g_result_dev, ++g_seq);
+  double *partials = reduction_scratch(nblk);
+  if (!partials) return record_error(hipErrorOutOfMemory, "blackbox_finalize: no scratch");
+  hipLaunchKernelGGL(blackbox_finalize_kernel, dim3(nblk), dim3(256), 0, g_stream, *L, Aii_id, sumAbs_id, a, b, h2inv, partials);
   HPGMG_LAUNCH_CHECK("blackbox_finalize");
-  return fetch_result(lambda_max_out);
+  return max_of_partials(nblk, -1e9, lambda_max_out);
 }
 
 int hpgmg_hip_rebuild_7pt(const hpgmg_hip_level *L, int variable_coeff, int alpha_id, int l1inv_id,
@@ -580,12 +496,12 @@ int hpgmg_hip_rebuild_7pt(const hpgmg_hip_level *L, int variable_coeff, int alph
   *lambda_max_out = -1e9;
   if (L->num_boxes <= 0) return 0;
   const int nblk = rows_grid(L->num_boxes * L->dim * L->dim);
-  if (int e = ensure_scratch(nblk)) return e;
+  double *partials = reduction_scratch(nblk);
+  if (!partials) return record_error(hipErrorOutOfMemory, "rebuild_7pt: no scratch");
   RebuildArgs A = { variable_coeff, alpha_id, l1inv_id, a, b, h2inv };
-  hipLaunchKernelGGL(rebuild7_kernel, dim3(nblk), dim3(256), 0, g_stream, *L, A, g_scratch);
-  hipLaunchKernelGGL(final_max_kernel, dim3(1), dim3(256), 0, g_stream, (const double *)g_scratch, nblk, -1e9, g_result_dev, ++g_seq);
+  hipLaunchKernelGGL(rebuild7_kernel, dim3(nblk), dim3(256), 0, g_stream, *L, A, partials);
   HPGMG_LAUNCH_CHECK("rebuild_7pt");
-  return fetch_result(lambda_max_out);
+  return max_of_partials(nblk, -1e9, lambda_max_out);
 }
 
 }  // extern "C"

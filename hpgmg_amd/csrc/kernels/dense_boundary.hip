@@ -13,13 +13,12 @@
 // Face kernels (flux, lift, interp): grid row y = box, x over the 6 dim^2 face positions of the box; a position on a box face that is not
 // a domain face does nothing.  A cell on several domain faces (edge, corner) is handled once, by the position of the first face it touches
 // in the order i-low .. k-high, so no two lanes write one cell.  One launch per level and operation; they are launch bound (6 n^2 cells).
-#include "common.hpp"
+#include "reduce.hpp"
 #include "hpgmg_boundary_math.h"
 
 namespace hpgmg {
 
 constexpr int kBndThreads = 256;
-static int *g_bnd_flag = nullptr;               // validation bits of the last lifted pack / flux (device word)
 
 // offset, from a cell's padded offset, of its beta on face `face`, and the vector holding it
 __device__ __forceinline__ int bnd_beta_vec(int face) { return face < 2 ? VECTOR_BETA_I : face < 4 ? VECTOR_BETA_J : VECTOR_BETA_K; }
@@ -235,18 +234,6 @@ static dim3 bnd_grid(int per_box, int boxes) {       // x: the positions of one 
   return dim3(blocks < 16384 ? (blocks > 0 ? blocks : 1) : 16384, boxes < 65535 ? boxes : 65535);
 }
 static int bnd_cube(const hpgmg_hip_level *L) { return L->dim_i == L->dim_j && L->dim_i == L->dim_k && L->periodic == 0; }
-// around a kernel that ORs validation bits into g_bnd_flag: clear the word; after the launch, copy the bits to *status and wait for them
-static int bnd_flag_begin() {
-  if (!g_bnd_flag) HPGMG_CHECK(hipMalloc((void **)&g_bnd_flag, sizeof(int)));
-  HPGMG_CHECK(hipMemsetAsync(g_bnd_flag, 0, sizeof(int), g_stream));
-  return 0;
-}
-static int bnd_flag_end(const char *name, int *status) {
-  HPGMG_LAUNCH_CHECK(name);
-  HPGMG_CHECK(hipMemcpyAsync(status, g_bnd_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-  HPGMG_CHECK(hipStreamSynchronize(g_stream));
-  return 0;
-}
 
 }  // namespace hpgmg
 
@@ -282,10 +269,11 @@ int hpgmg_hip_dense_pack_lifted_robin(const hpgmg_hip_level *L, int id, const do
   if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "dense_pack_lifted: the level is not a Dirichlet cube");
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
-  if (int e = bnd_flag_begin()) return e;
+  int *flag;
+  if (int e = status_begin(&flag)) return e;
   hipLaunchKernelGGL(kappa ? dense_pack_lifted_kernel<true> : dense_pack_lifted_kernel<false>, bnd_grid(L->volume, L->num_boxes), dim3(kBndThreads), 0, g_stream,
-                     *L, id, src, g, w, mask, wall, wn, kappa, h, g_bnd_flag);
-  return bnd_flag_end("dense_pack_lifted_kernel", status);
+                     *L, id, src, g, w, mask, wall, wn, kappa, h, flag);
+  return status_end("dense_pack_lifted_kernel", status);
 }
 
 int hpgmg_hip_boundary_flux_faces(const hpgmg_hip_level *L, double *phi, const double *g, double w, int mask, const double *wall, double wn, int *status) {
@@ -298,19 +286,21 @@ int hpgmg_hip_boundary_flux_robin(const hpgmg_hip_level *L, double *phi, const d
   if (!bnd_cube(L)) return record_error(hipErrorInvalidValue, "boundary_flux: the level is not a Dirichlet cube");
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
-  if (int e = bnd_flag_begin()) return e;
+  int *flag;
+  if (int e = status_begin(&flag)) return e;
   hipLaunchKernelGGL(kappa ? boundary_flux_kernel<true> : boundary_flux_kernel<false>, bnd_grid(6 * L->dim * L->dim, L->num_boxes), dim3(kBndThreads), 0, g_stream,
-                     *L, phi, g, w, mask, wall, wn, kappa, h, g_bnd_flag);
-  return bnd_flag_end("boundary_flux_kernel", status);
+                     *L, phi, g, w, mask, wall, wn, kappa, h, flag);
+  return status_end("boundary_flux_kernel", status);
 }
 
 int hpgmg_hip_boundary_check_kappa(const double *kappa, int n, int robin_mask, int *status) {
   *status = 0;
   if (!kappa || n <= 0 || n > 9459 || robin_mask < 0 || robin_mask > 63) return record_error(hipErrorInvalidValue, "boundary_check_kappa: no array, or not a face mask");
   if (int e = hpgmg_hip_graph_flush()) return e;
-  if (int e = bnd_flag_begin()) return e;
-  hipLaunchKernelGGL(boundary_check_kappa_kernel, bnd_grid(6 * n * n, 1), dim3(kBndThreads), 0, g_stream, kappa, n, robin_mask, g_bnd_flag);
-  return bnd_flag_end("boundary_check_kappa_kernel", status);
+  int *flag;
+  if (int e = status_begin(&flag)) return e;
+  hipLaunchKernelGGL(boundary_check_kappa_kernel, bnd_grid(6 * n * n, 1), dim3(kBndThreads), 0, g_stream, kappa, n, robin_mask, flag);
+  return status_end("boundary_check_kappa_kernel", status);
 }
 
 int hpgmg_hip_boundary_store_walls(const hpgmg_hip_level *L, const double *wall, const double *kappa, double h, int mask) {

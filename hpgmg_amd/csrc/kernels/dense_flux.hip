@@ -9,13 +9,12 @@
 // domain wall takes the wall expression instead and never reads the ghost outside the domain; on a high wall it writes face dim too, from the
 // level's beta in the high ghost layer.  That is dense_pack_kernel's ownership rule for a face array: every entry has exactly one lane.  Only
 // lanes on a wall read g, wall and kappa; each g value read is validated, a bad one ORs a bit into one device word that the host reads once.
-#include "common.hpp"
+#include "reduce.hpp"
 #include "hpgmg_boundary_math.h"
 
 namespace hpgmg {
 
 constexpr int kFluxThreads = 256;
-static int *g_flux_flag = nullptr;              // validation bits of the last call (device word)
 
 struct FluxWalls { const double *g, *wall, *kappa; double b, wq, h; int mask; };
 // q on wall face `face` of the cell (gi, gj, gk) with value uc; beta: the level's beta there (used on a Dirichlet wall)
@@ -73,16 +72,13 @@ int hpgmg_hip_dense_unpack_flux(const hpgmg_hip_level *L, int id, const double *
   if (L->periodic && (g || mask)) return record_error(hipErrorInvalidValue, "dense_unpack_flux: boundary data on a periodic level");
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
-  if (!g_flux_flag) HPGMG_CHECK(hipMalloc((void **)&g_flux_flag, sizeof(int)));
-  HPGMG_CHECK(hipMemsetAsync(g_flux_flag, 0, sizeof(int), g_stream));
+  int *flag;
+  if (int e = status_begin(&flag)) return e;
   const FluxWalls W = { g, mask ? wall : nullptr, mask ? kappa : nullptr, b, wq, h, mask };
   const int blocks = (L->dim * L->dim * L->dim + kFluxThreads - 1) / kFluxThreads;
   const dim3 grid(blocks < 16384 ? (blocks > 0 ? blocks : 1) : 16384, L->num_boxes < 65535 ? L->num_boxes : 65535);   // the rest of either by grid stride
-  hipLaunchKernelGGL(dense_flux_kernel, grid, dim3(kFluxThreads), 0, g_stream, *L, id, W, flux_i, flux_j, flux_k, g_flux_flag);
-  HPGMG_LAUNCH_CHECK("dense_flux_kernel");
-  HPGMG_CHECK(hipMemcpyAsync(status, g_flux_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-  HPGMG_CHECK(hipStreamSynchronize(g_stream));      // the caller's arrays are complete on return (a torch tensor is read on another stream)
-  return 0;
+  hipLaunchKernelGGL(dense_flux_kernel, grid, dim3(kFluxThreads), 0, g_stream, *L, id, W, flux_i, flux_j, flux_k, flag);
+  return status_end("dense_flux_kernel", status);      // synchronises: the caller's arrays are complete on return (a torch tensor is read on another stream)
 }
 
 }  // extern "C"

@@ -11,12 +11,11 @@
 // a lane that finds a bad value ORs a bit into one device word, which the host reads once per call.
 //
 // Unpack: one lane per interior cell, box-major then k, j, i; the dense array's interior cells only are written.
-#include "common.hpp"
+#include "reduce.hpp"
 
 namespace hpgmg {
 
 constexpr int kDenseThreads = 256;
-static int *g_dense_flag = nullptr;             // validation bits of the last pack (device word)
 
 __global__ __launch_bounds__(kDenseThreads) void dense_pack_kernel(const hpgmg_hip_level L, int id, const double *__restrict__ src,
                                                                    int ni, int nj, int nk, int check, int *flag) {
@@ -112,13 +111,10 @@ int hpgmg_hip_dense_pack(const hpgmg_hip_level *L, int id, const double *src, in
     return record_error(hipErrorInvalidValue, "dense_pack: array extents do not match the level");
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
-  if (!g_dense_flag) HPGMG_CHECK(hipMalloc((void **)&g_dense_flag, sizeof(int)));
-  HPGMG_CHECK(hipMemsetAsync(g_dense_flag, 0, sizeof(int), g_stream));
-  hipLaunchKernelGGL(dense_pack_kernel, dense_grid(L->volume, L->num_boxes), dim3(kDenseThreads), 0, g_stream, *L, id, src, ni, nj, nk, check, g_dense_flag);
-  HPGMG_LAUNCH_CHECK("dense_pack_kernel");
-  HPGMG_CHECK(hipMemcpyAsync(status, g_dense_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-  HPGMG_CHECK(hipStreamSynchronize(g_stream));
-  return 0;
+  int *flag;
+  if (int e = status_begin(&flag)) return e;
+  hipLaunchKernelGGL(dense_pack_kernel, dense_grid(L->volume, L->num_boxes), dim3(kDenseThreads), 0, g_stream, *L, id, src, ni, nj, nk, check, flag);
+  return status_end("dense_pack_kernel", status);
 }
 
 int hpgmg_hip_dense_pack_walls(const hpgmg_hip_level *L, int id, const double *src, int axis, int check, int mask, double *wall, int *status) {
@@ -128,14 +124,11 @@ int hpgmg_hip_dense_pack_walls(const hpgmg_hip_level *L, int id, const double *s
   const int ni = L->dim_i + (axis == 0), nj = L->dim_j + (axis == 1), nk = L->dim_k + (axis == 2);
   if (int e = hpgmg_hip_graph_flush()) return e;
   if (L->num_boxes <= 0) return 0;
-  if (!g_dense_flag) HPGMG_CHECK(hipMalloc((void **)&g_dense_flag, sizeof(int)));
-  HPGMG_CHECK(hipMemsetAsync(g_dense_flag, 0, sizeof(int), g_stream));
+  int *flag;
+  if (int e = status_begin(&flag)) return e;
   hipLaunchKernelGGL(dense_pack_walls_kernel, dense_grid(L->volume, L->num_boxes), dim3(kDenseThreads), 0, g_stream, *L, id, src, ni, nj, nk, check,
-                     axis, (mask >> (2 * axis)) & 1, (mask >> (2 * axis + 1)) & 1, wall, g_dense_flag);
-  HPGMG_LAUNCH_CHECK("dense_pack_walls_kernel");
-  HPGMG_CHECK(hipMemcpyAsync(status, g_dense_flag, sizeof(int), hipMemcpyDeviceToHost, g_stream));
-  HPGMG_CHECK(hipStreamSynchronize(g_stream));
-  return 0;
+                     axis, (mask >> (2 * axis)) & 1, (mask >> (2 * axis + 1)) & 1, wall, flag);
+  return status_end("dense_pack_walls_kernel", status);
 }
 
 int hpgmg_hip_dense_unpack(const hpgmg_hip_level *L, int id, double *dst) {

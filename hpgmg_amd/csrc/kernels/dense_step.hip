@@ -8,9 +8,9 @@
 // Mapped as kernels/dense_flux.hip: one lane per interior cell, grid row y = box, inside a box k, j, i with consecutive lanes on consecutive i
 // (32-bit offsets inside a box), grid stride over both axes.  Ghost and padding cells are neither read nor written.  The grid is capped near
 // 16 workgroups per CU; a lane takes the rest of its box by stride, every trip six independent accesses.  step_rate leaves one maximum per workgroup
-// in the reduction scratch of kernels/blas1.hip, whose final_max_kernel folds them and publishes the value: a maximum has no order, so the result
+// in the reduction scratch of kernels/reduce.hip, whose final_max_kernel folds them and publishes the value: a maximum has no order, so the result
 // does not depend on the launch shape.  A NaN never becomes the maximum (f > m is false for it), as in pcg_update_kernel.
-#include "common.hpp"
+#include "reduce.hpp"
 #include "hpgmg_step_math.h"
 
 namespace hpgmg {
@@ -57,7 +57,8 @@ __global__ __launch_bounds__(kStepThreads) void step_rate_kernel(const hpgmg_hip
       best = (f > best) ? f : best;
     }
   }
-  for (int off = 32; off > 0; off >>= 1) { const double other = __shfl_down(best, off, 64); best = (other > best) ? other : best; }
+  // (the fold in place, not block_max_store: that form changes this kernel's scalar register count)
+  best = wave_max(best);
   if (threadIdx.x % 64 == 0) smem[threadIdx.x / 64] = best;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -112,7 +113,7 @@ int hpgmg_hip_step_rate(const hpgmg_hip_level *L, int num_vectors, int w_id, int
   if (!partials) return record_error(hipErrorOutOfMemory, "step_rate: no scratch");
   hipLaunchKernelGGL(step_rate_kernel, grid, dim3(kStepThreads), 0, g_stream, *L, w_id, r_id, u_id, uold_id, a, c, step_shift(L->dim), partials);
   HPGMG_LAUNCH_CHECK("step_rate_kernel");
-  return finish_max_reduction(blocks, 0.0, max_abs);
+  return max_of_partials(blocks, 0.0, max_abs);
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@
 // run exchange_boundary + apply_BCs_v4 (NO_CORNERS) before, as smooth()/residual() of operators.fv4.c do -- or, with P.ghost_free
 // (all boxes local), only apply_BCs_v4: x outside the box is then read from the neighbouring box itself (common.hpp gf_column).
 #pragma once
-#include "common.hpp"
+#include "reduce.hpp"
 #include "fv4_math.hpp"
 
 namespace hpgmg {
@@ -250,12 +250,9 @@ __device__ __forceinline__ void fv4_tile_body(const hpgmg_hip_level &L, const Fv
   }
   if (MODE == FV4_RESIDUAL && F.kind == 2) { __syncthreads(); fs.gather(F, sR, li, lj, k1 - 1, k0, coarse); }
   if (MODE == FV4_RESIDUAL && F.kind == 1) {                      // a maximum is exact under any order (misc.c:307-317)
-    double mx = fs.lane_max;
-    for (int off = 32; off > 0; off >>= 1) { const double o2 = __shfl_down(mx, off, 64); mx = (o2 > mx) ? o2 : mx; }
-    __syncthreads();
-    if ((tid & 63) == 0) sR[tid >> 6] = mx;
-    __syncthreads();
-    if (tid == 0) { double m2 = sR[0]; for (int q = 1; q < NT / 64; q++) m2 = (sR[q] > m2) ? sR[q] : m2; F.partials[logical] = m2; }
+    __syncthreads();                                              // sR is live until here
+    const double mx = block_max<NT / 64>(fs.lane_max, sR, tid);
+    if (tid == 0) F.partials[logical] = mx;
   }
 }
 template <int V, int MODE, int TJ, int TI = 64>

@@ -12,7 +12,7 @@
 // The per-box partials go to device scratch; the host adds them in box order after one copy (a few KB), mirrors the upper triangle
 // (matmul.c:45-46) and returns.
 #include <string.h>
-#include "common.hpp"
+#include "reduce.hpp"
 
 namespace hpgmg {
 

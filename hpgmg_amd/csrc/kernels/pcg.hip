@@ -9,7 +9,7 @@
 // stride-doubling tree over the leaves V[c + W (s + S box)] -- and pcg_fold_kernel folds the workgroups' values (stride 256 upwards) in a second tiny
 // launch (a last-workgroup form needs an agent-scope fence per workgroup: blas1.hip measured that 4x slower).  Lanes past dim^2 carry the tree's 0.0.
 // The stencil reads a face neighbour where it lives (common.hpp: box_nbr) and a Dirichlet face as -x(centre): apply_op's ghost-free rule, same bits.
-#include "common.hpp"
+#include "reduce.hpp"
 #include "stencil_math.hpp"
 
 namespace hpgmg {
@@ -46,15 +46,6 @@ __device__ __forceinline__ void pcg_block_sum2(double &v, double &w, double *sme
   __syncthreads();
   const double vlo = smem[0] + smem[1], vhi = smem[2] + smem[3], wlo = smem[4] + smem[5], whi = smem[6] + smem[7];
   v = vlo + vhi; w = wlo + whi;
-}
-__device__ __forceinline__ double pcg_block_max(double v, double *smem) {
-#pragma unroll
-  for (int stride = 1; stride < 64; stride *= 2) { const double o = __shfl_down(v, stride, 64); v = (o > v) ? o : v; }
-  if (threadIdx.x % 64 == 0) smem[threadIdx.x / 64] = v;
-  __syncthreads();
-  double m = smem[0];
-  for (int w = 1; w < 4; w++) m = (smem[w] > m) ? smem[w] : m;
-  return m;
 }
 
 // where lane (i, j) of box `box` reads its neighbour across face `face` when that neighbour lies outside the box: the column (pointer to its plane 0;
@@ -135,8 +126,7 @@ __global__ __launch_bounds__(kPcgLanes) void pcg_update_kernel(const hpgmg_hip_l
       best = (f > best) ? f : best;
     }
   }
-  const double m = pcg_block_max(best, smem);
-  if (threadIdx.x == 0) partials[it.item] = m;
+  block_max_store<4>(best, smem, partials, it.item);
 }
 
 __global__ __launch_bounds__(kPcgLanes) void pcg_dot_kernel(const hpgmg_hip_level L, int a_id, int b_id, int nseg, int ncb, int per_xcd, int items,
@@ -180,44 +170,33 @@ __global__ __launch_bounds__(kPcgLanes) void pcg_dot2_kernel(const hpgmg_hip_lev
   if (threadIdx.x == 0) { partials[it.item] = chain_a; partials[items + it.item] = chain_c; }
 }
 
-// the tree from stride 256 upwards over the workgroups' values: a lane folds its own `chunk` (a power of two) consecutive ones in place -- an aligned
-// run of the stride-doubling tree, which no other lane touches -- then the 1024 lanes fold through LDS; entries past n are the padding's 0.0
-__global__ __launch_bounds__(kFoldLanes) void pcg_fold_kernel(double *__restrict__ partials, int n, int chunk, ResultSlot *result, unsigned long long seq) {
-  __shared__ double smem[kFoldLanes];
+// the tree from stride 256 upwards over the workgroups' values, for N arrays of n values at once (partials[q n .. q n + n), q < N): a lane folds its own
+// `chunk` (a power of two) consecutive ones in place -- an aligned run of the stride-doubling tree, which no other lane touches -- then the 1024 lanes
+// fold through LDS (an array of 8 KB per q, the barriers of one fold); entries past n are the padding's 0.0.  The sum of array 0 is the launch's value,
+// that of array 1 its second value: the one sequence number publishes both.
+template <int N>
+__device__ __forceinline__ void pcg_fold_body(double *__restrict__ partials, int n, int chunk, ResultSlot *result, unsigned long long seq) {
+  __shared__ double smem[N][kFoldLanes];
   const int t = (int)threadIdx.x;
   const long long lo = (long long)t * chunk;
-  for (int stride = 1; stride < chunk; stride *= 2)
-    for (long long m = lo; m + stride < n && m < lo + chunk; m += 2 * stride) partials[m] = partials[m] + partials[m + stride];      // past n: + 0.0, which changes no bit
-  smem[t] = (lo < n) ? partials[lo] : 0.0;
-  __syncthreads();
-  for (int stride = 1; stride < kFoldLanes; stride *= 2) {
-    if (t % (2 * stride) == 0) smem[t] = smem[t] + smem[t + stride];
-    __syncthreads();
-  }
-  if (t == 0) publish(result, smem[0], seq);
-}
-// the same tree over TWO arrays of n values, partials[0 .. n) and partials[n .. 2 n), in one launch: a second LDS array (16 KB in all) and the barriers
-// of one fold.  The first sum goes to the slot's value, the second to the word behind its sequence number (reduction_second_value()), then the one
-// sequence number publishes both.
-__global__ __launch_bounds__(kFoldLanes) void pcg_fold2_kernel(double *__restrict__ partials, int n, int chunk, ResultSlot *result, unsigned long long seq) {
-  __shared__ double smem[2][kFoldLanes];
-  const int t = (int)threadIdx.x;
-  const long long lo = (long long)t * chunk;
-  for (int q = 0; q < 2; q++) {
+  for (int q = 0; q < N; q++) {
     double *P = partials + (long long)q * n;
     for (int stride = 1; stride < chunk; stride *= 2)
-      for (long long m = lo; m + stride < n && m < lo + chunk; m += 2 * stride) P[m] = P[m] + P[m + stride];
+      for (long long m = lo; m + stride < n && m < lo + chunk; m += 2 * stride) P[m] = P[m] + P[m + stride];      // past n: + 0.0, which changes no bit
     smem[q][t] = (lo < n) ? P[lo] : 0.0;
   }
   __syncthreads();
   for (int stride = 1; stride < kFoldLanes; stride *= 2) {
-    if (t % (2 * stride) == 0) { smem[0][t] = smem[0][t] + smem[0][t + stride]; smem[1][t] = smem[1][t] + smem[1][t + stride]; }
+    if (t % (2 * stride) == 0) for (int q = 0; q < N; q++) smem[q][t] = smem[q][t] + smem[q][t + stride];
     __syncthreads();
   }
-  if (t == 0) {
-    reinterpret_cast<double *>(result)[2] = smem[1][0];
-    publish(result, smem[0][0], seq);
-  }
+  if (t == 0) { if constexpr (N == 2) publish2(result, smem[0][0], smem[1][0], seq); else publish(result, smem[0][0], seq); }
+}
+__global__ __launch_bounds__(kFoldLanes) void pcg_fold_kernel(double *__restrict__ partials, int n, int chunk, ResultSlot *result, unsigned long long seq) {
+  pcg_fold_body<1>(partials, n, chunk, result, seq);
+}
+__global__ __launch_bounds__(kFoldLanes) void pcg_fold2_kernel(double *__restrict__ partials, int n, int chunk, ResultSlot *result, unsigned long long seq) {
+  pcg_fold_body<2>(partials, n, chunk, result, seq);
 }
 
 struct PcgGrid { int nseg, ncb, items, per_xcd, grid; };
@@ -229,27 +208,15 @@ static PcgGrid pcg_grid(const hpgmg_hip_level *L) {
   g.grid = grid_for(g.items, &g.per_xcd);
   return g;
 }
-static int pcg_fold(int items, double *out) {
+// fold the scratch's one (out1 == nullptr) or two arrays of `items` values and wait for the sums
+static int pcg_fold(int items, double *out0, double *out1 = nullptr) {
   int chunk = 1;
   while ((long long)chunk * kFoldLanes < items) chunk *= 2;
-  unsigned long long seq = 0;
-  ResultSlot *slot = reduction_slot_next(&seq);
-  if (!slot) return record_error(hipErrorOutOfMemory, "pcg: no result slot");
-  hipLaunchKernelGGL(pcg_fold_kernel, dim3(1), dim3(kFoldLanes), 0, g_stream, reduction_scratch(items), items, chunk, slot, seq);
+  Scalar t;
+  if (int e = scalar_begin(&t)) return e;
+  hipLaunchKernelGGL(out1 ? pcg_fold2_kernel : pcg_fold_kernel, dim3(1), dim3(kFoldLanes), 0, g_stream, reduction_scratch((out1 ? 2 : 1) * items), items, chunk, t.slot, t.seq);
   HPGMG_LAUNCH_CHECK("pcg_fold_kernel");
-  return reduction_fetch(out);
-}
-static int pcg_fold2(int items, double *out0, double *out1) {
-  int chunk = 1;
-  while ((long long)chunk * kFoldLanes < items) chunk *= 2;
-  unsigned long long seq = 0;
-  ResultSlot *slot = reduction_slot_next(&seq);
-  if (!slot) return record_error(hipErrorOutOfMemory, "pcg: no result slot");
-  hipLaunchKernelGGL(pcg_fold2_kernel, dim3(1), dim3(kFoldLanes), 0, g_stream, reduction_scratch(2 * items), items, chunk, slot, seq);
-  HPGMG_LAUNCH_CHECK("pcg_fold2_kernel");
-  if (int e = reduction_fetch(out0)) return e;
-  *out1 = reduction_second_value();
-  return 0;
+  return scalar_wait(t, out0, out1);
 }
 
 }  // namespace hpgmg
@@ -293,7 +260,7 @@ int hpgmg_hip_pcg_update(const hpgmg_hip_level *L, int x_id, int r_id, int p_id,
   if (!partials) return record_error(hipErrorOutOfMemory, "pcg_update: no scratch");
   hipLaunchKernelGGL(pcg_update_kernel, dim3(g.grid), dim3(kPcgLanes), 0, g_stream, *L, x_id, r_id, p_id, Ap_id, alpha, g.nseg, g.ncb, g.per_xcd, g.items, partials);
   HPGMG_LAUNCH_CHECK("pcg_update_kernel");
-  return finish_max_reduction(g.items, 0.0, rmax);
+  return max_of_partials(g.items, 0.0, rmax);
 }
 
 int hpgmg_hip_pcg_dot(const hpgmg_hip_level *L, int a_id, int b_id, double *dot) {
@@ -317,7 +284,7 @@ int hpgmg_hip_pcg_dot2(const hpgmg_hip_level *L, int a_id, int c_id, int b_id, d
   if (!partials) return record_error(hipErrorOutOfMemory, "pcg_dot2: no scratch");
   hipLaunchKernelGGL(pcg_dot2_kernel, dim3(g.grid), dim3(kPcgLanes), 0, g_stream, *L, a_id, c_id, b_id, g.nseg, g.ncb, g.per_xcd, g.items, partials);
   HPGMG_LAUNCH_CHECK("pcg_dot2_kernel");
-  return pcg_fold2(g.items, ab, cb);
+  return pcg_fold(g.items, ab, cb);
 }
 
 }  // extern "C"

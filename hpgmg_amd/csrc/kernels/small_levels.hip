@@ -2,6 +2,7 @@
 // host-driven Krylov solver on any plugin): a whole smooth() / residual() of a level of one box on an LDS image (small_level_kernel), the BiCGStab
 // bottom solve (solvers/bicgstab.c:14-97: bottom_bicgstab_kernel), queued BLAS-1 / operator calls ending in a scalar (small_ops_kernel) and the rest
 // of a V-cycle below a level of one box (mg.c:1145-1164: small_vtail_kernel).  A translation unit of its own (split from stencil.hip in round 4).
+#include "reduce.hpp"
 #include "stencil_direct.hpp"
 
 namespace hpgmg {
@@ -333,7 +334,7 @@ __device__ __forceinline__ void bottom_bicgstab_body(const hpgmg_hip_level &L, c
   auto norm = [&](double v) -> double {                            // max |v| (misc.c:303-349): exact under any order
     double m = 0.0;
     if (active) { const double f = fabs(v); m = (f > m) ? f : m; }
-    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(m, off, 64); m = (o > m) ? o : m; }
+    m = wave_max(m);
     if (lane == 0) scr[1032 + wave] = m;
     __syncthreads();
     m = scr[1032];
@@ -410,15 +411,14 @@ struct SmallOpsArgs {
   int n, bc_kind, zero_first, n_bc;
   const blockCopy_type *bc_list;
   double a, b, h2inv;
-  ResultSlot *result; unsigned long long seq;
+  Scalar t;                      // the launch's ticket, when it ends in a value
   SmallOp op[kSmallOpsMax];
 };
 // a launch may end in TWO value-returning operations (the second one a guess of what the host asks next): value k goes to the k-th double of
-// the slot's payload (value, then the word behind the sequence number), the LAST operation of the list publishes the sequence number
+// the slot (value, then second: the parts of reduce.hpp's publish2), the LAST operation of the list publishes the sequence number
 __device__ __forceinline__ void small_ops_value(ResultSlot *slot, int k, double v, bool last, unsigned long long seq) {
-  double *second = reinterpret_cast<double *>(slot) + 2;
-  if (k == 0) slot->value = v; else *second = v;
-  if (last) { __threadfence_system(); __hip_atomic_store(&slot->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+  if (k == 0) slot->value = v; else slot->second = v;
+  if (last) publish_seq(slot, seq);
 }
 template <int V>
 __global__ __launch_bounds__(512) void small_ops_kernel(const hpgmg_hip_level L, const SmallOpsArgs A) {
@@ -463,15 +463,15 @@ __global__ __launch_bounds__(512) void small_ops_kernel(const hpgmg_hip_level L,
     } else if (kind == SO_DOT) {
       if (active) part[tid] = vec_origin(L, 0, ida)[ijk] * vec_origin(L, 0, idb)[ijk];
       __syncthreads();
-      if (tid == 0) { double acc = 0.0; for (int t = 0; t < total; t++) acc += part[t]; small_ops_value(A.result, nvalues, 0.0 + acc, q == A.n - 1, A.seq); }   // (one tile: its partial added to 0.0, as tile_sum_kernel does)
+      if (tid == 0) { double acc = 0.0; for (int t = 0; t < total; t++) acc += part[t]; small_ops_value(A.t.slot, nvalues, 0.0 + acc, q == A.n - 1, A.t.seq); }   // (one tile: its partial added to 0.0, as tile_sum_kernel does)
       nvalues++;
     } else if (kind == SO_NORM) {
       double m = 0.0;
       if (active) { const double f = fabs(vec_origin(L, 0, ida)[ijk]); m = (f > m) ? f : m; }
-      for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(m, off, 64); m = (o > m) ? o : m; }
+      m = wave_max(m);
       if (lane == 0) part[512 + wave] = m;
       __syncthreads();
-      if (tid == 0) { for (int w = 1; w < nwaves; w++) m = (part[512 + w] > m) ? part[512 + w] : m; small_ops_value(A.result, nvalues, m, q == A.n - 1, A.seq); }
+      if (tid == 0) { for (int w = 1; w < nwaves; w++) m = (part[512 + w] > m) ? part[512 + w] : m; small_ops_value(A.t.slot, nvalues, m, q == A.n - 1, A.t.seq); }
       nvalues++;
     }
     __threadfence_block();
@@ -735,7 +735,7 @@ int hpgmg_hip_small_ops(const hpgmg_hip_level *L, int variant, int n, const int 
   }
   const bool wants = nvalues > 0;
   if ((nvalues >= 1) != (value_out != nullptr) || (nvalues == 2) != (value2_out != nullptr)) return record_error(hipErrorInvalidValue, "small_ops: one output pointer per value-returning operation");
-  if (wants) { A.result = reduction_slot_next(&A.seq); if (!A.result) return record_error(hipErrorOutOfMemory, "small_ops: result slot"); }
+  if (wants) if (int e = scalar_begin(&A.t)) return e;
   const int cells = L->dim * L->dim * L->dim;
   const int threads = cells > 64 ? 512 : (A.n_bc > 4 ? 512 : 64);           // one cell per lane (no striding); the boundary entries are a wave's work each
 #define SMALL_OPS_CASE(VAR) hipLaunchKernelGGL((small_ops_kernel<VAR>), dim3(1), dim3(threads), 0, g_stream, *L, A);
@@ -751,8 +751,7 @@ int hpgmg_hip_small_ops(const hpgmg_hip_level *L, int variant, int n, const int 
 #undef SMALL_OPS_CASE
   g_small_ops_launches++;
   HPGMG_LAUNCH_CHECK("small_ops_kernel");
-  if (wants) { if (int e = reduction_fetch(value_out)) return e; if (value2_out) *value2_out = reduction_second_value(); }
-  return 0;
+  return wants ? scalar_wait(A.t, value_out, value2_out) : 0;
 }
 // V-cycle tail below a level of one box (small_vtail_kernel).  The argument block lives in device memory: it is the same for every visit of
 // a chain in a solve, so a few of them are kept and uploaded only when their contents change.

@@ -22,6 +22,7 @@
 //   * stencil27_kernel (27-point) and stencil_direct_kernel (4th-order fv4, black-box probes);
 //   * logical tiles are ordered box, k, j, i and dealt to XCDs in contiguous ranges (common.hpp) so halo
 //     planes shared by adjacent tiles hit the same L2.
+#include "reduce.hpp"
 #include "stencil_direct.hpp"
 #include "stencil27_rb.hpp"
 #include "stencil27_rb_box.hpp"
@@ -375,10 +376,9 @@ __global__ __launch_bounds__(64 * WJ) void stencil7_wide_kernel(const hpgmg_hip_
     xm_b = xc_b; xc_b = xp_b; bk0_b = bk1_b;
   }
   if (kNorm) {                                                 // a maximum is exact under any order (misc.c:307-317)
-    for (int off = 32; off > 0; off >>= 1) { const double o2 = __shfl_down(lane_max, off, 64); lane_max = (o2 > lane_max) ? o2 : lane_max; }
-    if (lane == 0) wg_max[ty] = lane_max;
-    __syncthreads();
-    if (lane == 0 && ty == 0) { double m = wg_max[0]; for (int q = 1; q < WJ; q++) m = (wg_max[q] > m) ? wg_max[q] : m; F.partials[logical] = m; }
+    const int tid = 64 * ty + lane;
+    lane_max = block_max<WJ>(lane_max, wg_max, tid);
+    if (tid == 0) F.partials[logical] = lane_max;
   }
 }
 
@@ -1133,7 +1133,7 @@ int hpgmg_hip_residual_norm(const hpgmg_hip_level *L, int variant, int res_id, i
     g_tile_fused = TileFused{}; g_tile_fused.kind = 1; g_tile_fused.partials = part;
     StencilArgs T = {}; T.xn_id = x_id; T.xout_id = rhs_id; T.rhs_id = rhs_id; T.a = a; T.b = b; T.h2inv = h2inv;
     if (int e = launch<MODE_RESIDUAL>(L, variant, T, false)) return e;
-    return finish_max_reduction(g_tile_last_blocks, 0.0, norm_out);
+    return max_of_partials(g_tile_last_blocks, 0.0, norm_out);
   }
   if (!wide_fused_ok(L, variant)) return record_error(hipErrorInvalidValue, "residual_norm: level not supported");
   StencilArgs P = {}; P.xn_id = x_id; P.xout_id = res_id; P.rhs_id = rhs_id; P.a = a; P.b = b; P.h2inv = h2inv;
@@ -1143,7 +1143,7 @@ int hpgmg_hip_residual_norm(const hpgmg_hip_level *L, int variant, int res_id, i
   if (!F.partials) return record_error(hipErrorOutOfMemory, "residual_norm: scratch");
   if (int e = launch_wide_fused<MODE_RESIDUAL_NORM>(L, variant, P, F, 0)) return e;
   if (g_tile_part == 1) return 0;                 // the first part of a two-part launch: the tiles of the second part have not written their maxima yet
-  return finish_max_reduction(blocks, 0.0, norm_out);
+  return max_of_partials(blocks, 0.0, norm_out);
 }
 
 int hpgmg_hip_residual(const hpgmg_hip_level *L, int variant, int res_id, int x_id, int rhs_id, double a, double b, double h2inv) {

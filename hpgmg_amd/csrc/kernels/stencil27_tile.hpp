@@ -11,7 +11,7 @@
 // P.ghost_free (all boxes local): x outside the box is read from the neighbouring box itself (common.hpp gf_column), the caller then
 // runs only apply_BCs_p2 before the launch, no exchange_boundary.
 #pragma once
-#include "common.hpp"
+#include "reduce.hpp"
 
 #ifndef C27_0
 #define C27_0 (-4.2666666666666666666)
@@ -163,12 +163,9 @@ __global__ __launch_bounds__(TI * TJ) void stencil27_tile_kernel(const hpgmg_hip
   }
   if (MODE == 3 && F.kind == 2) { __syncthreads(); fs.gather(F, sR, li, lj, k1 - 1, k0, coarse); }
   if (MODE == 3 && F.kind == 1) {                                 // a maximum is exact under any order (misc.c:307-317)
-    double mx = fs.lane_max;
-    for (int off = 32; off > 0; off >>= 1) { const double o2 = __shfl_down(mx, off, 64); mx = (o2 > mx) ? o2 : mx; }
-    __syncthreads();
-    if ((tid & 63) == 0) sR[tid >> 6] = mx;
-    __syncthreads();
-    if (tid == 0) { double m2 = sR[0]; for (int q = 1; q < NT / 64; q++) m2 = (sR[q] > m2) ? sR[q] : m2; F.partials[logical] = m2; }
+    __syncthreads();                                              // sR is live until here
+    const double mx = block_max<NT / 64>(fs.lane_max, sR, tid);
+    if (tid == 0) F.partials[logical] = mx;
   }
 }
 

@@ -18,7 +18,7 @@
 // bit-identical to the per-operator path -- tests/test_gpu_* run both.
 // Ghost handling is the ghost-free form (neighbour box / Dirichlet -x, see stencil.hip), which
 // requires every face neighbour to be local: the host only uses this kernel then.
-#include "common.hpp"
+#include "reduce.hpp"
 #include "stencil_math.hpp"
 #include "dense_levels.hpp"
 
@@ -266,7 +266,7 @@ template <int NT>
 __device__ double bottom_norm(const BottomGeom &g, double v, double *scr) {          // max |v| (misc.c:303-349)
   double m = 0.0;
   if (g.active) { const double f = fabs(v); m = (f > m) ? f : m; }
-  for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_down(m, off, 64); m = (o > m) ? o : m; }
+  m = wave_max(m);
   double *w = scr + 2 * NT + 8;
   if (threadIdx.x % 64 == 0) w[threadIdx.x / 64] = m;
   __syncthreads();

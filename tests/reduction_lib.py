@@ -1,7 +1,7 @@
 """What tests/test_oracle_reductions.py and tests/test_gpu_reductions.py share: NumPy restatements of the reductions of operators/misc.c and, as
-plain Python, the launch arithmetic of kernels/blas1.hip (hpgmg_hip_norm_max, ordered_sum, final_max_kernel) that decides which kernel and which
-trip of which loop a cell meets.  The GPU tests assert the path they claim against these plans, so a later change of a constant in blas1.hip fails
-loudly instead of silently moving an edge away from the case that was placed on it.
+plain Python, the launch arithmetic of kernels/blas1.hip (hpgmg_hip_norm_max, ordered_sum) and kernels/reduce.hip (final_max_kernel) that decides
+which kernel and which trip of which loop a cell meets.  The GPU tests assert the path they claim against these plans, so a later change of a
+constant there fails loudly instead of silently moving an edge away from the case that was placed on it.
 
 A "geometry" is (boxes per side, box side); a "field" a (boxes, volume) array of whole padded boxes, as Level.read_all() returns it.
 """

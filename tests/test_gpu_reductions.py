@@ -1,5 +1,5 @@
 """BLAS-1 and every reduction that returns a maximum or an ordered sum, held to the CPU oracle at the edges of their launch shape (kernels/blas1.hip,
-kernels/pcg.hip pcg_update_kernel, the fused residual + norm of kernels/stencil.hip, stencil27_tile.hpp and fv4_tile.hpp).  Every
+kernels/reduce.hip final_max_kernel and the result slot, kernels/pcg.hip pcg_update_kernel, the fused residual + norm of kernels/stencil.hip, stencil27_tile.hpp and fv4_tile.hpp).  Every
 comparison is bitwise: all builds have -ffp-contract=off, a maximum is exact in any order and the sums have one order (misc.c:261-269).  The NumPy
 restatements and the launch arithmetic are tests/reduction_lib.py's, pinned on the CPU by tests/test_oracle_reductions.py; every test asserts the path
 it claims against those plans.
@@ -571,6 +571,58 @@ def test_norm_scale_restrict_wherever_the_maximum_sits(operator_pair, variant, g
                 assert rh[k, j, i] == value
     finally:
         P.restore(H.VECTOR_F, box)
+
+
+@pytest.mark.parametrize("where", ["first", "last"])
+def test_deferred_norm_collected_after_other_scalars(operator_pair, where):
+    """The deferred record of the result slot (kernels/reduce.hpp): hpgmg_norm_scale_restrict_fused_deferred is issued, then three launches take
+    immediate scalars -- a norm with another planted maximum, an ordered sum, and hpgmg_pcg_dot2's two values from one launch -- and only then
+    hpgmg_norm_deferred_fetch collects the first.  Every value is the oracle's (whose deferred form answers 0: its value is norm(F)), and the five
+    differ pairwise, so a crossed record, ticket or second value cannot pass."""
+    variant, geom = WIDE[0]
+    assert (variant, geom) == ("7pt-cheby-helm", (2, 128))
+    P = operator_pair(variant, geom)
+    Lh, Lo = P.hip.lib, P.oracle.lib
+    c_int, c_dbl, vp = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
+    for L in (Lh, Lo):
+        L.hpgmg_norm_scale_restrict_fused_deferred.restype = c_int
+        L.hpgmg_norm_scale_restrict_fused_deferred.argtypes = [vp, c_int, c_int, vp]
+        L.hpgmg_norm_deferred_fetch.restype = c_dbl
+        L.hpgmg_norm_deferred_fetch.argtypes = [vp]
+    box, k, j, i = restrict_places(geom)[where]
+    other = 0.25 * HUGE                                    # the maximum of U: another value, in another cell of another box
+    ubox, uk, uj, ui = (box + 3) % P.lh.num_boxes, 5, 77, 100
+    P.plant(H.VECTOR_F, box, P.cells[k, j, i], HUGE if where == "first" else -HUGE)
+    P.plant(H.VECTOR_U, ubox, P.cells[uk, uj, ui], -other)
+    try:
+        assert Lh.hpgmg_norm_scale_restrict_fused_deferred(P.lh.ptr, H.VECTOR_F, H.VECTOR_R, P.ch.ptr) == 1
+        ab, cb = c_dbl(-1.0), c_dbl(-1.0)
+        got_u = Lh.norm(P.lh.ptr, H.VECTOR_U)
+        got_dot = Lh.dot(P.lh.ptr, H.VECTOR_U, H.VECTOR_F)
+        assert Lh.hpgmg_pcg_dot2(P.lh.ptr, H.VECTOR_U, H.VECTOR_F, H.VECTOR_DINV, ctypes.byref(ab), ctypes.byref(cb)) == 1      # the kernel took it
+        got_f = Lh.hpgmg_norm_deferred_fetch(P.lh.ptr)
+
+        want_f = Lo.norm(P.lo.ptr, H.VECTOR_F)
+        if Lo.hpgmg_norm_scale_restrict_fused_deferred(P.lo.ptr, H.VECTOR_F, H.VECTOR_R, P.co.ptr):
+            assert Lo.hpgmg_norm_deferred_fetch(P.lo.ptr) == want_f
+        else:
+            Lo.scale_vector(P.lo.ptr, H.VECTOR_R, 1.0, H.VECTOR_F)
+            Lo.restriction(P.co.ptr, H.VECTOR_R, P.lo.ptr, H.VECTOR_R, H.RESTRICT_CELL)
+        want_u = Lo.norm(P.lo.ptr, H.VECTOR_U)
+        want_dot = Lo.dot(P.lo.ptr, H.VECTOR_U, H.VECTOR_F)
+        wab, wcb = c_dbl(-2.0), c_dbl(-2.0)
+        assert Lo.hpgmg_pcg_dot2(P.lo.ptr, H.VECTOR_U, H.VECTOR_F, H.VECTOR_DINV, ctypes.byref(wab), ctypes.byref(wcb)) == 0     # the portable form
+        got, want = [got_f, got_u, got_dot, ab.value, cb.value], [want_f, want_u, want_dot, wab.value, wcb.value]
+        assert want_f == HUGE and want_u == other
+        assert len(set(bits(np.array(want)).tolist())) == 5, want
+        assert bits(np.array(got)).tolist() == bits(np.array(want)).tolist(), (got, want, where)
+        same_bits(P.ch, P.co, H.VECTOR_R)
+        for q in (range(P.lh.num_boxes) if where == "first" else [box]):
+            rh, ro = P.lh.read_raw(q, H.VECTOR_R)[P.cells], P.lo.read_raw(q, H.VECTOR_R)[P.cells]
+            assert np.array_equal(bits(rh), bits(ro)), f"R of box {q}"
+    finally:
+        P.restore(H.VECTOR_F, box)
+        P.restore(H.VECTOR_U, ubox)
 
 
 def rebuild_restated(lv, a, b):

@@ -101,7 +101,7 @@ def test_elementwise_passes_are_their_numpy_expressions(oracle, geom):
 
 
 def test_launch_arithmetic_tables():
-    """The plans the GPU test's docstring tabulates (kernels/blas1.hip: hpgmg_hip_norm_max, ordered_sum, final_max_kernel)."""
+    """The plans the GPU test's docstring tabulates (kernels/blas1.hip: hpgmg_hip_norm_max, ordered_sum; kernels/reduce.hip: final_max_kernel)."""
     n = {g: R.norm_plan(*g) for g in GEOMS}
     assert [(n[g].path, n[g].nblk) for g in ((1, 1), (1, 6), (1, 16))] == [("absmax_small", 1), ("absmax_small", 9), ("absmax_small", 64)]
     assert (n[2, 8].per_box, n[2, 8].partials, n[2, 8].rows_in_flight, n[2, 8].row0_trips) == (16, 128, 1, 1)
