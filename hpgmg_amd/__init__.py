@@ -173,6 +173,9 @@ def _declare_driver_api(lib):
         # face fluxes of a solution
         "hpgmg_user_flux": (c_int, [vp, vp, vp, vp, vp, vp, c_int]),
         "hpgmg_dense_unpack_flux": (c_int, [vp, c_int, vp, c_dbl, c_int, vp, vp, vp, vp, vp, c_int]),
+        # coefficient sensitivities
+        "hpgmg_user_sensitivity": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_int]),
+        "hpgmg_dense_unpack_sensitivity": (c_int, [vp, c_int, c_int, vp, c_dbl, c_dbl, c_int, vp, vp, vp, vp, vp, vp, c_int]),
         # implicit time stepping
         "hpgmg_user_set_shift": (c_int, [vp, c_dbl]),
         "hpgmg_user_start": (c_int, [vp, vp, vp, vp, c_int, c_dbl, c_dbl]),

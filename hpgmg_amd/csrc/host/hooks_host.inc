@@ -351,6 +351,54 @@ __attribute__((weak)) int hpgmg_dense_unpack_flux(level_type *L, int x_id, const
   return bad ? HPGMG_DENSE_NOT_FINITE : 0;
 }
 
+/* ------------------------------------------------------------------ coefficient sensitivities (include/hpgmg_operators.h; DESIGN.md §11.9)
+ * G of the wall face `face` of the cell with state uc, adjoint lc and wall entry e */
+static double sens_wall_host(int face, int e, double uc, double lc, double w, double wn, double h, int mask, const double *gh, const double *kh, int *bad) {
+  const double gv = gh ? gh[e] : 0.0;
+  if (!isfinite(gv)) *bad = 1;
+  if ((mask >> face) & 1) return bnd_sens_masked(wn, kh ? kh[e] : 0.0, h, uc, gv, lc);
+  return bnd_sens_dirichlet(w, uc, gv, lc);
+}
+__attribute__((weak)) int hpgmg_dense_unpack_sensitivity(level_type *L, int u_id, int lam_id, const double *g, double a, double b, int mask, const double *wall,
+                                                         const double *kappa, double *d_alpha, double *d_beta_i, double *d_beta_j, double *d_beta_k, int where) {
+  if (L->num_ranks != 1 || u_id < 0 || u_id >= L->numVectors || lam_id < 0 || lam_id >= L->numVectors || !d_beta_i || !d_beta_j || !d_beta_k) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  if (mask < 0 || mask > 63 || (mask && !wall) || L->dim.i != L->dim.j || L->dim.i != L->dim.k || L->box_ghosts < 1) return -1;
+  const int walls = L->boundary_condition.type == BC_DIRICHLET;
+  if (!walls && (g || mask)) return -1;
+  const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t len = (size_t)6 * n * n, vol = (size_t)L->box_volume;
+  const size_t ni = (size_t)dense_extent(n, walls), nn = (size_t)n;      /* d_beta_i is (n, n, ni), d_beta_j (n, ni, n), d_beta_k (ni, n, n) */
+  const double w2 = bnd_sens_weight(b, L->h), w = bnd_weight(b, L->h), wn = bnd_weight_neumann(b, L->h), h = L->h;
+  double *gh = g ? bnd_download(g, len) : NULL, *kh = mask && kappa ? bnd_download(kappa, len) : NULL;
+  double *u = (double *)malloc(vol * 2 * sizeof(double)), *lam = u + vol;
+  int box, i, j, k, bad = 0;
+  for (box = 0; box < L->num_my_boxes; box++) {
+    const box_type *B = &L->my_boxes[box];
+    hpgmg_vector_download(u, B->vectors[u_id], vol);
+    hpgmg_vector_download(lam, B->vectors[lam_id], vol);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gi = B->low.i + i, gj = B->low.j + j, gk = B->low.k + k, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS;
+      const double uc = u[ijk], lc = lam[ijk];
+      const size_t cell = ((size_t)gk * nn + (size_t)gj) * nn + (size_t)gi;
+      double *qi = d_beta_i + ((size_t)gk * nn + (size_t)gj) * ni + (size_t)gi, *qj = d_beta_j + ((size_t)gk * ni + (size_t)gj) * nn + (size_t)gi;
+      double *qk = d_beta_k + cell;
+      if (d_alpha) d_alpha[cell] = bnd_sens_alpha(a, uc, lc);
+      if (walls && gi == 0) *qi = sens_wall_host(0, bnd_entry(n, 0, gi, gj, gk), uc, lc, w, wn, h, mask, gh, kh, &bad);
+      else *qi = bnd_sens_interior(w2, u[ijk - 1], uc, lam[ijk - 1], lc);
+      if (walls && gi == n - 1) qi[1] = sens_wall_host(1, bnd_entry(n, 1, gi, gj, gk), uc, lc, w, wn, h, mask, gh, kh, &bad);
+      if (walls && gj == 0) *qj = sens_wall_host(2, bnd_entry(n, 2, gi, gj, gk), uc, lc, w, wn, h, mask, gh, kh, &bad);
+      else *qj = bnd_sens_interior(w2, u[ijk - jS], uc, lam[ijk - jS], lc);
+      if (walls && gj == n - 1) qj[nn] = sens_wall_host(3, bnd_entry(n, 3, gi, gj, gk), uc, lc, w, wn, h, mask, gh, kh, &bad);
+      if (walls && gk == 0) *qk = sens_wall_host(4, bnd_entry(n, 4, gi, gj, gk), uc, lc, w, wn, h, mask, gh, kh, &bad);
+      else *qk = bnd_sens_interior(w2, u[ijk - kS], uc, lam[ijk - kS], lc);
+      if (walls && gk == n - 1) qk[nn * nn] = sens_wall_host(5, bnd_entry(n, 5, gi, gj, gk), uc, lc, w, wn, h, mask, gh, kh, &bad);
+    }
+  }
+  free(u); free(gh); free(kh);
+  return bad ? HPGMG_DENSE_NOT_FINITE : 0;
+}
+
 /* ------------------------------------------------------------------ the implicit time march (include/hpgmg_operators.h; DESIGN.md §11.8)
  * The two cell expressions of include/hpgmg_step_math.h over the interior cells, box by box; weak like the dense pair above (the HIP plugin:
  * host/plugin_step.c).  A box goes up whole, so a vector that is only written (u_old) is downloaded first: its ghost and padding cells keep

@@ -1,6 +1,7 @@
 /*
- * plugin_dense.c -- hpgmg_dense_pack / hpgmg_dense_unpack / hpgmg_dense_unpack_flux of the operator plugin (include/hpgmg_operators.h): one launch
- * of kernels/dense_io.hip per array (the three flux arrays: one of kernels/dense_flux.hip).  A device array is read / written in place; a host array is copied once into the level's staging buffer
+ * plugin_dense.c -- hpgmg_dense_pack / hpgmg_dense_unpack / hpgmg_dense_unpack_flux / hpgmg_dense_unpack_sensitivity of the operator plugin
+ * (include/hpgmg_operators.h): one launch of kernels/dense_io.hip per array (the three flux arrays: one of kernels/dense_flux.hip; the four
+ * sensitivity arrays: one of kernels/dense_sensitivity.hip).  A device array is read / written in place; a host array is copied once into the level's staging buffer
  * (allocated on first use, freed with the level) and packed from there, or unpacked into it and copied out once.  They replace the weak
  * host defaults of host/hooks_host.inc, which go box by box through hpgmg_vector_upload / download.  The boundary-value hooks below likewise
  * (their arithmetic: include/hpgmg_boundary_math.h, shared with the kernels and the host defaults).
@@ -80,6 +81,35 @@ int hpgmg_dense_unpack_flux(level_type *L, int x_id, const double *g, double b, 
   HIP_OK(hpgmg_hip_memcpy_d2h(flux_i, stage, len * sizeof(double)));
   HIP_OK(hpgmg_hip_memcpy_d2h(flux_j, stage + len, len * sizeof(double)));
   HIP_OK(hpgmg_hip_memcpy_d2h(flux_k, stage + 2 * len, len * sizeof(double)));
+  return status;
+}
+
+/* coefficient sensitivities of vectors u_id and lam_id: one launch of kernels/dense_sensitivity.hip for the four arrays, written in
+ * place when they are device arrays, else into the staging buffer (sized for the four) and copied out, one copy each */
+int hpgmg_dense_unpack_sensitivity(level_type *L, int u_id, int lam_id, const double *g, double a, double b, int mask, const double *wall,
+                                   const double *kappa, double *d_alpha, double *d_beta_i, double *d_beta_j, double *d_beta_k, int where) {
+  int status = 0;
+  if (L->num_ranks != 1 || u_id < 0 || u_id >= L->numVectors || lam_id < 0 || lam_id >= L->numVectors || !d_beta_i || !d_beta_j || !d_beta_k) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  if (mask < 0 || mask > 63 || (mask && !wall) || L->dim.i != L->dim.j || L->dim.i != L->dim.k || L->box_ghosts < 1) return -1;
+  if (L->boundary_condition.type != BC_DIRICHLET && (g || mask)) return -1;
+  backend_t *B = hp_backend_of(L);
+  const double w2 = bnd_sens_weight(b, L->h), w = bnd_weight(b, L->h), wn = bnd_weight_neumann(b, L->h);
+  if (where == HPGMG_WHERE_PLUGIN) {
+    HIP_OK(hpgmg_hip_dense_unpack_sensitivity(&B->dev, u_id, lam_id, g, a, w2, w, wn, L->h, mask, mask ? kappa : NULL, d_alpha, d_beta_i, d_beta_j,
+                                              d_beta_k, &status));
+    return status;
+  }
+  size_t n[3];
+  dense_extents(L, HPGMG_DENSE_FACE_I, n);
+  const size_t len = n[0] * n[1] * n[2], cells = (size_t)L->dim.i * L->dim.j * L->dim.k;      /* of each face array (the level is a cube), of d_alpha */
+  double *stage = dense_stage(B, 3 * len + cells);
+  HIP_OK(hpgmg_hip_dense_unpack_sensitivity(&B->dev, u_id, lam_id, g, a, w2, w, wn, L->h, mask, mask ? kappa : NULL, d_alpha ? stage + 3 * len : NULL,
+                                            stage, stage + len, stage + 2 * len, &status));
+  HIP_OK(hpgmg_hip_memcpy_d2h(d_beta_i, stage, len * sizeof(double)));
+  HIP_OK(hpgmg_hip_memcpy_d2h(d_beta_j, stage + len, len * sizeof(double)));
+  HIP_OK(hpgmg_hip_memcpy_d2h(d_beta_k, stage + 2 * len, len * sizeof(double)));
+  if (d_alpha) HIP_OK(hpgmg_hip_memcpy_d2h(d_alpha, stage + 3 * len, cells * sizeof(double)));
   return status;
 }
 

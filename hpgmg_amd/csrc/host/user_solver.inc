@@ -14,6 +14,7 @@ struct hpgmg_user_solver {
   int n, bc, verbose;
   int x_id;                    /* the finest level's one extra vector: u0 of a warm start, the operand of apply */
   int operator_ok, rhs_ok;     /* 0 after a set_coefficients / set_rhs that was refused part way */
+  int coef_given;              /* 1 once a set_coefficients succeeded (until then the coefficients are create's ones: sensitivity has no arrays to differentiate) */
   double mean_shift;           /* what the last set_rhs subtracted from f */
   int bnd;                     /* 1: f was set with boundary values (set_rhs_dirichlet): an F-cycle runs with the hook below */
   double **bnd_g, **bnd_phi;   /* per level: the boundary values g_l and their lift flux phi_l (plugin memory; allocated on first use) */
@@ -239,7 +240,7 @@ int hpgmg_user_set_coefficients_robin(hpgmg_user_solver *us, const double *alpha
   if (helmholtz) st |= e;
   if (st) { USER_LOUD(); return user_pack_status(st); }
   user_rebuild(us);
-  us->operator_ok = 1;
+  us->operator_ok = us->coef_given = 1;
   USER_LOUD();
   return HPGMG_USER_OK;
 refused:
@@ -460,6 +461,31 @@ int hpgmg_user_flux(hpgmg_user_solver *us, const double *u, const double *g, dou
     exchange_boundary(L, us->x_id, stencil_get_shape());      /* the neighbours across box faces and the periodic wrap; no ghost outside the domain is read */
     st = user_pack_status(hpgmg_dense_unpack_flux(L, us->x_id, g ? us->app_g : NULL, s->b, us->mask, us->mask ? us->wall[0] : NULL, USER_KAPPA(us, 0),
                                                   flux_i, flux_j, flux_k, where));
+  }
+  USER_LOUD();
+  return st;
+}
+
+/* coefficient sensitivities (DESIGN.md §11.9): u into the operand vector, lam into VECTOR_R (apply's scratch: every solve sets it from f before
+ * reading it), then one pass over both.  Nothing else is written: VECTOR_U, VECTOR_F, rhs_ok and a live march stay as they were. */
+int hpgmg_user_sensitivity(hpgmg_user_solver *us, const double *u, const double *lam, const double *g, double *d_alpha, double *d_beta_i, double *d_beta_j,
+                           double *d_beta_k, int where) {
+  hpgmg_solver *s = &us->s;
+  level_type *L = &s->level_h;
+  if (!u || !lam || !d_beta_i || !d_beta_j || !d_beta_k || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
+  if ((d_alpha != NULL) != (s->a != 0.0)) return HPGMG_USER_BAD_ARGUMENT;
+  if (g && us->bc != BC_DIRICHLET) return HPGMG_USER_UNSUPPORTED;
+  if (!us->operator_ok || !us->coef_given) return HPGMG_USER_NOT_READY;      /* no coefficient arrays (yet, or after a refused set_coefficients) */
+  if (!user_config_ok()) return HPGMG_USER_CONFLICT;
+  USER_QUIET(us);
+  int st = user_pack_status(hpgmg_dense_pack(L, us->x_id, u, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
+  if (st == HPGMG_USER_OK) st = user_pack_status(hpgmg_dense_pack(L, VECTOR_R, lam, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
+  if (st == HPGMG_USER_OK) {
+    if (g) { user_bnd_alloc(us); user_bnd_take(us, us->app_g, g, where); }
+    exchange_boundary(L, us->x_id, stencil_get_shape());      /* the neighbours across box faces and the periodic wrap; no ghost outside the domain is read */
+    exchange_boundary(L, VECTOR_R, stencil_get_shape());
+    st = user_pack_status(hpgmg_dense_unpack_sensitivity(L, us->x_id, VECTOR_R, g ? us->app_g : NULL, s->a, s->b, us->mask, us->mask ? us->wall[0] : NULL,
+                                                         USER_KAPPA(us, 0), d_alpha, d_beta_i, d_beta_j, d_beta_k, where));
   }
   USER_LOUD();
   return st;

@@ -44,8 +44,21 @@ solver created with a != 0: one step is one solve with a = 1 / (theta dt), which
 diagonal is rebuilt, no coefficient array is packed).  step(f, boundary=g) advances to the next time, f and g being those of that time, with
 V-cycles warm-started from the state; dt= / theta= change the step.  The state u and the rate w stay in the library, on the device, between
 calls: get_solution() and rate() return them, StepInfo.rate is max |w| and StepInfo.t the time since start().  The rate is exact for the state
-the solve stopped at, whatever rtol.  set_coefficients, set_rhs and solve end a march; get_solution, rate, apply, flux and set_shift do not.
-DESIGN.md §11.8.
+the solve stopped at, whatever rtol.  set_coefficients, set_rhs and solve end a march; get_solution, rate, apply, flux, sensitivity and
+set_shift do not.  DESIGN.md §11.8.
+
+Sensitivities: apply(u, boundary=g) = A0 u - T(g) is affine in alpha, in every beta entry and in a Neumann / Robin wall's own beta.
+sensitivity(u, lam, boundary=g) returns (d_alpha, d_beta_i, d_beta_j, d_beta_k), G_p = d/dp sum_c lam_c apply(u, boundary=g)_c for every
+coefficient entry p, in the shapes of set_coefficients' arguments (d_alpha is None on a Poisson solver).  With t = kappa h:
+
+    alpha[c]                                                              a u_c lam_c
+    face between cells lo and hi = lo + 1 (box-to-box, periodic wrap)     (b/h^2) (u_lo - u_hi) (lam_lo - lam_hi)
+    Dirichlet wall face of cell c, either side                            (b/h^2) 2 (u_c - g) lam_c
+    Neumann / Robin wall face of cell c, either side (Neumann: kappa = 0) (b/h) (2/(2 + t)) (kappa u_c - g) lam_c
+
+None of them reads a beta.  If J depends on the solution u of A u = f + T(g), and lam solves A lam = dJ/du with no boundary data (the operator is
+symmetric: the adjoint solve is solve()), then dJ/dp = -G_p and dJ/df = lam -- also on the singular solvers, whose solve subtracts the mean of
+any right-hand side.  hpgmg_amd.autograd.solve wraps exactly that as a differentiable torch function.  DESIGN.md §11.9.
 
 NumPy arrays take the host path.  torch tensors on the library's GPU (float64, contiguous) are read and written in place, and results come
 back as tensors on that device.  torch must be imported before this package loads its libraries: both bring a HIP runtime
@@ -142,6 +155,7 @@ class Solver:
         self._ptr = None
         self._dt = self._theta = None       # of the last start() / step()
         self._t = 0.0                       # time since start()
+        self.coefficient_version = 0        # counts the calls that may change the operator (set_coefficients, set_shift, a march's new a): autograd.solve
         out = ctypes.c_void_p()
         if faces is None:
             st = self.lib.hpgmg_user_create(self.n, int(box_dim or 0), _BC[bc], _OPERATOR[operator], _SMOOTHER[smoother], self.a, self.b,
@@ -270,6 +284,7 @@ class Solver:
         if robin is not None and not self.robin_faces:
             raise ValueError("robin: this solver has no 'convective' face (bc=)")
         pi, where, kind = self._arg(beta_i, self._face_shape(0), "beta_i")
+        self.coefficient_version += 1
         pj, _, _ = self._arg(beta_j, self._face_shape(1), "beta_j", kind)
         pk, _, _ = self._arg(beta_k, self._face_shape(2), "beta_k", kind)
         pa = self._arg(alpha, (self.n,) * 3, "alpha", kind)[0] if alpha is not None else None
@@ -427,6 +442,40 @@ class Solver:
         self._check(st, "u, boundary" if boundary is not None else "u")
         return out
 
+    def sensitivity(self, u, lam, boundary=None, out=None):
+        """(d_alpha, d_beta_i, d_beta_j, d_beta_k): G_p = d/dp sum_c lam_c apply(u, boundary)_c for every coefficient entry p, in the shapes of
+        set_coefficients' arguments (module docstring); d_alpha is None on a Poisson solver (a = 0).  With u the solution for
+        `boundary` and lam the solution of A lam = dJ/du without boundary data, dJ/dp = -G_p.  boundary: the data u was solved with (None: zero
+        data).  out: an optional 4-tuple of arrays of u's kind to write into (out[0] None on a Poisson solver).  NumPy arrays or tensors
+        according to u."""
+        pu, where, kind = self._arg(u, (self.n,) * 3, "u")
+        pl = self._arg(lam, (self.n,) * 3, "lam", kind)[0]
+        pg = self._boundary(boundary, kind) if boundary is not None else None
+        helm = self.a != 0.0
+        shapes = [(self.n,) * 3] + [self._face_shape(axis) for axis in range(3)]
+        if out is None:
+            if kind == "torch":
+                import torch
+                out = tuple(torch.empty(shape, dtype=torch.float64, device=u.device) for shape in shapes)
+            else:
+                out = tuple(np.empty(shape, dtype=np.float64) for shape in shapes)
+            if not helm:
+                out = (None,) + out[1:]
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 4:
+                raise ValueError("out: expected a 4-tuple (d_alpha, d_beta_i, d_beta_j, d_beta_k) of arrays")
+            out = tuple(out)
+            if (out[0] is None) == helm:
+                raise ValueError("out[0]: d_alpha is required when a != 0 (Helmholtz), must be None when a == 0 (Poisson)")
+        po = [None if q is None else self._arg(q, shape, f"out[{slot}]", kind)[0] for slot, (q, shape) in enumerate(zip(out, shapes))]
+        self._sync_torch(kind)
+        st = self.lib.hpgmg_user_sensitivity(self._ptr, pu, pl, pg, po[0], po[1], po[2], po[3], where)
+        if st == H.USER_NOT_FINITE:
+            named = [("u", u, 0.0, False), ("lam", lam, 0.0, False)] + ([("boundary", boundary, 0.0, False)] if boundary is not None else [])
+            self._check(st, self._first_bad(named, st))
+        self._check(st, "u, lam, boundary" if boundary is not None else "u, lam")
+        return out
+
     # ---- implicit time stepping (module docstring; DESIGN.md §11.8)
     def set_shift(self, a):
         """A new a (> 0) for a Helmholtz solver: every level's operator is rebuilt from the coefficients already set, without packing an array.
@@ -435,6 +484,7 @@ class Solver:
             raise ValueError("a: this solver is Poisson (a = 0) and stays so (create it with a != 0)")
         if isinstance(a, bool) or not isinstance(a, (int, float, np.integer, np.floating)) or not np.isfinite(a) or not a > 0.0:
             raise ValueError(f"a: {a!r} must be a finite number > 0")
+        self.coefficient_version += 1
         self._check(self.lib.hpgmg_user_set_shift(self._ptr, float(a)), "a")
         self.a = float(a)
 
@@ -461,6 +511,7 @@ class Solver:
         pf = self._arg(f, (self.n,) * 3, "f", kind)[0]
         pg = self._boundary(boundary, kind) if boundary is not None else None
         self._sync_torch(kind)
+        self.coefficient_version += 1        # the march sets a = 1 / (theta dt)
         st = self.lib.hpgmg_user_start(self._ptr, pu, pf, pg, where, dt, theta)
         if st == H.USER_NOT_FINITE:
             named = [("u", u, 0.0, False), ("f", f, 0.0, False)] + ([("boundary", boundary, 0.0, False)] if boundary is not None else [])
@@ -484,6 +535,8 @@ class Solver:
         pg = self._boundary(boundary, kind) if boundary is not None else None
         self._sync_torch(kind)
         info, rate = H.UserInfo(), ctypes.c_double(0.0)
+        if 1.0 / (theta * dt) != self.a:
+            self.coefficient_version += 1
         st = self.lib.hpgmg_user_step(self._ptr, pf, pg, where, dt, theta, float(rtol), ctypes.byref(info), ctypes.byref(rate))
         if st == H.USER_NOT_FINITE:
             named = [("f", f, 0.0, False)] + ([("boundary", boundary, 0.0, False)] if boundary is not None else [])

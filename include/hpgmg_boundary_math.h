@@ -1,7 +1,7 @@
 /*
  * hpgmg_boundary_math.h -- INTERNAL: the arithmetic of the dense-array boundary hooks (include/hpgmg_operators.h hpgmg_dense_*, hpgmg_boundary_*;
  * DESIGN.md §11.1, §11.2, §11.5, §11.6), written once for the host defaults (host/hooks_host.inc), the HIP plugin (host/plugin_dense.c) and its kernels
- * (kernels/dense_boundary.hip, kernels/dense_flux.hip).  Not part of the C ABI: it declares nothing extern and no caller of the library includes it.
+ * (kernels/dense_boundary.hip, kernels/dense_flux.hip, kernels/dense_sensitivity.hip).  Not part of the C ABI: it declares nothing extern and no caller of the library includes it.
  *
  * The GPU tests hold the HIP build to the host defaults bit for bit, and every build has -ffp-contract=off, so the written order of each
  * floating-point expression here IS the contract: change one and both sides change together.  Whatever reads a vector of the level (the coarse
@@ -67,6 +67,24 @@ HPGMG_BND_FN double bnd_flux_masked(double b, double wall, double kappa, double 
   const double t = kappa * h;
   const double Q = ((b * wall) * (2.0 / (2.0 + t))) * (kappa * u_c - g);
   return high ? Q : -Q;
+}
+
+/* Coefficient sensitivities (hpgmg_dense_unpack_sensitivity): G_p = d/dp sum_c lam_c (A0 u - T(g))_c for every coefficient entry p,
+ * the bilinear twin of the fluxes above.  None reads a beta: the operator is affine in each.  w2 = bnd_sens_weight(b, h), w = bnd_weight(b, h),
+ * wn = bnd_weight_neumann(b, h), t = kappa * h.
+ *   alpha of cell c:                              a * (u_c * l_c)
+ *   a face between two cells (the wrap included): w2 * ((u_lo - u_hi) * (l_lo - l_hi))
+ *   a Dirichlet wall face of cell c, either side: (w * (u_c - g)) * l_c
+ *   a masked wall face of cell c, either side:    ((wn * (2.0 / (2.0 + t))) * (kappa * u_c - g)) * l_c      (the wall's own beta)
+ * The first two are symmetric in u and lam bit for bit: the product of the two states (of their differences) is formed first.  kappa = 0.0 is the
+ * Neumann wall bit for bit: a factor wn * 1.0 and +-0.0 - g. */
+HPGMG_BND_FN double bnd_sens_weight(double b, double h) { return b * (1.0 / (h * h)); }
+HPGMG_BND_FN double bnd_sens_alpha(double a, double u_c, double l_c) { return a * (u_c * l_c); }
+HPGMG_BND_FN double bnd_sens_interior(double w2, double u_lo, double u_hi, double l_lo, double l_hi) { return w2 * ((u_lo - u_hi) * (l_lo - l_hi)); }
+HPGMG_BND_FN double bnd_sens_dirichlet(double w, double u_c, double g, double l_c) { return (w * (u_c - g)) * l_c; }
+HPGMG_BND_FN double bnd_sens_masked(double wn, double kappa, double h, double u_c, double g, double l_c) {
+  const double t = kappa * h;
+  return ((wn * (2.0 / (2.0 + t))) * (kappa * u_c - g)) * l_c;
 }
 
 /* S(c) of hpgmg_boundary_lift: the four finer entries under each face entry of coarse cell (gi,gj,gk) of an n-cube, faces in order */

@@ -133,6 +133,19 @@ int  hpgmg_user_set_coefficients_robin(hpgmg_user_solver *s, const double *alpha
  * HPGMG_USER_UNSUPPORTED).  u or a g entry not finite: HPGMG_USER_NOT_FINITE; after a refused set_coefficients: HPGMG_USER_NOT_READY.  Only the
  * solver's operand vector (apply's) is written: the solution, the right-hand side and the state of the last set_rhs stay as they were. */
 int  hpgmg_user_flux(hpgmg_user_solver *s, const double *u, const double *g, double *flux_i, double *flux_j, double *flux_k, int where);
+/* Coefficient sensitivities.  Write apply(u; g) for apply_dirichlet(u, g) = A0 u - T(g): it is affine in alpha, in every beta entry and
+ * in a Neumann / Robin wall's own beta.  For a state u and an adjoint lam, G_p = d/dp sum_c lam_c apply(u; g)_c for every coefficient entry p, into
+ * d_alpha (N,N,N) and d_beta_i / j / k in the shapes of the beta arrays.  With t = kappa h:
+ *   alpha[c]: a u_c lam_c;   the face between cells lo and hi = lo + 1 (box-to-box and the periodic wrap included): (b/h^2) (u_lo - u_hi) (lam_lo - lam_hi);
+ *   a Dirichlet wall face of cell c: (b/h^2) 2 (u_c - g) lam_c;   a Neumann / Robin wall face: (b/h) (2/(2 + t)) (kappa u_c - g) lam_c   (kappa = 0: Neumann).
+ * None reads a beta.  If J depends on the solution u of A u = f + T(g) and A lam = dJ/du with homogeneous data, then dJ/dp = -G_p and dJ/df = lam
+ * (also for the singular solvers, whose solve subtracts the mean of any right-hand side).  u, lam, g and the outputs are in the same memory (where);
+ * g == NULL: zero data (a periodic solver takes no other: HPGMG_USER_UNSUPPORTED).  d_alpha must be given exactly when a != 0, the others always
+ * (else HPGMG_USER_BAD_ARGUMENT).  u, lam or a g entry not finite: HPGMG_USER_NOT_FINITE; before the first set_coefficients (there
+ * are no coefficient arrays yet) and after a refused one: HPGMG_USER_NOT_READY.  Only the solver's operand vector and the scratch vector apply writes are written: the solution, the right-hand side, the state of the last set_rhs
+ * and a live march stay as they were. */
+int  hpgmg_user_sensitivity(hpgmg_user_solver *s, const double *u, const double *lam, const double *g, double *d_alpha, double *d_beta_i, double *d_beta_j,
+                            double *d_beta_k, int where);
 /* Implicit time stepping:  alpha du/dt = b div(beta grad u) + f  with the walls and data g of the solver, by the theta scheme
  *   alpha (u1 - u0) / dt = theta w1 + (1 - theta) w0,   w = f - L(u; g) = alpha du/dt,   L(u; g) = apply_dirichlet(u, g) - a alpha u,
  * 1/2 <= theta <= 1 (1: backward Euler, 1/2: Crank-Nicolson).  One step is one solve with the operator for a = 1 / (theta dt).  The library keeps the
@@ -149,7 +162,7 @@ int  hpgmg_user_flux(hpgmg_user_solver *s, const double *u, const double *g, dou
  *   info as hpgmg_user_solve fills it (norm_of_f = |F|), *rate = max |w|.  w is exact for the u the solve stopped at, whatever rtol.  f or g not finite:
  *   HPGMG_USER_NOT_FINITE, and u, w and the march are as before the call.  Without a live march: HPGMG_USER_NOT_READY.
  * get_rate: w into an (N,N,N) array.  get_solution returns the state u.
- * set_coefficients*, set_rhs* and solve end a march (step: HPGMG_USER_NOT_READY until the next start); get_solution, apply*, flux and set_shift do
+ * set_coefficients*, set_rhs* and solve end a march (step: HPGMG_USER_NOT_READY until the next start); get_solution, apply*, flux, sensitivity and set_shift do
  * not.  After a step the solver holds no right-hand side of the caller's: solve needs a set_rhs first. */
 int  hpgmg_user_set_shift(hpgmg_user_solver *s, double a);
 int  hpgmg_user_start(hpgmg_user_solver *s, const double *u, const double *f, const double *g, int where, double dt, double theta);

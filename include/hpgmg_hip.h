@@ -401,6 +401,15 @@ int hpgmg_hip_boundary_interp_robin(const hpgmg_hip_level *L, int id, const hpgm
  * synchronises. */
 int hpgmg_hip_dense_unpack_flux(const hpgmg_hip_level *L, int id, const double *g, double b, double wq, double h, int mask, const double *wall,
                                 const double *kappa, double *flux_i, double *flux_j, double *flux_k, int *status);
+/* coefficient sensitivities of vectors u_id and lam_id (include/hpgmg_operators.h hpgmg_dense_unpack_sensitivity; kernels/dense_sensitivity.hip;
+ * DESIGN.md §11.9): ONE launch writes the four DEVICE arrays d_alpha (the level's cells; nullptr: not written) and d_beta_i / j / k (each one longer
+ * along its axis unless the level is periodic).  The level is a cube with ghost zones whose box-to-box part holds both vectors' neighbours; g, kappa
+ * are DEVICE boundary arrays (g nullptr: zero data; kappa read under mask only, nullptr: Neumann walls); a the operator's a, w2 = b * (1.0 / (h * h)),
+ * w = (2.0 * b) * (1.0 / (h * h)), wn = b * (1.0 / h), h the level's.  The grid is capped at 4096 workgroups of 256, the rest by grid stride.
+ * Validates the g values read (HPGMG_DENSE_NOT_FINITE in *status) and synchronises. */
+int hpgmg_hip_dense_unpack_sensitivity(const hpgmg_hip_level *L, int u_id, int lam_id, const double *g, double a, double w2, double w, double wn,
+                                       double h, int mask, const double *kappa, double *d_alpha, double *d_beta_i, double *d_beta_j,
+                                       double *d_beta_k, int *status);
 /* the two passes of the implicit time march (include/hpgmg_operators.h hpgmg_step_rhs / hpgmg_step_rate; kernels/dense_step.hip), one
  * launch each over the interior cells of every box; num_vectors: the vectors a box of the level holds (the ids and VECTOR_ALPHA are checked against
  * it).  step_rhs: F = F + ((a alpha) u + c w), u_old = u.  step_rate: w = (r + (a alpha) (u - u_old)) - c w, and *max_abs = max |w| (0.0 <= it; a

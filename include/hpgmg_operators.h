@@ -203,6 +203,18 @@ void    hpgmg_boundary_interp_robin(level_type *fine, int id, level_type *coarse
  * plugin overrides it with one launch for the three arrays (kernels/dense_flux.hip). */
 int     hpgmg_dense_unpack_flux(level_type *level, int x_id, const double *g, double b, int mask, const double *wall, const double *kappa,
                                 double *flux_i, double *flux_j, double *flux_k, int where);
+/* Coefficient sensitivities of a state u (vector u_id) and an adjoint lam (vector lam_id): for every coefficient entry p
+ * G_p = d/dp sum_c lam_c (A0 u - T(g))_c, into d_alpha (N,N,N; NULL on a Poisson level: not written) and d_beta_i / j / k in the shapes of the beta
+ * arrays (as the flux arrays above).  With w2 = b * (1.0 / (h * h)), w = (2.0 * b) * (1.0 / (h * h)), wn = b * (1.0 / h), t = kappa * h:
+ *   alpha of cell c:  a * (u_c * lam_c);   between cells lo and hi = lo + 1 (the periodic wrap included):  w2 * ((u_lo - u_hi) * (lam_lo - lam_hi));
+ *   a Dirichlet wall face of cell c:  (w * (u_c - g)) * lam_c;   a masked wall face:  ((wn * (2.0 / (2.0 + t))) * (kappa * u_c - g)) * lam_c
+ * (include/hpgmg_boundary_math.h bnd_sens_*; either side alike).  No beta is read: a masked wall's entry is the derivative to the wall's own beta,
+ * which `wall` holds; `wall` is required when mask != 0, as above, and not read.  Ownership, g, kappa, where, the refusals (-1) and the returned status
+ * bits (HPGMG_DENSE_NOT_FINITE: an entry of g that was read is not finite) are hpgmg_dense_unpack_flux's.  The caller has filled the box-to-box ghost
+ * zones of BOTH vectors (exchange_boundary); no ghost outside the domain is read.  Weak host default in host/hooks_host.inc; the HIP plugin overrides it
+ * with one launch for the four arrays (kernels/dense_sensitivity.hip). */
+int     hpgmg_dense_unpack_sensitivity(level_type *level, int u_id, int lam_id, const double *g, double a, double b, int mask, const double *wall,
+                                       const double *kappa, double *d_alpha, double *d_beta_i, double *d_beta_j, double *d_beta_k, int where);
 /* The two streaming passes of the implicit time march of the user-problem API (hpgmg_user_start / hpgmg_user_step, include/hpgmg_fv.h)
  * over the interior cells of every box of a Helmholtz level (alpha = VECTOR_ALPHA); ghost and padding cells are neither read nor written:
  *   step_rhs:   F = F + ((a * alpha) * u + c * w) ;  u_old = u              (F holds f + T(g) on entry; a = 1 / (theta dt), c = (1 - theta) / theta)
