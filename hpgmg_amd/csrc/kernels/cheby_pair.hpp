@@ -19,6 +19,9 @@
 //     written beforehand by cheby_pair_edge_kernel (the columns next to interior tile edges, 0.8 % of the cells);
 //   * the domain boundary is the in-register Dirichlet rule ghost = -centre (apply_BCs_p1), applied to x0 for
 //     the first sweep and to x1 for the second, as the reference does between sweeps.
+//   * the march runs in segments (one box, away from the ends of the chunk and of the domain): the boxes and the base of every stream are looked up once per
+//     segment, a step inside it adds kS to a plane offset and tests nothing about the plane; the first step, the steps at a box face and the last ones -- and
+//     every step of the multi-rank (REMOTE) instances -- take the general form.
 // x1/x2 go to vectors distinct from x0/xm1 (plugin-private scratch for the first pair of a smooth() call), since
 // neighbouring workgroups still read x0/xm1 on their halo.
 #pragma once
@@ -83,6 +86,14 @@ __device__ __forceinline__ void pst(double *p, p2 v) { d2v w; w.x = v.x; w.y = v
 __device__ __forceinline__ double gld1(const double *p) { return *as_global(p); }      // one double of device memory
 __device__ __forceinline__ p2 pneg(p2 v) { return p2{-v.x, -v.y}; }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// Segments of the march (below): a pointer that is the same for every lane, held as such (a scalar register pair) -- what comes out of the LDS box tables is not
+// known to be -- and a lane's pair / single value at it plus an unsigned per-lane ELEMENT offset: the scalar base + vector offset form of common.hpp's gld / gst
+template <class T> __device__ __forceinline__ T *uni_ptr(T *p) {
+  const unsigned long long v = (unsigned long long)p;
+  return (T *)(((unsigned long long)(unsigned)uni((int)(v >> 32)) << 32) | (unsigned long long)(unsigned)uni((int)(unsigned)v));
+}
+__device__ __forceinline__ p2 pld_so(const double *base, unsigned e) { const d2v v = *(gd2cptr)((gcbytes)as_global(base) + e * 8u); return p2{v.x, v.y}; }
+__device__ __forceinline__ void pst_so(double *base, unsigned e, p2 v) { d2v w; w.x = v.x; w.y = v.y; *(gd2ptr)((gbytes)as_global(base) + e * 8u) = w; }
 
 // Coefficient streams.  fp64 mode reads the level's own vectors; the mixed-precision smoother (BASELINE config 5) reads
 // fp32 copies -- 4 instead of 8 bytes per value on 5 of the 8 input streams -- and widens them to double, so all
@@ -101,6 +112,22 @@ template <bool C32> struct CoefStream {
     return pld(p64 + off);
   }
   __device__ __forceinline__ double one(int off) const { return C32 ? (double)*(const float __attribute__((address_space(1))) *)(p32 + off) : gld1(p64 + off); }
+};
+
+// The same stream inside one segment of the march: the base of the box (moved by `shift` elements) is wave-uniform and looked up once, a lane adds its
+// unsigned element offset (of the fp32 copies' layout with C32, of the level vectors' otherwise)
+template <bool C32> struct CoefSeg {
+  const double *p64; const float *p32;
+  __device__ __forceinline__ CoefSeg(const hpgmg_hip_level &L, const PairArgs &A, int box, int vec_id, int slot, long long shift = 0) {
+    const size_t first = (size_t)L.ghosts * (size_t)(1 + L.jStride + L.kStride);
+    if (C32) { p32 = uni_ptr(A.c32_base[box] + (size_t)slot * (size_t)L.volume + first + shift); p64 = nullptr; }
+    else     { p64 = uni_ptr((const double *)L.box_base[box] + (size_t)vec_id * (size_t)L.volume + first + shift); p32 = nullptr; }
+  }
+  __device__ __forceinline__ p2 pair(unsigned e) const {
+    if (C32) { typedef float __attribute__((ext_vector_type(2))) f2v; const f2v f = *(const f2v __attribute__((address_space(1))) *)((gcbytes)p32 + e * 4u); return p2{(double)f.x, (double)f.y}; }
+    return pld_so(p64, e);
+  }
+  __device__ __forceinline__ double one(unsigned e) const { return C32 ? (double)*(const float __attribute__((address_space(1))) *)((gcbytes)p32 + e * 4u) : gld(as_global(p64), e * 8u); }
 };
 
 // coefficients of one plane for a lane's two cells
@@ -305,6 +332,9 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
 #else
 #define TL_MARK() do { } while (0)
 #endif
+  // ---- the march.  A pass of this loop is one plane step in its general form: the box and the address of every stream from the plane number, every end condition
+  // tested.  The REMOTE instances take all their steps so; the others the first step, the steps next to a box face and the last ones -- the rest run in the segment
+  // that follows a general step (below)
   for (int p = pstart; p <= P1 && p < khi; p++) {
     const int box = box_of(bi_, bj_, p), off = row_off + plane_off(p);
     TL_MARK();                                                   // 0: step begins
@@ -405,6 +435,141 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
     __syncthreads();
     TL_MARK();                                                   // 4: barrier passed
     x0m = x0c; x0c = x0p; x1m2 = x1m1; x1m1 = x1c; far_c = far_n; bj_c = bj_n; qp = qc;
+
+    if constexpr (!REMOTE) {
+      // ---- the march in SEGMENTS.  A segment is a run of steps p for which the planes p-1, p, p+1 lie in one box, none of them is outside the domain or the
+      // first / last of the march, and x2 is due on p-1:  have_next, above_in, x0plane(p-1), in_dom(p-2) and q >= K0 all hold, the lower beta_k face is the
+      // previous step's upper one, and every stream stays in its box.  The box-table lookups and the base of every stream are made once per segment -- wave-uniform
+      // pointers; a lane keeps ONE element offset per layout (level vectors; scratch vectors and fp32 copies differ from it only with narrow boxes) -- and a step
+      // moves the plane offset by kS, nothing else.  No load of a segment's step sits behind a test of p.  What remains conditional is the role of the wave (halo
+      // rows, the slab's top row, lanes 0 / 63 at a tile edge) and the launch (c1a, keep_x1): the same for every step.  Steps outside a segment are passes of the loop above.
+      // The bounds come from K0, KCs, bd, Dk alone -- workgroup-uniform -- and every step of either kind passes exactly one barrier.
+      const int pend = (P1 < khi - 1) ? P1 : khi - 1;               // the last step: have_next(p) is  p + 1 <= pend
+      const int ps = p + 1;                                          // the segment, if any, begins after the step just made
+      int lk = ps % bd;
+      int last = ps - lk + bd - 2;
+      if (last > pend - 1) last = pend - 1;
+      if (lk < 1 || ps - 1 < K0 || ps < 2 || last < ps) continue;
+      p = ps;
+      // ---- segment p .. last
+      // what a step asks about the wave and the lane, not about the plane
+      const bool jm_wall = !x0row(gj - 1), jp_wall = !x0row(gj + 1), jm_far = (w == 0), jp_far = (w == NRs + 1);
+      const bool farw = far_lo || far_hi;
+      const bool bjhi_mem = (w == NRs + 1 || gj + 1 >= jhi || ((lj + 1) == bd));
+      const bool x2_jm_wall = (gj - 1 < jlo), x2_jp_wall = (gj + 1 >= jhi);
+      const bool read_xm1 = (SM == PAIR_CHEBY && A.c1a != 0.0), store_x1 = (SM == PAIR_CHEBY && A.keep_x1 && row_out);
+      const double fil = (lane == 0 && left_dom) ? -2.0 : -1.0, fih = (lane == 63 && right_dom) ? -2.0 : -1.0, fjl = (gj - 1 < 0) ? -2.0 : -1.0, fjh = (gj + 1 >= A.Dj) ? -2.0 : -1.0;
+      const double nbh2 = (-A.b) * A.h2inv;
+      // a lane's element offsets inside a plane of its box, for level vectors / scratch vectors / the coefficient streams.  (Formed HERE, from pinned copies of their
+      // inputs: as values of the whole march they would be held in registers across the general steps too, which the narrow-box and 16-wave instances have none to spare for)
+      int ro = row_off, hp = hop;
+      asm volatile("" : "+v"(ro), "+v"(hp));
+      const unsigned eL0 = (unsigned)(ro + (NARROW ? hp * (int)L.box_stride : 0)), eS0 = (unsigned)(ro + (NARROW ? hp * 2 * L.volume : 0));
+      const unsigned eK0 = C32 ? (unsigned)(ro + (NARROW ? hp * C32_COUNT * L.volume : 0)) : eL0;
+      const unsigned eX0 = A.x0.scratch ? eS0 : eL0, eXm1 = A.xm1.scratch ? eS0 : eL0, eO1 = A.out1.scratch ? eS0 : eL0, eO2 = A.out2.scratch ? eS0 : eL0;
+      const int cjS = INTERP ? A.Lc.jStride : 0, ckS = INTERP ? A.Lc.kStride : 0;
+      const int row_edge = lj * jS;                                  // the tile-edge neighbour columns: their own box, no lane shift
+      const int sb = box_of(bi_, bj_, p);
+      int po = lk * kS;                                            // plane offset inside the box, elements
+      const size_t first = (size_t)L.ghosts * (size_t)(1 + jS + kS);
+      const double *const lvl = (const double *)L.box_base[sb] + first;
+      auto vbase = [&](VecRef r, int box) -> double * { return uni_ptr(pair_vec(L, A, r, box)); };
+      const double *const s_x0n = vbase(A.x0, sb) + kS;
+      const double *const s_rhs = uni_ptr(lvl + (size_t)A.rhs_id * (size_t)L.volume);
+      const double *const s_xm1 = vbase(A.xm1, sb);
+      double *const s_o1 = vbase(A.out1, sb), *const s_o2q = vbase(A.out2, sb) - kS;
+      const double *const s_farn = farw ? vbase(A.x0, box_of(bi_, bjf, p)) + ((ljf - lj) * jS + kS) : s_x0n;
+      const CoefSeg<C32> s_dinv(L, A, sb, VECTOR_DINV, C32_DINV), s_al(L, A, sb, VECTOR_ALPHA, C32_ALPHA), s_bi(L, A, sb, VECTOR_BETA_I, C32_BETA_I);
+      const CoefSeg<C32> s_bk1(L, A, sb, VECTOR_BETA_K, C32_BETA_K, kS), s_bjn(L, A, sb, VECTOR_BETA_J, C32_BETA_J, kS), s_bjh(L, A, sb, VECTOR_BETA_J, C32_BETA_J, jS);
+      // lanes 0 / 63 across a tile edge: x0 on plane p, x1 (the pre-pass's) on plane p-1
+      const int boxL = box_of(biL, bj_, p), boxR = box_of(biR, bj_, p);
+      const double *const s_x0L = vbase(A.x0, boxL) + (liL + row_edge), *const s_x0R = vbase(A.x0, boxR) + (liR + row_edge);
+      const double *const s_o1Lq = vbase(A.out1, boxL) + (liL + row_edge - kS), *const s_o1Rq = vbase(A.out1, boxR) + (liR + row_edge - kS);
+      // INTERP: the coarse parents -- of the own row and the far row per lane (narrow boxes: the lane's own coarse box), of the edge columns wave-uniform
+      const double *c_own = nullptr, *c_far = nullptr, *c_L = nullptr, *c_R = nullptr;
+      if (INTERP) {
+        c_own = vec_origin(A.Lc, NARROW ? sb + hop : sb, A.coarse_id) + ((li >> 1) + (lj >> 1) * cjS);
+        if (farw) { const int bf = box_of(bi_, bjf, p); c_far = vec_origin(A.Lc, NARROW ? bf + hop : bf, A.coarse_id) + ((li >> 1) + (ljf >> 1) * cjS); }
+        c_L = uni_ptr(vec_origin(A.Lc, boxL, A.coarse_id) + ((liL >> 1) + (lj >> 1) * cjS));
+        c_R = uni_ptr(vec_origin(A.Lc, boxR, A.coarse_id) + ((liR >> 1) + (lj >> 1) * cjS));
+      }
+      for (; p <= last; p++, po += kS, lk++) {
+        TL_MARK();                                                 // 0: step begins
+        if (row_x1) {
+          const unsigned ek = eK0 + (unsigned)po;
+          auto load_ahead = [&]() {
+            x0p = pld_so(s_x0n, eX0 + (unsigned)po);
+            if (INTERP) { const double c = gld1(c_own + ((lk + 1) >> 1) * ckS); x0p.x = A.prescale * x0p.x + c; x0p.y = A.prescale * x0p.y + c; }
+            if (kVC) bj_n = s_bjn.pair(ek);
+            if (farw) {
+              far_n = pld_so(s_farn, eX0 + (unsigned)po);
+              if (INTERP) { const double c = gld1(c_far + ((lk + 1) >> 1) * ckS); far_n.x = A.prescale * far_n.x + c; far_n.y = A.prescale * far_n.y + c; }
+            }
+            qc.rhs = pld_so(s_rhs, eL0 + (unsigned)po);
+          };
+          if (!FORM) load_ahead();
+          if (!FORM) qc.dinv = s_dinv.pair(ek);
+          if (kHelm) qc.al = s_al.pair(ek);
+          if (kVC) {
+            qc.bi = s_bi.pair(ek);
+            qc.bir = __shfl_down(qc.bi.x, 1, 64);
+            if (lane == 63) qc.bir = s_bi.one(ek + 2u);
+            qc.bk0 = qp.bk1;
+            qc.bk1 = s_bk1.pair(ek);
+            qc.bjlo = bj_c;
+            if (bjhi_mem) qc.bjhi = s_bjh.pair(ek); else qc.bjhi = slabBJ[p & 1][w + 1][lane];
+          }
+          if (FORM) load_ahead();
+          p2 xm1 = x0c;
+          if (read_xm1) xm1 = pld_so(s_xm1, eXm1 + (unsigned)po);
+          if (FORM) qc.dinv = pair_form_dinv<V>(qc, fil, fih, fjl, fjh, -1.0, -1.0, A.a, nbh2);
+#ifdef HPGMG_EXP_TIMELINE
+          if (probe) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+          TL_MARK();                                               // 1: every load of the step has arrived
+#endif
+          // ---- x1 on plane p
+          p2 jm, jp;
+          if (jm_wall) jm = pneg(x0c); else if (jm_far) jm = far_c; else jm = slabX0[p & 1][w - 1][lane];
+          if (jp_wall) jp = pneg(x0c); else if (jp_far) jp = far_c; else jp = slabX0[p & 1][w + 1][lane];
+          double left = __shfl_up(x0c.y, 1, 64), right = __shfl_down(x0c.x, 1, 64);
+          if (lane == 0) {
+            if (left_dom) left = -x0c.x;
+            else { left = gld1(s_x0L + po); if (INTERP) left = A.prescale * left + gld1(c_L + (lk >> 1) * ckS); }
+          }
+          if (lane == 63) {
+            if (right_dom) right = -x0c.y;
+            else { right = gld1(s_x0R + po); if (INTERP) right = A.prescale * right + gld1(c_R + (lk >> 1) * ckS); }
+          }
+          x1c = pair_update<V, SM>(x0c, left, right, jm, jp, x0m, x0p, xm1, qc, A.a, A.b, A.h2inv, A.c1a, A.c2a, ((gj ^ p ^ A.sweep_a) & 1) == 0);
+        }
+#ifdef HPGMG_EXP_TIMELINE
+        if (probe) { asm volatile("" :: "v"(x1c.x)); }
+        TL_MARK();                                                 // 2: x1 formed
+#endif
+        // ---- x2 on plane q = p-1
+        if (row_out) {
+          const int q = p - 1;
+          p2 jm, jp;
+          if (x2_jm_wall) jm = pneg(x1m1); else jm = slabX1[q & 1][w - 1][lane];
+          if (x2_jp_wall) jp = pneg(x1m1); else jp = slabX1[q & 1][w + 1][lane];
+          double left = __shfl_up(x1m1.y, 1, 64), right = __shfl_down(x1m1.x, 1, 64);
+          if (lane == 0)  left  = left_dom  ? -x1m1.x : gld1(s_o1Lq + po);
+          if (lane == 63) right = right_dom ? -x1m1.y : gld1(s_o1Rq + po);
+          const p2 x2 = pair_update<V, SM>(x1m1, left, right, jm, jp, x1m2, x1c, x0m, qp, A.a, A.b, A.h2inv, A.c1b, A.c2b, ((gj ^ q ^ (A.sweep_a + 1)) & 1) == 0);
+          pst_so(s_o2q, eO2 + (unsigned)po, x2);
+        }
+        if (store_x1) pst_so(s_o1, eO1 + (unsigned)po, x1c);
+        TL_MARK();                                                 // 3: x2 formed and stored
+        if (row_x1) {
+          slabX1[p & 1][w][lane] = x1c;
+          slabX0[(p + 1) & 1][w][lane] = x0p; slabBJ[(p + 1) & 1][w][lane] = bj_n;
+        }
+        __syncthreads();
+        TL_MARK();                                                 // 4: barrier passed
+        x0m = x0c; x0c = x0p; x1m2 = x1m1; x1m1 = x1c; far_c = far_n; bj_c = bj_n; qp = qc;
+      }
+      p = last;                                                    // (the march goes on with a general step on plane last + 1)
+    }
   }
 #ifdef HPGMG_EXP_TIMELINE
   if (probe) tl[4095] = (unsigned long long)tl_n;
