@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from hpgmg_testlib import ROOT
-from test_oracle_ca_bottom import CASES, GOLD, SHAPES, call_matmul, cli_args, parse, seeded_level
+from test_oracle_ca_bottom import CASES, GOLD, SHAPE_IDS, SHAPES, call_matmul, cli_args, parse, seeded_level, shape_vectors
 import hpgmg_amd as H
 
 pytestmark = pytest.mark.gpu
@@ -38,16 +38,13 @@ def gram_on_both(hip, oracle, nb, d, g, id_A, id_B, nvec, seed):
     return out
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=[f"{s[0]}x{s[1]}g{s[2]}-{s[3]}x{s[4]}" for s in SHAPES])
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
 def test_gram_launch_equals_the_oracle_matmul(hip, oracle, shape):
-    nb, d, g, rows, cols, same = shape
-    nvec = max(rows, cols) + (0 if same else rows + 2)
-    if same:
-        id_A, id_B = list(range(rows)), list(range(cols))
-    else:
-        id_A, id_B = [nvec - 1 - m for m in range(rows)], [(3 * n + 1) % nvec for n in range(cols)]
+    nb, d, g, rows, cols, _ = shape
+    nvec, id_A, id_B = shape_vectors(shape)
     got, want = gram_on_both(hip, oracle, nb, d, g, id_A, id_B, nvec, seed=11 + d)
     assert not np.isnan(got).any() and same_bits(got, want)
+    assert len(set(want[:cols].tolist())) == len(set(id_B))        # the first row: one value per distinct vector of id_B, so a crossed slot shows
 
 
 # bottom levels of many boxes (the U-cycle ladder keeps every box: 8 per side = 512 boxes of one or two cells), CABiCGStab's 17 x 18 and CACG's 9 x 9

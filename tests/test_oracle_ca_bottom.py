@@ -13,6 +13,7 @@ import pytest
 
 from hpgmg_testlib import ROOT, Backend, build_oracle, load_golden, seeded_field
 import hpgmg_amd as H
+from pcg_lib import gram_plan, gram_restated
 
 GOLD = load_golden("ca_bottom_norms.json")
 SOLVERS = {"cabicgstab": H.BOTTOM_CABICGSTAB, "cacg": H.BOTTOM_CACG}
@@ -108,7 +109,7 @@ def seeded_level(backend, boxes_in_i, box_dim, ghosts, nvec, seed):
     return lv
 
 
-# (boxes per side, box side, ghosts, rows, cols, A == B)
+# (boxes per side, box side, ghosts, rows, cols, ids): ids True = id_A a prefix of id_B = 0 .. cols - 1, False = two scattered lists, or (id_A, id_B)
 SHAPES = [(1, 3, 1, 17, 18, True),      # CABiCGStab at s = 4 on a 3^3 bottom box: 17 x 18, mirrored
           (1, 3, 2, 9, 9, True),        # CACG at s = 4, ghosts 2 (fv4)
           (2, 2, 2, 17, 18, True),      # eight boxes of 2^3 (fv4 U-cycle bottom)
@@ -116,26 +117,49 @@ SHAPES = [(1, 3, 1, 17, 18, True),      # CABiCGStab at s = 4 on a 3^3 bottom bo
           (2, 16, 1, 17, 18, True),     # boxes of several dim x 8 x 8 tiles: dot()'s order differs here
           (1, 24, 2, 9, 9, True),
           (2, 4, 1, 7, 3, False),       # id_A != id_B, rows > cols
-          (2, 8, 1, 4, 11, False)]
+          (2, 8, 1, 4, 11, False),
+          # the edges of the launch (kernels/gram.hip; the plans of pcg_lib.gram_plan in GRAM_PLANS below)
+          (2, 4, 1, 32, 32, True),      # 528 pairs: three per lane, the third slot live in lanes 0 - 15 only
+          (1, 5, 1, 23, 23, True),      # 276 pairs: the second slot live in 20 lanes; 125 cells = one full chunk + 61
+          (1, 6, 1, 32, 32, (list(range(32)), list(range(32, 64)))),      # 64 staged vectors, the full 33 KB of LDS; 216 = 3 * 64 + 24
+          (1, 7, 2, 5, 3, ([0, 1, 0, 2, 1], [3, 0, 3])),                  # repeated ids on both sides; ghosts 2; rows > cols
+          (1, 13, 1, 20, 5, (list(range(20)), list(range(5)))),           # rows > 16 > cols; 2197 = 34 * 64 + 21; rows >= cols stay as matmul leaves them
+          (3, 5, 1, 17, 18, True)]      # the product's shape on 27 ragged boxes: a box-order sum of ragged chains
+# rows, cols, side -> (pairs, most pairs of a lane, chunks, cells of the last chunk)
+GRAM_PLANS = {(32, 32, 4): (528, 3, 1, 64), (23, 23, 5): (276, 2, 2, 61), (32, 32, 6): (528, 3, 4, 24), (5, 3, 7): (6, 1, 6, 23),
+              (20, 5, 13): (15, 1, 35, 21), (17, 18, 5): (170, 1, 2, 61)}
+SHAPE_IDS = [f"{s[0]}x{s[1]}g{s[2]}-{s[3]}x{s[4]}" for s in SHAPES]
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=[f"{s[0]}x{s[1]}g{s[2]}-{s[3]}x{s[4]}" for s in SHAPES])
+def shape_vectors(shape):
+    """(vectors of the level, id_A, id_B) of a shape; asserts its plan where GRAM_PLANS names one"""
+    nb, d, g, rows, cols, ids = shape
+    if ids is True:
+        nvec, id_A, id_B = max(rows, cols), list(range(rows)), list(range(cols))
+    elif ids is False:
+        nvec = max(rows, cols) + rows + 2
+        id_A, id_B = [nvec - 1 - m for m in range(rows)], [(3 * n + 1) % nvec for n in range(cols)]
+    else:
+        id_A, id_B = ids
+        nvec = max(id_A + id_B) + 1
+    assert (len(id_A), len(id_B)) == (rows, cols)
+    if (rows, cols, d) in GRAM_PLANS:
+        assert gram_plan(rows, cols, d) == GRAM_PLANS[rows, cols, d]
+    return nvec, id_A, id_B
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
 def test_oracle_matmul_follows_the_reference_order(shape):
-    nb, d, g, rows, cols, same = shape
+    nb, d, g, rows, cols, _ = shape
     be = Backend.oracle()
     be.configure()
-    nvec = max(rows, cols) + (0 if same else rows + 2)
+    nvec, id_A, id_B = shape_vectors(shape)
     lv = seeded_level(be, nb, d, g, nvec, seed=11 + d)
     try:
-        if same:
-            ids = list(range(cols))
-            id_A, id_B = ids[:rows], ids
-        else:
-            id_A = [nvec - 1 - m for m in range(rows)]
-            id_B = [(3 * n + 1) % nvec for n in range(cols)]
         got = call_matmul(be.lib, lv, id_A, id_B)
         want = numpy_matmul(lv, id_A, id_B)
         assert np.array_equal(got.view(np.uint64), want.view(np.uint64))
+        assert np.array_equal(got.view(np.uint64), gram_restated(lv, id_A, id_B).view(np.uint64))        # the chain as a Python loop
         if d >= 16:     # more than one tile per box: the per-tile order of dot() gives other bits, so matmul cannot be built from dot()
             dots = [be.lib.dot(lv.ptr, id_A[0], id_B[n]) for n in range(cols)]
             assert any(dots[n] != got[n] for n in range(cols))

@@ -9,7 +9,7 @@ project's margin for a change of summation order (not of Krylov space):
     contrast 100, N = 24, box 8, rtol 1e-8:     fpcg 33 (cheby) / 49 (gsrb);  mg stalls at 7.1e-3 / 1.5e-2;  pcg is at 1.8e-8 / 2.8e-4 after 100
     periodic Helmholtz a = 1.3, rtol 1e-10:     fpcg 20 at (24, 8) and 16 at (32, 16);  pcg is at 9.1e-4 / 7.4e-3 after 100
 
-hpgmg_pcg_dot2 is checked against hpgmg_pcg_dot and against a NumPy restatement of the summation order of include/hpgmg_operators.h.
+hpgmg_pcg_dot2 is checked against hpgmg_pcg_dot and against the NumPy restatement of the summation order of include/hpgmg_operators.h (tests/pcg_lib.py).
 """
 import ctypes
 
@@ -20,6 +20,7 @@ import scipy.sparse.linalg as spl
 import hpgmg_amd as H
 from hpgmg_amd.problem import Solver
 from hpgmg_testlib import Backend
+from pcg_lib import dense_boxes, header_order_dot
 from user_neumann_lib import ALL, SIDES, assemble_faces, lift_faces
 from user_pcg_lib import contrast_problem
 from user_problem_lib import assemble, random_coefficients
@@ -151,35 +152,6 @@ def test_periodic_helmholtz_pcg_fails_fpcg_converges(lib, n, box_dim):
     assert info.vcycles <= 1.25 * PERIODIC_ITERATIONS[(n, box_dim)]
 
 
-def header_order_dot(va, vb, box_dim):
-    """a . b in the order of include/hpgmg_operators.h, restated: chains over <= 16 planes per column and segment, leaves V[c + W (s + S B)], padded
-    with 0.0 to a power of two, folded with doubling strides.  Arrays are [k][j][i]; box B = bi + nb (bj + nb bk)."""
-    n = va.shape[0]
-    nb, seg = n // box_dim, H_SEGMENT
-    W = H_COLUMNS * ((box_dim * box_dim + H_COLUMNS - 1) // H_COLUMNS)
-    S = (box_dim + seg - 1) // seg
-    size = 1
-    while size < W * S * nb ** 3:
-        size *= 2
-    V = np.zeros(size)
-    q = va * vb
-    for B in range(nb ** 3):
-        i0, j0, k0 = (B % nb) * box_dim, (B // nb % nb) * box_dim, (B // (nb * nb)) * box_dim
-        box = q[k0:k0 + box_dim, j0:j0 + box_dim, i0:i0 + box_dim]
-        for s in range(S):
-            chain = np.zeros((box_dim, box_dim))
-            for k in range(s * seg, min(s * seg + seg, box_dim)):
-                chain = chain + box[k]
-            base = W * (s + S * B)
-            V[base:base + box_dim * box_dim] = chain.ravel()          # c = i + dim * j
-    while V.size > 1:
-        V = V[0::2] + V[1::2]
-    return float(V[0])
-
-
-H_SEGMENT, H_COLUMNS = 16, 256           # HPGMG_PCG_SEGMENT, HPGMG_PCG_COLUMNS of include/hpgmg_operators.h
-
-
 @pytest.mark.parametrize("n,box_dim", GRIDS)
 def test_dot2_equals_two_dots_and_the_headers_order(lib, n, box_dim):
     rng = np.random.default_rng(40 + n)
@@ -197,7 +169,8 @@ def test_dot2_equals_two_dots_and_the_headers_order(lib, n, box_dim):
         assert ab.value == one.value
         lib.hpgmg_pcg_dot(L, c_id, b_id, ctypes.byref(one))
         assert cb.value == one.value
-    assert ab.value == header_order_dot(va, vb, box_dim) and cb.value == header_order_dot(vc, vb, box_dim)
+    A, C, B = (dense_boxes(v, box_dim) for v in (va, vc, vb))
+    assert ab.value == header_order_dot(A, B, box_dim) and cb.value == header_order_dot(C, B, box_dim)
     assert ab.value != 0.0 and cb.value != 0.0 and ab.value != cb.value
     assert abs(ab.value - float((va * vb).sum())) <= 1e-12 * n ** 3
 
