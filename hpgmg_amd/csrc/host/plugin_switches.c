@@ -4,7 +4,8 @@
  * The reference fixes its variants with -D flags at compile time; the plugin's own choices -- which fused form runs, whether
  * an exchange is overlapped, which debugging path is taken -- are run-time switches instead: each has an environment variable (read once, on
  * first use), a default, and a setter in the API (include/hpgmg_fv.h: hpgmg_set_*) that the tests use.  None of them changes a result; they
- * select between bit-identical ways of computing it.  HPGMG_SWITCHES=1 prints the table (with the values in force) when the library is loaded.
+ * select between bit-identical ways of computing it.  HPGMG_SWITCHES=1 prints the table (with the values in force), and after it
+ * the kernel library's table of launch knobs (kernels/knobs.hip), when the library is loaded.
  */
 #include "plugin_internal.h"
 
@@ -63,5 +64,6 @@ void hp_switch_set(hp_switch_id id, long long value) { table[id].value = value; 
 void hpgmg_print_switches(void) {
   int q;
   for (q = 0; q < SW_COUNT; q++) fprintf(stderr, "  %-28s = %-8lld (default %lld)  %s\n", table[q].env, hp_switch((hp_switch_id)q), table[q].dflt, table[q].what);
+  hpgmg_hip_print_knobs();      /* the kernel library's own table (kernels/knobs.hip): launch shapes and kernel choices */
 }
 __attribute__((constructor)) static void switches_report(void) { const char *e = getenv("HPGMG_SWITCHES"); if (e && e[0] == '1') hpgmg_print_switches(); }

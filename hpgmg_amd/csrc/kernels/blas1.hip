@@ -9,6 +9,7 @@
 // order (misc.c:261-269).  They are only ever called on the coarsest level
 // (BiCGStab) and in untimed setup, so one lane per tile is enough.
 #include "reduce.hpp"
+#include "knobs.hpp"
 
 namespace hpgmg {
 
@@ -418,8 +419,7 @@ static int norm_copy_restrict(const hpgmg_hip_level *L, int f_id, int r_id, cons
   const int nblk = rows_grid(L->num_boxes * (L->dim / 2) * (L->dim / 2));
   double *partials = reduction_scratch(nblk);
   if (!partials) return record_error(hipErrorOutOfMemory, "norm_copy_restrict: no scratch");
-  static const bool nt_allowed = [] { const char *e = getenv("HPGMG_TUNE_COPY_NT"); return !(e && *e == '0'); }();
-  if (nt_allowed && (double)L->num_boxes * L->dim * L->dim * L->dim * sizeof(double) > 256e6)
+  if (knob(K_COPY_NT) && (double)L->num_boxes * L->dim * L->dim * L->dim * sizeof(double) > 256e6)
     hipLaunchKernelGGL(norm_copy_restrict_kernel<true>, dim3(nblk), dim3(256), 0, g_stream, *L, f_id, r_id, *Lc, rc_id, map, partials);
   else hipLaunchKernelGGL(norm_copy_restrict_kernel<false>, dim3(nblk), dim3(256), 0, g_stream, *L, f_id, r_id, *Lc, rc_id, map, partials);
   HPGMG_LAUNCH_CHECK("norm_copy_restrict");

@@ -11,6 +11,7 @@
 //   interp p0  interpolation_p0.c:6-46 interp p1   interpolation_p1.c:8-65
 // All of these are pure data movement or <= 8-term sums: HBM/L2-bound, no LDS.
 #include "common.hpp"
+#include "knobs.hpp"
 #include "block_ops.hpp"
 
 namespace hpgmg {
@@ -411,9 +412,7 @@ int hpgmg_hip_interpolate_blocks(const hpgmg_hip_level *Lf, int id_f, double pre
   else if (order == 1) hipLaunchKernelGGL((interp_blocks_kernel<1>), dim3(n, slabs), dim3(256), 0, g_stream, *Lf, id_f, prescale, *Lc, id_c, blocks);
   else if (order >= 17 && order <= 20) {      // order - 16 onto a fine vector that counts as zeroed (zero_vector + interpolation_fcycle, the fine level touched once)
     if (prescale != 0.0) return record_error(hipErrorInvalidValue, "interpolation onto a zeroed vector: prescale 0");
-    // a fine vector beyond the infinity cache (256 MB) is written past the caches: nothing of it would still be there when the next kernel reads it
-    static const bool nt_allowed = [] { const char *e = getenv("HPGMG_TUNE_INTERP_NT"); return !(e && *e == '0'); }();
-    const bool nt = nt_allowed && (double)Lf->num_boxes * Lf->dim * Lf->dim * Lf->dim * sizeof(double) > 256e6;
+    const bool nt = knob(K_INTERP_NT) && (double)Lf->num_boxes * Lf->dim * Lf->dim * Lf->dim * sizeof(double) > 256e6;
 #define INTERP_ZEROED(KERNEL, ORD) do { if (nt) hipLaunchKernelGGL((KERNEL<ORD, true, true>), dim3(n, slabs), dim3(256), 0, g_stream, *Lf, id_f, prescale, *Lc, id_c, blocks); \
                                         else hipLaunchKernelGGL((KERNEL<ORD, true, false>), dim3(n, slabs), dim3(256), 0, g_stream, *Lf, id_f, prescale, *Lc, id_c, blocks); } while (0)
     if (order == 17)      INTERP_ZEROED(interp_blocks_kernel, 1);

@@ -31,6 +31,7 @@
 // residual.c:42-48, restriction.c:54-57, interpolation_p0.c:43, interpolation_p1.c:40-70): bit-identical to the per-operator path;
 // tests/test_gpu_operators.py runs both, tools/stress_bricks.py repeats a cycle hundreds of times and compares the bytes.
 #include "common.hpp"
+#include "knobs.hpp"
 #include "stencil_math.hpp"
 #include "dense_levels.hpp"
 #include "brick_records.hpp"
@@ -384,17 +385,14 @@ int brick_records_for_launch(BrickRecords *R) {
 // Every workgroup of a brick launch waits for records of others: all of them must be RESIDENT at once.  What the device holds of a kernel = its occupancy
 // per CU (registers, LDS, waves) x the CUs of this device (a partition in CPX / DPX mode reports its own count).
 int brick_workgroups_resident(const void *kernel, int threads, size_t lds_bytes) {
-  static const int forced = [] { const char *e = getenv("HPGMG_TEST_BRICK_CAPACITY"); return (e && *e) ? atoi(e) : -1; }();
+  const int forced = (int)knob(K_TEST_BRICK_CAPACITY);
   if (forced >= 0) return forced;
   int per_cu = 0, dev = 0, cus = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds_bytes) != hipSuccess) { (void)hipGetLastError(); return 0; }
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
   return per_cu * cus;
 }
-int brick_test_absent_wg(void) {
-  static const int absent = [] { const char *e = getenv("HPGMG_TEST_BRICK_ABSENT"); return (e && *e) ? atoi(e) : -1; }();
-  return absent;
-}
+int brick_test_absent_wg(void) { return (int)knob(K_TEST_BRICK_ABSENT); }
 void brick_count_visits(int n) { g_visits += n; }
 bool brick_error_pending(void) { return g_error && *(volatile unsigned *)g_error; }
 

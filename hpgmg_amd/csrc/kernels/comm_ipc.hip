@@ -31,6 +31,7 @@
 #include <atomic>
 #include <vector>
 #include "common.hpp"
+#include "knobs.hpp"
 
 namespace hpgmg {
 constexpr int kIpcMaxRanks = 16, kIpcMaxVals = 1024;     // values per reduction: a scalar on the V-cycle path, matmul's whole Gram matrix (<= 32 x 32) for the s-step solvers
@@ -75,10 +76,9 @@ template <class F> static void spin_until(F done, const char *what) {
   }
 }
 static int ipc_hip_fail(hipError_t e, const char *where) { fprintf(stderr, "hpgmg_hip (ipc transport, rank %d): %s: %s\n", g_irank, where, hipGetErrorString(e)); return (int)e; }
-static int ipc_debug(void) { static int d = -1; if (d < 0) { const char *e = getenv("HPGMG_IPC_DEBUG"); d = (e && e[0] == '1'); } return d; }
 #define IPC_OK(call) do {                                                                                                                    \
     hipError_t e_ = (call);                                                                                                                  \
-    if (ipc_debug()) { fprintf(stderr, "[ipc %d] %s -> %s (stream %p)\n", g_irank, #call, hipGetErrorString(e_), (void *)g_stream); fflush(stderr); } \
+    if (knob(K_IPC_DEBUG)) { fprintf(stderr, "[ipc %d] %s -> %s (stream %p)\n", g_irank, #call, hipGetErrorString(e_), (void *)g_stream); fflush(stderr); } \
     if (e_ != hipSuccess) { ipc_hip_fail(e_, #call); abort(); } } while (0)
 
 // stream-ordered "set counter" / "wait for counter": host functions (they run on the runtime's callback thread, in stream order)

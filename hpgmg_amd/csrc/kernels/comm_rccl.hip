@@ -26,6 +26,7 @@
 #include <string.h>
 #include <rccl/rccl.h>
 #include "common.hpp"
+#include "knobs.hpp"
 
 namespace hpgmg {
 static ncclComm_t g_comm = nullptr;
@@ -80,8 +81,7 @@ void hpgmg_hip_rccl_prepare_subset(void *ctx, const int *ranks, int nranks) {
   S.n = nranks; S.ranks = (int *)malloc((size_t)nranks * sizeof(int)); memcpy(S.ranks, ranks, (size_t)nranks * sizeof(int)); S.comm = nullptr; S.ok = 0;
   int member = 0;
   for (int q = 0; q < nranks; q++) if (ranks[q] == g_rank) member = 1;
-  static const int off = [] { const char *e = getenv("HPGMG_RCCL_SUBCOMM"); return (e && e[0] == '0') ? 1 : 0; }();      // 0: keep the all-to-all (every rank must say the same)
-  if (!off) {
+  if (knob(K_RCCL_SUBCOMM)) {
     ncclComm_t sub = nullptr;
     const ncclResult_t r = ncclCommSplit(g_comm, member ? g_nsub : NCCL_SPLIT_NOCOLOR, g_rank, &sub, nullptr);      // key = my rank: the members keep their order
     int fine = (r == ncclSuccess && (sub != nullptr || !member)) ? 1 : 0;

@@ -4,13 +4,13 @@
 #include <stdlib.h>
 #include <vector>
 #include "common.hpp"
+#include "knobs.hpp"
 #include "fv4_tile.hpp"
 #include "fv4_rb.hpp"
 
 namespace hpgmg {
 int  profile_begin(long long cells);          // stencil.hip: hipEvent pair around a smoother launch (bench.py's roofline)
 void profile_end(int p, long long cells, bool first_part = false);
-static int env_int(const char *name, int dflt) { const char *e = getenv(name); return (e && *e) ? atoi(e) : dflt; }
 }
 using namespace hpgmg;
 
@@ -26,12 +26,11 @@ void hpgmg_hip_exp_timeline_fv4(void *buf) { g_fv4rb_timeline = (unsigned long l
 #endif
 long long hpgmg_hip_rb_fv4_launch_count(void) { return g_rb4_launches; }
 int hpgmg_hip_smooth_gsrb_fv4_rb_supported(const hpgmg_hip_level *L, int variant) {
-  static const int off = env_int("HPGMG_TUNE_FV4_NO_RB", 0);
   if (variant != HPGMG_HIP_FV4_VC_HELMHOLTZ && variant != HPGMG_HIP_FV4_VC_POISSON) return 0;
   // boxes of side 64 m; 32-wide tiles (two workgroups per CU) also take boxes of 32^3, but measured slower there than two half-sweep launches
   // of the tiled kernel (98 vs 2 x 35 us on a 128^3 level of 64 boxes: the march is too short for its prologue), so only on request
   const int need = 64;                                    // (32-wide tiles, two workgroups per CU, measured slower in two rounds: removed)
-  return !off && L->num_boxes > 0 && L->dim % need == 0 && L->box_nbr != nullptr && L->ghosts == 2;
+  return !knob(K_FV4_NO_RB) && L->num_boxes > 0 && L->dim % need == 0 && L->box_nbr != nullptr && L->ghosts == 2;
 }
 // Dispatch order of the tiles.  A tile at a domain wall in i or j forms the boundary values of the intermediate vector in every step
 // (two more barriers, a short serial stage): its workgroup takes about a quarter longer, and with 4 workgroups per CU in a launch the
@@ -40,8 +39,7 @@ int hpgmg_hip_smooth_gsrb_fv4_rb_supported(const hpgmg_hip_level *L, int variant
 struct TileOrder { const int *nbr; int num_boxes, dim, ti, kchunk, grid; int *d_order; };
 static std::vector<TileOrder> g_tile_orders;
 static const int *tile_order(const hpgmg_hip_level *L, const Fv4RbArgs &A, int TI, int grid) {
-  static const int on = env_int("HPGMG_TUNE_FV4_RB_ORDER", 1);
-  if (!on || A.total_blocks <= 256) return nullptr;                  // one round: every workgroup starts at once anyway
+  if (!knob(K_FV4_RB_ORDER) || A.total_blocks <= 256) return nullptr;                  // one round: every workgroup starts at once anyway
   for (const TileOrder &o : g_tile_orders)
     if (o.nbr == L->box_nbr && o.num_boxes == L->num_boxes && o.dim == L->dim && o.ti == TI && o.kchunk == A.kchunk && o.grid == grid) return o.d_order;
   std::vector<int> nbr(6 * (size_t)L->num_boxes), order((size_t)grid);
@@ -119,7 +117,7 @@ int hpgmg_hip_smooth_gsrb_fv4_rb(const hpgmg_hip_level *L, int variant, double *
   A.tiles_i = L->dim / TI; A.tiles_j = L->dim / fv4rb::TJ;
   int kchunk = L->dim;                                   // 256 (512) resident workgroups fill the chip; every k chunk costs four extra planes of loads and two red stages
   while (kchunk > 16 && (long long)L->num_boxes * A.tiles_i * A.tiles_j * (L->dim / kchunk) < (TI == 64 ? 256 : 512)) kchunk /= 2;
-  static const int tune_kc = env_int("HPGMG_TUNE_FV4_RB_KCHUNK", 0);
+  const int tune_kc = (int)knob(K_FV4_RB_KCHUNK);
   if (tune_kc > 0 && L->dim % tune_kc == 0) kchunk = tune_kc;
   A.kchunk = kchunk; A.chunks_k = (L->dim + kchunk - 1) / kchunk;
   A.total_blocks = L->num_boxes * A.chunks_k * A.tiles_j * A.tiles_i;
@@ -134,7 +132,7 @@ int hpgmg_hip_smooth_gsrb_fv4_rb(const hpgmg_hip_level *L, int variant, double *
     cells = cells * count / A.total_blocks;
   } else A.order = tile_order(L, A, TI, grid);
 #ifdef HPGMG_EXP_TIMELINE
-  A.timeline = g_fv4rb_timeline; A.timeline_wg = env_int("HPGMG_EXP_TIMELINE_WG", -1);
+  A.timeline = g_fv4rb_timeline; A.timeline_wg = (int)knob(K_EXP_TIMELINE_WG);
 #endif
   const int prof = profile_begin(whole_cells);               // (the caller's size threshold is on the whole launch; a part reports its share of the cells)
 #define FV4_RB_CASE(VAR, TI_) { \

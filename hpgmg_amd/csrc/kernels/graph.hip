@@ -23,6 +23,7 @@
 #include <stdlib.h>
 #include <unordered_map>
 #include "common.hpp"
+#include "knobs.hpp"
 
 namespace hpgmg {
 enum { SEG_NONE = 0, SEG_EAGER, SEG_CAPTURE, SEG_REPLAY };
@@ -83,7 +84,7 @@ int hpgmg_hip_graph_begin(long long key) {
     const hipError_t ce = hipStreamBeginCapture(g_stream, hipStreamCaptureModeThreadLocal);
     if (ce != hipSuccess) {
       static bool told = false;
-      if (!told && getenv("HPGMG_GRAPH_DEBUG")) { fprintf(stderr, "hpgmg_hip: hipStreamBeginCapture failed: %s (stream %p)\n", hipGetErrorString(ce), (void *)g_stream); told = true; }
+      if (!told && knob(K_GRAPH_DEBUG)) { fprintf(stderr, "hpgmg_hip: hipStreamBeginCapture failed: %s (stream %p)\n", hipGetErrorString(ce), (void *)g_stream); told = true; }
       (void)hipGetLastError(); g_state = SEG_EAGER;
     }
     else g_state = SEG_CAPTURE;

@@ -2,6 +2,7 @@
 // pairs of in-place GSRB half sweeps, gsrb.c:24-132), of its pre-pass, of the packed pre-pass coefficients, of the two-part launches across rank
 // boundaries, and the pack / unpack kernel of its halo messages.  A translation unit of its own (split from stencil.hip in round 4).
 #include "stencil_direct.hpp"
+#include "knobs.hpp"
 #include "cheby_pair.hpp"
 
 namespace hpgmg {
@@ -110,8 +111,7 @@ extern "C" void hpgmg_hip_pair_packed_forget(const hpgmg_hip_level *L) {
   }
 }
 static EdgePack *edge_pack_slot(const hpgmg_hip_level *L, int variant, const PairArgs &A) {
-  static const int on = env_int("HPGMG_TUNE_PAIR_PACKED", 1);
-  if (!on || A.tiles_i < 2 || variant == HPGMG_HIP_7PT_CC) return nullptr;
+  if (!knob(K_PAIR_PACKED) || A.tiles_i < 2 || variant == HPGMG_HIP_7PT_CC) return nullptr;
   for (EdgePack &e : g_edge_packs) if (e.key == (const void *)L->box_base && e.variant == variant && e.Di == A.Di && e.Dj == A.Dj && e.Dk == A.Dk) return &e;
   EdgePack e = { (const void *)L->box_base, variant, A.Di, A.Dj, A.Dk, nullptr, false };
   const size_t n = (size_t)2 * (A.tiles_i - 1) * A.Dk * A.Dj * 8;
@@ -161,8 +161,7 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
   const int Di = remote ? g_pair_brick[0] * L->dim : L->dim_i, Dj = remote ? g_pair_brick[1] * L->dim : L->dim_j, Dk = remote ? g_pair_brick[2] * L->dim : L->dim_k;
   if (!pair_supported_dims(L, variant, Di, Dj, Dk)) return record_error(hipErrorInvalidValue, "smooth_cheby_pair: level not supported");
   if (remote && c32_base) return record_error(hipErrorInvalidValue, "smooth_cheby_pair: remote faces need fp64 coefficients");
-  static const int tune_kc = env_int("HPGMG_TUNE_PAIR_KC", 0);
-  static const int tune_nw = env_int("HPGMG_TUNE_PAIR_NW", 0);
+  const int tune_kc = (int)knob(K_PAIR_KC), tune_nw = (int)knob(K_PAIR_NW);
   // Waves per workgroup (nw - 2 output rows each) and k chunk.  A workgroup occupies a CU (one fits: LDS, registers) and costs KC + 2 plane steps; a step
   // costs about in proportion to its waves (the CU's load path is what a step waits for) -- measured at 256^3, launch time over steps: 4.2 / 4.7 / 7.2 us with
   // 10 / 12 / 16 waves since the march runs in segments (4.6 / 5.1 / 7.5 before; at 512^3, every CU busy in every round, 4.8 / 5.3 / 8.3; the 16-wave kernel is

@@ -7,6 +7,7 @@
 #include <dlfcn.h>
 #include <vector>
 #include "common.hpp"
+#include "knobs.hpp"
 
 namespace hpgmg {
 hipStream_t g_stream = nullptr;
@@ -174,8 +175,7 @@ static int g_roctx_state = -1;   // -1 unknown, 0 off, 1 on
 static int roctx_ready() {
   if (g_roctx_state < 0) {
     g_roctx_state = 0;
-    const char *e = getenv("HPGMG_ROCTX");
-    if (e && e[0] == '1') {
+    if (knob(K_ROCTX)) {
       void *h = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
       if (!h) h = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
       if (h) { g_roctx_push = (roctx_push_t)dlsym(h, "roctxRangePushA"); g_roctx_pop = (roctx_pop_t)dlsym(h, "roctxRangePop"); }

@@ -3,6 +3,7 @@
 // bottom solve (solvers/bicgstab.c:14-97: bottom_bicgstab_kernel), queued BLAS-1 / operator calls ending in a scalar (small_ops_kernel) and the rest
 // of a V-cycle below a level of one box (mg.c:1145-1164: small_vtail_kernel).  A translation unit of its own (split from stencil.hip in round 4).
 #include "reduce.hpp"
+#include "knobs.hpp"
 #include "stencil_direct.hpp"
 
 namespace hpgmg {
@@ -655,8 +656,7 @@ int hpgmg_hip_small_level_op(const hpgmg_hip_level *L, int variant, int mode, in
   const int threads = cells >= 1024 ? 1024 : (cells >= 256 ? 256 : 64);
   // one box whose vectors fit the LDS: work on an image of it there
   const size_t image = (size_t)kSmallSlots * (size_t)L->volume * sizeof(double);
-  static const int no_lds = env_int("HPGMG_TUNE_SMALL_NO_LDS", 0);
-  A.lds_resident = (!no_lds && L->num_boxes == 1 && A.n_copy == 0 && image <= 150 * 1024) ? 1 : 0;
+  A.lds_resident = (!knob(K_SMALL_NO_LDS) && L->num_boxes == 1 && A.n_copy == 0 && image <= 150 * 1024) ? 1 : 0;
 #ifdef HPGMG_EXP_TIMELINE
   A.timeline = (unsigned long long *)g_exp_timeline;
 #endif
@@ -692,8 +692,7 @@ int hpgmg_hip_bottom_bicgstab(const hpgmg_hip_level *L, int variant, int x_id, i
   BottomArgs A = {};
   A.e_id = x_id; A.R_id = rhs_id; A.krylov_base = krylov_base; A.a = a; A.b = b; A.h2inv = h2inv; A.want = want;
   A.bc_list = bc_list; A.n_bc = bc_list ? n_bc : 0; A.bc_kind = A.n_bc > 0 ? bc_kind : 0; A.zero_first = zero_first; A.krylov_iterations = krylov_iterations;
-  // eight waves whatever the level: the boundary entries (26 of them) are a wave's work each
-  static const int tune_threads = env_int("HPGMG_TUNE_BOTTOM_THREADS", 512);
+  const int tune_threads = (int)knob(K_BOTTOM_THREADS);
   const int threads = (cells > 256 || tune_threads >= 512) ? 512 : (cells > 64 || tune_threads >= 256 ? 256 : 64);
   const size_t lds = ((size_t)5 * L->volume + 1100) * sizeof(double);
   if (lds > 150 * 1024) return record_error(hipErrorInvalidValue, "bottom_bicgstab: box too large for the LDS image");

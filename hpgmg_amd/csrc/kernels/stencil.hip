@@ -23,6 +23,7 @@
 //   * logical tiles are ordered box, k, j, i and dealt to XCDs in contiguous ranges (common.hpp) so halo
 //     planes shared by adjacent tiles hit the same L2.
 #include "reduce.hpp"
+#include "knobs.hpp"
 #include "stencil_direct.hpp"
 #include "stencil27_rb.hpp"
 #include "stencil27_rb_box.hpp"
@@ -607,7 +608,7 @@ static int refuse_unfused(const char *kernel) {
 }
 
 static void plan(const hpgmg_hip_level *L, StencilArgs &P, dim3 &block, int &grid) {
-  static const int tune_ty = env_int("HPGMG_TUNE_TY", 0), tune_kchunk = env_int("HPGMG_TUNE_KCHUNK", 0);   // experiments only
+  const int tune_ty = (int)knob(K_TY), tune_kchunk = (int)knob(K_KCHUNK);
   P.ghost_free = (g_ghost_free && L->box_nbr) ? 1 : 0;
   int tx = 64;
   while (tx > 1 && tx / 2 >= L->dim) tx /= 2;           // smallest power of two >= dim, capped at one wave
@@ -621,7 +622,7 @@ static void plan(const hpgmg_hip_level *L, StencilArgs &P, dim3 &block, int &gri
   // mid-size levels (<= 128^3) parallelism wins over reuse -- their planes are L2 resident anyway (measured:
   // 7.07 -> 5.70 ms per 256^3 F-cycle going from a 16-plane minimum to this rule)
   int kchunk = L->dim;
-  static const int min_kchunk = env_int("HPGMG_TUNE_MIN_KCHUNK", 1), want_blocks = env_int("HPGMG_TUNE_WANT_BLOCKS", 4096);
+  const int min_kchunk = (int)knob(K_MIN_KCHUNK), want_blocks = (int)knob(K_WANT_BLOCKS);
   while (kchunk > min_kchunk && (long long)L->num_boxes * P.tiles_i * P.tiles_j * ((L->dim + kchunk - 1) / kchunk) < want_blocks) kchunk /= 2;
   if (tune_kchunk > 0 && L->dim >= tune_kchunk) kchunk = tune_kchunk;
   P.kchunk = kchunk;
@@ -630,16 +631,12 @@ static void plan(const hpgmg_hip_level *L, StencilArgs &P, dim3 &block, int &gri
   grid = grid_for(P.total_blocks, &P.per_xcd);
 }
 
-// smallest box side the tiled 27-point kernel takes: 64.  The 32 x 16 tiles for boxes of 32^3 work (HPGMG_TUNE_27PT_TILE32=1, covered by the
-// tests) but measured 0.35 ms per `7 64` F-cycle SLOWER than the register kernel on that level (the 128^3 level is cache resident)
-static int g_s27_tile32 = -1;
-static int s27_tile_granule() { if (g_s27_tile32 < 0) g_s27_tile32 = env_int("HPGMG_TUNE_27PT_TILE32", 0) ? 1 : 0; return g_s27_tile32 ? 32 : 64; }
+static int s27_tile_granule() { return knob(K_27PT_TILE32) ? 32 : 64; }      // smallest box side the tiled 27-point kernel takes
 template <int MODE>
 static int launch27(const hpgmg_hip_level *L, StencilArgs P, bool is_smoother) {
   HPGMG_SKIP_IF_REPLAY();
   if (L->num_boxes <= 0) return 0;
-  static const int no_tile27 = env_int("HPGMG_TUNE_27PT_DIRECT", 0);
-  if (MODE != MODE_BLACKBOX && !no_tile27 && L->dim % s27_tile_granule() == 0 && P.xn_id != P.xout_id) {       // LDS-staged kernel (stencil27_tile.hpp)
+  if (MODE != MODE_BLACKBOX && !knob(K_27PT_DIRECT) && L->dim % s27_tile_granule() == 0 && P.xn_id != P.xout_id) {       // LDS-staged kernel (stencil27_tile.hpp)
     constexpr int TM = (MODE == MODE_BLACKBOX) ? MODE_APPLY : MODE;
     const bool narrow = (L->dim % 64 != 0);               // boxes of 32^3: 32 x 16 tiles
     const int TI = narrow ? 32 : 64, TJ = narrow ? 16 : 8;
@@ -650,7 +647,7 @@ static int launch27(const hpgmg_hip_level *L, StencilArgs P, bool is_smoother) {
     A.tiles_i = L->dim / TI; A.tiles_j = L->dim / TJ;
     int kchunk = L->dim;
     while (kchunk > 32 && (long long)L->num_boxes * A.tiles_i * A.tiles_j * (L->dim / kchunk) < 8192) kchunk /= 2;   // measured at 512^3: 32-plane chunks 929 us, whole boxes 952
-    static const int tune_kc = env_int("HPGMG_TUNE_27PT_KCHUNK", 0);
+    const int tune_kc = (int)knob(K_27PT_KCHUNK);
     if (tune_kc > 0 && L->dim % tune_kc == 0) kchunk = tune_kc;
     A.kchunk = kchunk; A.chunks_k = (L->dim + kchunk - 1) / kchunk;
     A.total_blocks = L->num_boxes * A.chunks_k * A.tiles_j * A.tiles_i;
@@ -684,7 +681,7 @@ static int launch27(const hpgmg_hip_level *L, StencilArgs P, bool is_smoother) {
   return 0;
 }
 
-static int fv4_tile_granule() { static const int g = env_int("HPGMG_TUNE_FV4_TILE32", 1) ? 32 : 64; return g; }   // smallest box side the tiled fv4 kernel takes
+static int fv4_tile_granule() { return knob(K_FV4_TILE32) ? 32 : 64; }   // smallest box side the tiled fv4 kernel takes
 // the LDS-tiled 4th-order kernel (fv4_tile.hpp): boxes whose side is a multiple of 32, out of place
 template <int MODE, int TJ, int TI>
 static int launch_fv4_tile_tj(const hpgmg_hip_level *L, int variant, const StencilArgs &S, bool is_smoother) {
@@ -695,9 +692,9 @@ static int launch_fv4_tile_tj(const hpgmg_hip_level *L, int variant, const Stenc
   P.tiles_i = L->dim / TI; P.tiles_j = L->dim / TJ;
   int kchunk = L->dim;                                   // enough workgroups to fill the chip, as few chunk prologues as possible
   const int want = (TJ * TI >= 1024) ? 512 : 1024;
-  static const int kc_min = env_int("HPGMG_TUNE_FV4_KCHUNK_MIN", 8);      // (a chunk costs four extra planes of loads: chunks of 4 planes -- what filling 1024 slots asked for on the 128^3 level of 7 64 -- fetch every plane twice; 8: 29 vs 34 us per half sweep there, tools/ab_fv4_kcmin.sh)
+  const int kc_min = (int)knob(K_FV4_KCHUNK_MIN);
   while (kchunk > kc_min && (long long)L->num_boxes * P.tiles_i * P.tiles_j * (L->dim / kchunk) < want) kchunk /= 2;
-  static const int tune_kc = env_int("HPGMG_TUNE_FV4_KCHUNK", 0);
+  const int tune_kc = (int)knob(K_FV4_KCHUNK);
   if (tune_kc > 0 && L->dim % tune_kc == 0) kchunk = tune_kc;
   P.kchunk = kchunk; P.chunks_k = (L->dim + kchunk - 1) / kchunk;
   P.total_blocks = L->num_boxes * P.chunks_k * P.tiles_j * P.tiles_i;
@@ -730,9 +727,8 @@ static int launch_fv4_tile_tj(const hpgmg_hip_level *L, int variant, const Stenc
 // halo saves.  Boxes of 32^3 (the 128^3 level of `7 64`): 32 x 16 tiles (a wave = two rows of 32 cells, still conflict free in LDS).
 template <int MODE>
 static int launch_fv4_tile(const hpgmg_hip_level *L, int variant, const StencilArgs &S, bool is_smoother) {
-  static const int tj = env_int("HPGMG_TUNE_FV4_TJ", 8);
   if (L->dim % 64 != 0) return launch_fv4_tile_tj<MODE, 16, 32>(L, variant, S, is_smoother);
-  if (tj == 8) return launch_fv4_tile_tj<MODE, 8, 64>(L, variant, S, is_smoother);
+  if (knob(K_FV4_TJ) == 8) return launch_fv4_tile_tj<MODE, 8, 64>(L, variant, S, is_smoother);
   return launch_fv4_tile_tj<MODE, 16, 64>(L, variant, S, is_smoother);
 }
 
@@ -741,8 +737,7 @@ static int launch_direct(const hpgmg_hip_level *L, int variant, StencilArgs P, b
   HPGMG_SKIP_IF_REPLAY();
   if (L->num_boxes <= 0) return 0;
   if (MODE != MODE_BLACKBOX && (variant == HPGMG_HIP_FV4_VC_HELMHOLTZ || variant == HPGMG_HIP_FV4_VC_POISSON)) {
-    static const int no_tile = env_int("HPGMG_TUNE_FV4_DIRECT", 0);
-    if (!no_tile && L->dim % fv4_tile_granule() == 0 && L->ghosts >= 2 && P.xn_id != P.xout_id) return launch_fv4_tile<(MODE == MODE_BLACKBOX) ? MODE_APPLY : MODE>(L, variant, P, is_smoother);
+    if (!knob(K_FV4_DIRECT) && L->dim % fv4_tile_granule() == 0 && L->ghosts >= 2 && P.xn_id != P.xout_id) return launch_fv4_tile<(MODE == MODE_BLACKBOX) ? MODE_APPLY : MODE>(L, variant, P, is_smoother);
   }
   if (int e = refuse_unfused("fused residual form requested, but this level runs stencil_direct_kernel")) return e;
   dim3 block; int grid;
@@ -795,11 +790,10 @@ static int launch(const hpgmg_hip_level *L, int variant, StencilArgs P, bool is_
   }
   const long long cells = (long long)L->num_boxes * L->dim * L->dim * L->dim;
   int prof = is_smoother ? profile_begin(cells) : -1;
-  static const int no_wide = env_int("HPGMG_TUNE_NO_WIDE", 0);
   // wide kernel: side a multiple of 128, 16-byte aligned interior rows (even strides; the box bases are checked by the host)
   if (g_fold_now.which && L->dim % 128 == 0) { return record_error(hipErrorInvalidValue, "folded interpolation: not in the wide kernel (hpgmg_hip_smooth_cheby_fold_supported)"); }
-  if (!no_wide && L->dim % 128 == 0 && L->jStride % 2 == 0 && L->kStride % 2 == 0 && L->volume % 2 == 0 && (L->flags & 1)) {
-    static const int wj = env_int("HPGMG_TUNE_WIDE_WJ", 8), tune_kc = env_int("HPGMG_TUNE_KCHUNK", 0);
+  if (!knob(K_NO_WIDE) && L->dim % 128 == 0 && L->jStride % 2 == 0 && L->kStride % 2 == 0 && L->volume % 2 == 0 && (L->flags & 1)) {
+    const int wj = (int)knob(K_WIDE_WJ), tune_kc = (int)knob(K_KCHUNK);
     block = dim3(64, wj, 1);
     P.tiles_i = L->dim / 128; P.tiles_j = L->dim / (2 * wj);
     const int kchunk = tune_kc > 0 ? tune_kc : 16;
@@ -822,8 +816,8 @@ static int launch(const hpgmg_hip_level *L, int variant, StencilArgs P, bool is_
     return 0;
   }
   // boxes of side 64 m (the 128^3 level of config 2): LDS-staged tile kernel (stencil7_tile.hpp)
-  static const int no_tile7 = env_int("HPGMG_TUNE_7PT_NO_TILE", 0), tile7_kc = env_int("HPGMG_TUNE_7PT_TILE_KCHUNK", 8);
-  if (!no_tile7 && !g_defer_mode && MODE != MODE_BLACKBOX && L->dim % 64 == 0) {
+  const int tile7_kc = (int)knob(K_7PT_TILE_KCHUNK);
+  if (!knob(K_7PT_NO_TILE) && !g_defer_mode && MODE != MODE_BLACKBOX && L->dim % 64 == 0) {
     constexpr int TJ = 8, TM = (MODE == MODE_BLACKBOX) ? MODE_APPLY : MODE;
     S7TileArgs A = {};
     A.xn_id = P.xn_id; A.xout_id = P.xout_id; A.rhs_id = P.rhs_id; A.a = P.a; A.b = P.b; A.h2inv = P.h2inv; A.c1 = P.c1; A.c2 = P.c2; A.sweep = P.sweep;
@@ -883,8 +877,7 @@ static int launch(const hpgmg_hip_level *L, int variant, StencilArgs P, bool is_
 // residual + restriction + zero_vector on the launch-bound levels (boxes of an even side <= 32, every box local): stencil7_kernel<.., RR>
 static int small_fused_ok(const hpgmg_hip_level *L, int variant) {
   if (variant != HPGMG_HIP_7PT_VC_HELMHOLTZ && variant != HPGMG_HIP_7PT_VC_POISSON && variant != HPGMG_HIP_7PT_CC) return 0;
-  static const int on = env_int("HPGMG_TUNE_SMALL_RR", 1);      // 0: the two launches (experiments)
-  return on && L->num_boxes > 0 && g_ghost_free && L->box_nbr && !g_defer_mode && !g_tile_part && L->dim % 2 == 0 && (L->dim <= 32 || (L->dim % 64 == 0 && L->dim % 128 != 0));
+  return knob(K_SMALL_RR) && L->num_boxes > 0 && g_ghost_free && L->box_nbr && !g_defer_mode && !g_tile_part && L->dim % 2 == 0 && (L->dim <= 32 || (L->dim % 64 == 0 && L->dim % 128 != 0));
 }
 static int launch_small_fused(const hpgmg_hip_level *L, int variant, StencilArgs P, FusedArgs FA, int extra_blocks) {
   dim3 block; int grid;
@@ -956,13 +949,12 @@ extern "C" {
 void hpgmg_hip_set_ghost_free(int on) { g_ghost_free = on; }
 void hpgmg_hip_set_defer_mode(int mode) { g_defer_mode = mode; }
 void hpgmg_hip_set_tile_ghost_free(int on) { g_tile_ghost_free = on; }
-void hpgmg_hip_set_27pt_tile32(int on) { g_s27_tile32 = on ? 1 : 0; }
+void hpgmg_hip_set_27pt_tile32(int on) { knob_set(K_27PT_TILE32, on ? 1 : 0); }
 // would smooth / residual / apply_op of this variant run the LDS-tiled kernel on this level (out of place)?
 int hpgmg_hip_tile_kernel_applies(const hpgmg_hip_level *L, int variant, int out_of_place) {
-  static const int no_fv4 = env_int("HPGMG_TUNE_FV4_DIRECT", 0), no_27 = env_int("HPGMG_TUNE_27PT_DIRECT", 0);
   if (L->num_boxes <= 0 || !out_of_place) return 0;
-  if (variant == HPGMG_HIP_27PT_CC) return !no_27 && L->dim % s27_tile_granule() == 0;
-  if (variant == HPGMG_HIP_FV4_VC_HELMHOLTZ || variant == HPGMG_HIP_FV4_VC_POISSON) return !no_fv4 && L->ghosts >= 2 && L->dim % fv4_tile_granule() == 0;
+  if (variant == HPGMG_HIP_27PT_CC) return !knob(K_27PT_DIRECT) && L->dim % s27_tile_granule() == 0;
+  if (variant == HPGMG_HIP_FV4_VC_HELMHOLTZ || variant == HPGMG_HIP_FV4_VC_POISSON) return !knob(K_FV4_DIRECT) && L->ghosts >= 2 && L->dim % fv4_tile_granule() == 0;
   return 0;
 }
 int hpgmg_hip_get_ghost_free(void) { return g_ghost_free; }
@@ -1011,8 +1003,7 @@ int hpgmg_hip_smooth_gsrb(const hpgmg_hip_level *L, int variant, int xn_id, int 
 static long long g_rb27_launches = 0;
 long long hpgmg_hip_rb27_launch_count(void) { return g_rb27_launches; }   // launches of the one-pass red + black kernel so far (tests)
 int hpgmg_hip_smooth_gsrb27_rb_supported(const hpgmg_hip_level *L) {
-  static const int off = env_int("HPGMG_TUNE_27PT_NO_RB", 0);
-  return !off && L->num_boxes > 0 && L->dim % 64 == 0 && L->box_nbr != nullptr && L->ghosts >= 1;
+  return !knob(K_27PT_NO_RB) && L->num_boxes > 0 && L->dim % 64 == 0 && L->box_nbr != nullptr && L->ghosts >= 1;
 }
 int hpgmg_hip_smooth_gsrb27_rb(const hpgmg_hip_level *L, int x_id, int out_id, int rhs_id, double a, double b, double h2inv, int sweep) {
   HPGMG_SKIP_IF_REPLAY();
@@ -1025,7 +1016,7 @@ int hpgmg_hip_smooth_gsrb27_rb(const hpgmg_hip_level *L, int x_id, int out_id, i
   // two workgroups fit a CU: 512 workgroups fill the chip, and every k chunk costs three extra planes of loads and a red stage more
   // (measured at 512^3: whole boxes 1.09 ms, chunks of 64 planes 1.19, of 32 planes 1.27)
   while (kchunk > 16 && (long long)L->num_boxes * A.tiles_i * A.tiles_j * (L->dim / kchunk) < 512) kchunk /= 2;
-  static const int tune_kc = env_int("HPGMG_TUNE_27PT_RB_KCHUNK", 0);
+  const int tune_kc = (int)knob(K_27PT_RB_KCHUNK);
   if (tune_kc > 0 && L->dim % tune_kc == 0) kchunk = tune_kc;
   A.kchunk = kchunk; A.chunks_k = (L->dim + kchunk - 1) / kchunk;
   A.total_blocks = L->num_boxes * A.chunks_k * A.tiles_j * A.tiles_i;
@@ -1048,15 +1039,10 @@ int hpgmg_hip_smooth_gsrb27_rb(const hpgmg_hip_level *L, int x_id, int out_id, i
 }
 // The same on small levels: one workgroup per box of 2^3 ... 16^3 cells (stencil27_rb_box.hpp); forms the boundary ghost cells of x_id itself,
 // so the caller runs neither exchange_boundary nor apply_BCs_p2.  Every box local.
-// Largest box side it takes.  Boxes of 16^3 and 32^3 are handled as cubes of 8^3 (bit-identical, tested) but measure no faster (16^3) or
-// slower (32^3: 14.3 vs 14.2 ms per `7 64` F-cycle) than the launches they replace -- every cube re-reads a two-cell rim, 3.4 values per cell.
-static int g_rb_box_maxdim = -1;
-void hpgmg_hip_set_27pt_rb_box_maxdim(int dim) { g_rb_box_maxdim = dim; }
+// The largest box side it takes is a knob (K_27PT_RB_BOX_MAXDIM).
+void hpgmg_hip_set_27pt_rb_box_maxdim(int dim) { knob_set(K_27PT_RB_BOX_MAXDIM, dim); }
 int hpgmg_hip_smooth_gsrb27_rb_box_supported(const hpgmg_hip_level *L) {
-  static const int off = env_int("HPGMG_TUNE_27PT_NO_RB_BOX", 0);
-  if (g_rb_box_maxdim < 0) g_rb_box_maxdim = env_int("HPGMG_TUNE_27PT_RB_BOX_MAXDIM", 8);
-  const int maxdim = g_rb_box_maxdim;
-  return !off && L->num_boxes > 0 && L->box_nbr != nullptr && L->ghosts >= 1 && L->dim <= maxdim && (L->dim == 2 || L->dim == 4 || L->dim == 8 || L->dim == 16 || L->dim == 32);
+  return !knob(K_27PT_NO_RB_BOX) && L->num_boxes > 0 && L->box_nbr != nullptr && L->ghosts >= 1 && L->dim <= knob(K_27PT_RB_BOX_MAXDIM) && (L->dim == 2 || L->dim == 4 || L->dim == 8 || L->dim == 16 || L->dim == 32);
 }
 int hpgmg_hip_smooth_gsrb27_rb_box(const hpgmg_hip_level *L, int x_id, int out_id, int rhs_id, double a, double b, double h2inv, int sweep) {
   HPGMG_SKIP_IF_REPLAY();

@@ -76,6 +76,14 @@ void   hpgmg_hip_timer_forget(const void *lo, const void *hi);
 int    hpgmg_hip_range_enabled(void);
 void   hpgmg_hip_range_push(const char *name);
 void   hpgmg_hip_range_pop(void);
+/* The library's environment knobs (kernels/knobs.hpp: one table of name, default, accepted values, description).  A variable is read
+ * on the first use of its knob, never at load time; a value outside the accepted set costs one line on stderr and gives the default.
+ * Rows 0 .. count - 1; name() is NULL outside them.  print_knobs(): the table on stderr, as HPGMG_SWITCHES=1 prints the plugin's. */
+int    hpgmg_hip_knob_count(void);
+const char *hpgmg_hip_knob_name(int k);
+long long hpgmg_hip_knob_value(int k);
+long long hpgmg_hip_knob_default(int k);
+void   hpgmg_hip_print_knobs(void);
 /* accumulate the GPU time of every smoother-kernel launch between begin/end (hipEvents around each launch) */
 void   hpgmg_hip_profile_smoother(int enable);
 void   hpgmg_hip_profile_smoother_min_cells(long long min_cells); /* time only launches over >= this many cells */

@@ -76,7 +76,7 @@ def worker():
         print("CASE " + json.dumps(dict(smooth_case(hip, oracle, variant, geom), case=name)), flush=True)
 
 
-_RUNS = {}
+_RUNS, _STDERR = {}, {}
 
 
 def run_with(nw, kc, names):
@@ -91,6 +91,7 @@ def run_with(nw, kc, names):
         assert out.returncode == 0, (out.stdout[-800:], out.stderr[-800:])
         rows = [json.loads(l[5:]) for l in out.stdout.splitlines() if l.startswith("CASE ")]
         _RUNS[(nw, kc)] = {r["case"]: r for r in rows}
+        _STDERR[(nw, kc)] = out.stderr
         assert sorted(_RUNS[(nw, kc)]) == sorted(names)
     return _RUNS[(nw, kc)]
 
@@ -109,6 +110,19 @@ def test_every_chunk_length_gives_the_oracles_bits(case, nw, kc):
     check(case, nw, kc, list(SMALL), SHAPES_SMALL[0])
     # the pair kernel ran (two launches per smooth(), more as the worker goes through its cases): a level it refused would be smoothed by the single-sweep kernels
     assert run_with(nw, kc, list(SMALL))[case]["pair_launches"] >= 2
+
+
+def test_a_refused_wave_count_is_the_launchers_choice():
+    """HPGMG_TUNE_PAIR_NW=11 names no instance of the kernel.  The launcher reads the knob table (kernels/knobs.hip), not the variable: the table refuses 11 with one line
+    on stderr and gives 0, the cost model's choice -- the oracle's bits, the digest of every other shape, and the pair kernel ran."""
+    case = list(SMALL)[0]
+    r = run_with(11, 0, [case])[case]
+    print(case, 11, 0, r)
+    assert r["is_oracle"]
+    assert r["sha"] == run_with(*SHAPES_SMALL[0], list(SMALL))[case]["sha"]
+    assert r["pair_launches"] >= 2
+    refusals = [l for l in _STDERR[(11, 0)].splitlines() if l.startswith("hpgmg_hip: HPGMG_TUNE_PAIR_NW=11 is not accepted")]
+    assert len(refusals) == 1 and refusals[0].endswith("using 0"), _STDERR[(11, 0)][-800:]
 
 
 @pytest.mark.parametrize("nw,kc", SHAPES_EDGE)
