@@ -16,7 +16,9 @@
  *   operators_hip.c     (this file) restriction, interpolation, the fused residual passes, BLAS-1 and reductions
  *   plugin_runtime.c    timers, storage hooks, transports, the per-level device record
  *   plugin_ghosts.c     exchange_boundary, apply_BCs_*, the overlapped exchange, black-box rebuild
- *   plugin_smooth.c     smooth(), residual(), apply_op() in all their forms
+ *   plugin_smooth.c     smooth(), residual(), apply_op(): which form each takes; single sweeps, red + black passes, one small level as one launch
+ *   plugin_pairs.c      smooth() as sweep pairs, the interpolation folded into them, the fp32 coefficient copies
+ *   plugin_legs.c       the fused legs of a cycle: brick visits, the single-launch tails, the device bottom solve
  *   plugin_pair_halo.c  the two-deep halo of the sweep pairs across ranks
  *   halo_images.c       images of the neighbouring ranks' boxes (27-point / fv4 across ranks)
  *   plugin_problem.c    initialize_problem, rebuild_operator

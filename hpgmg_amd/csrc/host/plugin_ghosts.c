@@ -45,7 +45,7 @@ int hp_exchange_and_bcs_one_launch(level_type *L, int id, int shape, int order, 
   if (order == 2 && !(L->box_dim >= 2)) return 0;
   if (order == 4 && !(L->box_dim >= 4)) return 0;
   communicator_type *C = &L->exchange_ghosts[shape];
-  if (C->num_sends + C->num_recvs > 0 || C->num_blocks[0] || C->num_blocks[2]) return 0;
+  if (!hp_comm_no_messages(C)) return 0;
   backend_t *B = hp_backend_of(L);
   int n = 0;
   const hpgmg_hip_bc_entry *e = hp_bc_entries(L, shape, &n);

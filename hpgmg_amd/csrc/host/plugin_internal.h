@@ -137,6 +137,19 @@ HP_INTERNAL void hp_switch_set(hp_switch_id id, long long value);
 HP_INTERNAL backend_t *hp_backend_of(level_type *L);
 HP_INTERNAL const blockCopy_type *hp_mirror(level_type *owner, const blockCopy_type *host, int n);
 HP_INTERNAL int  hp_variant(void);
+/* ---- level predicates: one copy each, whoever selects a launch form asks these (plugin_runtime.c) ---- */
+/* Which apply_BCs form a small level gets inside a single-workgroup kernel: kind 1 apply_BCs_p1 (the 7-point operator; every operator on a box of one cell),
+ * 2 apply_BCs_p2 (27-point; boundary_fd.c:93-205), 3 apply_BCs_v2 (fv2, and fv4 below 4^3), 4 apply_BCs_v4; zero_first: the ghost zone is deeper than the
+ * form fills.  The conditions interpolation_vcycle applies are the same rule asked with HPGMG_OP_FV2 for fv4. */
+typedef struct { int kind, zero_first; } hp_small_bc;
+HP_INTERNAL hp_small_bc hp_small_bc_rule(int op, const level_type *L);
+/* every box of the level is local and local box b sits at lexicographic position b (what the kernels that address cells by global coordinate assume); cached in backend_t.lexicographic */
+HP_INTERNAL int  hp_boxes_lexicographic(level_type *L);
+/* no message in or out, nothing to pack or unpack.  Copies between LOCAL boxes (num_blocks[1]) may remain: the caller's kernel is handed that list or reads
+ * neighbouring boxes where they live.  hp_comm_nothing_to_exchange asks for none of those either: a level of one box. */
+static inline int hp_comm_no_messages(const communicator_type *C) { return C->num_sends + C->num_recvs == 0 && !C->num_blocks[0] && !C->num_blocks[2]; }
+static inline int hp_comm_nothing_to_exchange(const communicator_type *C) { return hp_comm_no_messages(C) && !C->num_blocks[1]; }
+HP_INTERNAL int *hp_krylov_pinned(backend_t *B);      /* backend_t.krylov_pinned, allocated (zero) on first use; NULL: no pinned memory */
 HP_INTERNAL int  hp_ghost_free_mode(void);
 HP_INTERNAL int  hp_box_rank_at(const level_type *L, int bi, int bj, int bk);
 HP_INTERNAL void hp_ensure_pair_scratch(level_type *L, backend_t *B);
@@ -179,6 +192,10 @@ HP_INTERNAL void hp_dinv_record_forget(level_type *L);                          
 HP_INTERNAL void hp_dinv_record_written(const double *dst, size_t n);                      /* a raw copy into device storage: clears the record of the level whose coefficient vectors it touches */
 /* an operator is about to write vector `id` of the level (ghost zones count: the kernels read the betas' high faces there) */
 static inline void hp_coef_written(level_type *L, int id) { if (id >= VECTOR_DINV && id <= VECTOR_ALPHA) hp_dinv_record_clear(L); }
+HP_INTERNAL void hp_cheby_coefficients(const level_type *L, int degree, double *c1, double *c2);
+/* smooth() as sweep pairs (plugin_pairs.c); 0: the level does not qualify */
+HP_INTERNAL int hp_smooth_cheby_pairs(level_type *L, int x_id, int rhs_id, double a, double b, const double *c1, const double *c2, int sweeps, int temp_dead, const hpgmg_hip_level *fold_Lc);
+HP_INTERNAL int hp_smooth_gsrb_pairs(level_type *L, int x_id, int rhs_id, double a, double b, int sweeps);
 HP_INTERNAL int hp_interp_smooth_fused(level_type *Lf, int e_id, int R_id, level_type *Lc, double a, double b, int exact_state);
 HP_INTERNAL void hp_do_smooth(level_type *L, int x_id, int rhs_id, double a, double b, int temp_dead);
 HP_INTERNAL void hp_do_residual(level_type *L, int res_id, int x_id, int rhs_id, double a, double b);
@@ -201,6 +218,13 @@ HP_INTERNAL void hp_small_ops_forget(void);
 HP_INTERNAL const int *hp_restrict_map_of(level_type *Lf, backend_t *Bf);      /* device table: per fine box the coarse box and the coarse cell under its first cell; NULL when a parent is not local */
 
 #define BLAS1(call) do { TICK(L, blas1, "BLAS1"); HIP_OK(call); TOCK(); } while (0)
+/* A stencil launch, whole or (TWO_PARTS: hp_ghosts_for_stencil / hp_images_refresh_begin returned 1) in two parts around an image refresh that runs on
+ * the exchange stream: the tiles that read no image, the wait for the images, then BEFORE_REST (what only the rest needs) and the other tiles. */
+#define LAUNCH_IN_PARTS(TWO_PARTS, BEFORE_REST, CALL) do {                                               \
+    if (TWO_PARTS) { hpgmg_hip_set_tile_part(1); HIP_OK(CALL); hp_images_refresh_end(); hpgmg_hip_set_tile_part(2); } \
+    BEFORE_REST; HIP_OK(CALL);                                                                           \
+    if (TWO_PARTS) hpgmg_hip_set_tile_part(0);                                                           \
+  } while (0)
 #define STENCIL_WITH_GHOSTS(L, id, out_id, TIMER, CALL) do {                                                     \
     hp_backend_of(L)->img_active = 0;                                                                    \
     if (hp_overlap_begin(L, id)) {                                                                          \
@@ -212,28 +236,8 @@ HP_INTERNAL const int *hp_restrict_map_of(level_type *Lf, backend_t *Bf);      /
     } else {                                                                                             \
       const int two_parts_ = hp_ghosts_for_stencil(L, id, out_id);   /* 1: the images' refresh runs on the exchange stream */ \
       TICK(L, TIMER, #TIMER);                                                                            \
-      if (two_parts_) {                                                                                  \
-        hpgmg_hip_set_tile_part(1); HIP_OK(CALL);                                                        \
-        hp_images_refresh_end();                                                                         \
-        hpgmg_hip_set_tile_part(2); HIP_OK(CALL); hpgmg_hip_set_tile_part(0);                            \
-      } else HIP_OK(CALL);                                                                               \
+      LAUNCH_IN_PARTS(two_parts_, (void)0, CALL);                                                        \
       TOCK();                                                                                            \
-    } } while (0)
-#define PAIR_REMOTE_LAUNCH(OVERLAPPED, DISCARD_X1, CALL) do {                                                   \
-    pair_halo *H_ = B->halo;                                                                                   \
-    if (OVERLAPPED) {                                                                                          \
-      hpgmg_hip_pair_set_halo(H_->brick, H_->rem, H_->deep, H_->deep_beta); hpgmg_hip_set_tile_part(1);        \
-      if (DISCARD_X1) hpgmg_hip_pair_discard_x1();                                                             \
-      HIP_OK(CALL);                                                                                            \
-      hp_overlap_end();                                                                                           \
-      hpgmg_hip_pair_set_halo(H_->brick, H_->rem, H_->deep, H_->deep_beta); hpgmg_hip_set_tile_part(2);        \
-      if (DISCARD_X1) hpgmg_hip_pair_discard_x1();                                                             \
-      HIP_OK(CALL);                                                                                            \
-      hpgmg_hip_set_tile_part(0);                                                                              \
-    } else {                                                                                                   \
-      hpgmg_hip_pair_set_halo(H_->brick, H_->rem, H_->deep, H_->deep_beta);                                    \
-      if (DISCARD_X1) hpgmg_hip_pair_discard_x1();                                                             \
-      HIP_OK(CALL);                                                                                            \
     } } while (0)
 
 #endif

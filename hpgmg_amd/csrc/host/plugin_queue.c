@@ -47,8 +47,7 @@ static int small_ops_kind(int op) { return op == LZ_ADD ? 1 : op == LZ_MUL ? 2 :
 static int small_ops_level_ok(level_type *L) {
   if (!hp_switch(SW_SMALL_OPS) || !L->active || L->num_my_boxes != 1 || L->boxes_in.i * L->boxes_in.j * L->boxes_in.k != 1 || L->box_dim > 8) return 0;
   if (L->boundary_condition.type != BC_DIRICHLET) return 0;
-  communicator_type *C = &L->exchange_ghosts[stencil_get_shape()];
-  if (C->num_sends + C->num_recvs > 0 || C->num_blocks[0] || C->num_blocks[1] || C->num_blocks[2]) return 0;      /* one box: nothing to exchange */
+  if (!hp_comm_nothing_to_exchange(&L->exchange_ghosts[stencil_get_shape()])) return 0;
   { const hpgmg_transport *T = hpgmg_get_transport(); if (T && T->size > 1) { hpgmg_level_ext *X = hpgmg_level_ext_get(L); if (X->num_active_ranks > 1) return 0; } }
   return L->boundary_condition.num_blocks[stencil_get_shape()] <= 64;
 }
@@ -71,7 +70,7 @@ static double small_ops_issue(level_type *L, int value_kind, int va, int vb, int
   lz_busy = 1;                                            /* from here on every device call (the first hp_backend_of() of a level uploads its tables) runs at once */
   backend_t *B = hp_backend_of(L);
   hpgmg_config cfg;
-  int kinds[16], c[16], a[16], b[16], q, n = 0, bc_kind, zero_first = 0;
+  int kinds[16], c[16], a[16], b[16], q, n = 0;
   double sa[16], sb[16], op_a = 0.0, op_b = 0.0, v = 0.0;
   hpgmg_get_config(&cfg);
   for (q = 0; q < lz_n; q++, n++) {
@@ -83,13 +82,10 @@ static double small_ops_issue(level_type *L, int value_kind, int va, int vb, int
   if (value_kind && p_kind) { kinds[n] = p_kind; c[n] = 0; a[n] = pa; b[n] = pb; sa[n] = sb[n] = 0.0; n++; }
   lz_n = 0; lz_mode = LZ_NONE;
   const int shape = stencil_get_shape(), n_bc = L->boundary_condition.num_blocks[shape];
-  if (cfg.op == HPGMG_OP_7PT) bc_kind = 1;                                                              /* apply_BCs, as the operators themselves choose */
-  else if (cfg.op == HPGMG_OP_27PT) bc_kind = (L->box_dim < 2) ? 1 : 2;
-  else if (cfg.op == HPGMG_OP_FV2 || L->box_dim < 4) { bc_kind = (L->box_dim < 2) ? 1 : 3; zero_first = (bc_kind == 3 && L->box_ghosts > 1); }
-  else { bc_kind = 4; zero_first = (L->box_ghosts > 2); }
+  const hp_small_bc bc = hp_small_bc_rule(cfg.op, L);                                                   /* apply_BCs, as the operators themselves choose */
   {
     TICK(L, blas1, "queued small-level operators, one launch");
-    HIP_OK(hpgmg_hip_small_ops(&B->dev, hp_variant(), n, kinds, c, a, b, sa, sb, n_bc ? hp_mirror(L, L->boundary_condition.blocks[shape], n_bc) : NULL, n_bc, bc_kind, zero_first,
+    HIP_OK(hpgmg_hip_small_ops(&B->dev, hp_variant(), n, kinds, c, a, b, sa, sb, n_bc ? hp_mirror(L, L->boundary_condition.blocks[shape], n_bc) : NULL, n_bc, bc.kind, bc.zero_first,
                                op_a, op_b, 1.0 / (L->h * L->h), value_kind ? &v : NULL, (value_kind && p_kind) ? p_out : NULL));
     TOCK();
   }

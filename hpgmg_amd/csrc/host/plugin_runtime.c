@@ -173,6 +173,33 @@ backend_t *hp_backend_of(level_type *L) {
   return B;
 }
 
+/* ---- level predicates (plugin_internal.h) ---- */
+hp_small_bc hp_small_bc_rule(int op, const level_type *L) {
+  hp_small_bc r = { 1, 0 };
+  if (op == HPGMG_OP_7PT || L->box_dim < 2) return r;
+  if (op == HPGMG_OP_27PT) r.kind = 2;
+  else if (op == HPGMG_OP_FV2 || L->box_dim < 4) { r.kind = 3; r.zero_first = (L->box_ghosts > 1); }
+  else { r.kind = 4; r.zero_first = (L->box_ghosts > 2); }
+  return r;
+}
+int hp_boxes_lexicographic(level_type *L) {
+  backend_t *B = hp_backend_of(L);
+  if (B->lexicographic < 0) {
+    int bx, ok = (L->num_my_boxes == L->boxes_in.i * L->boxes_in.j * L->boxes_in.k);
+    for (bx = 0; ok && bx < L->num_my_boxes; bx++) {
+      const box_type *X = &L->my_boxes[bx];
+      if (X->low.i != (bx % L->boxes_in.i) * L->box_dim || X->low.j != ((bx / L->boxes_in.i) % L->boxes_in.j) * L->box_dim ||
+          X->low.k != (bx / (L->boxes_in.i * L->boxes_in.j)) * L->box_dim) ok = 0;
+    }
+    B->lexicographic = ok;
+  }
+  return B->lexicographic;
+}
+int *hp_krylov_pinned(backend_t *B) {
+  if (!B->krylov_pinned) { B->krylov_pinned = (int *)hpgmg_hip_host_malloc(64); if (B->krylov_pinned) *B->krylov_pinned = 0; }
+  return B->krylov_pinned;
+}
+
 /* device mirror of one immutable host list (uploaded on first use) */
 const blockCopy_type *hp_mirror(level_type *owner, const blockCopy_type *host, int n) {
   int s;

@@ -522,7 +522,7 @@ static long long fp32_pair_smooths = 0;
 long long hpgmg_fp32_pair_smooths(void) { return fp32_pair_smooths; }     /* smooth() calls run on rounded coefficients (tests) */
 
 /* Does the HIP plugin run this smooth() as sweep pairs on fp32 coefficients?  The same rule as pair_kernel_ready
- * (hpgmg_amd/csrc/host/plugin_smooth.c) and pair_supported_dims (kernels/pair.hip), derived from the level's geometry; the
+ * (hpgmg_amd/csrc/host/plugin_pairs.c) and pair_supported_dims (kernels/pair.hip), derived from the level's geometry; the
  * plugin's switches that could turn the pairs off (HPGMG_FUSED_SWEEPS, HPGMG_GHOST_FREE) are taken at their defaults, and its storage
  * conditions (16-byte aligned boxes at a constant distance) hold for every level the host layer creates.  Keep the two in step. */
 static int fp32_pair_smooth(const level_type *L, const hpgmg_config *cfg, int x_id, int rhs_id, int sweeps) {

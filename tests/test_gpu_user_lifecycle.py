@@ -3,7 +3,7 @@ boundary data, warm starts, methods and switches computes at every step the bits
 to a fresh solver per step.  What lives across calls on the HIP side only, and which test reaches it:
 
   hipGraph segments (kernels/graph.hip, keyed by host/mg.c seg_reset)     test_graph_segments_*: 32^3 / 48^3, every level <= 64^3 lies in segments
-  fp32 coefficient copies (plugin_smooth.c coef32_of)                      test_sweep_pair_level_*: 128^3 in boxes of 64, the smallest sweep-pair level
+  fp32 coefficient copies (plugin_pairs.c coef32_of)                       test_sweep_pair_level_*: 128^3 in boxes of 64, the smallest sweep-pair level
   packed edge coefficients of the sweep-pair pre-pass (pair.hip EdgePack)  test_packed_edge_coefficients_*: 256^3 in boxes of 128 (two 128-cell i tiles)
   staging buffer, lazy queue, one-shot statics, two live solvers           test_reused_solver_*, test_two_live_solvers_*
   all of these across the first start()'s new storage of the finest level  test_a_marching_solver_*, test_packed_edge_coefficients_across_the_storage_*
