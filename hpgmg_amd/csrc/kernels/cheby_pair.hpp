@@ -16,7 +16,8 @@
 //   * j neighbours of x0 / x1 and the upper beta_j face: the neighbouring wave's row via LDS (x0 and beta_j are
 //     deposited one step ahead; one __syncthreads per step, buffers double-buffered);
 //   * i neighbours: adjacent lane (shuffle).  Across a 128-cell tile edge x0 is read from memory; x1 there was
-//     written beforehand by cheby_pair_edge_kernel (the columns next to interior tile edges, 0.8 % of the cells);
+//     written beforehand by cheby_pair_edge_kernel (the columns next to interior tile edges, 0.8 % of the cells) -- or, in the EDGEW instances, both come through LDS
+//     from an eleventh wave of the workgroup that forms x1 on those two columns while the ten march (pair_edge_wave below): no pre-pass launch;
 //   * the domain boundary is the in-register Dirichlet rule ghost = -centre (apply_BCs_p1), applied to x0 for
 //     the first sweep and to x1 for the second, as the reference does between sweeps.
 //   * the march runs in segments (one box, away from the ends of the chunk and of the domain): the boxes and the base of every stream are looked up once per
@@ -172,8 +173,82 @@ __device__ __forceinline__ p2 pair_form_dinv(const PlaneCoef<V> &q, double fil, 
 }
 
 constexpr int kPairMaxBoxes = 1024;       // boxes per rank the pair kernel takes (their base-pointer tables are copied into LDS, see below)
-template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP, bool REMOTE = false, bool FORM = false>
-__global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_level L_in, const PairArgs A_in) {
+
+// ---- the edge wave (EDGEW instances of cheby_pair_kernel): wave NW of the workgroup, which never enters the march.  It forms x1 on the two cell columns next to the
+// tile -- gi0 - 1 (side 0) and gi0 + 128 (side 1) -- that lanes 0 / 63 of the main waves read as i neighbours of the second sweep, and hands them over in LDS together with
+// x0 of the same columns for the first sweep: with it the launch needs no pre-pass (cheby_pair_edge_kernel) and a main wave no single-lane load.  One lane per (side, row):
+// lane side * 16 + r serves row R - 1 + r of the slab, r = 0 .. NW - 1; a side at a domain wall has no lanes.  Per step p, the planes and the step count of the main waves:
+//   * x0 of its column on plane p + 1: one 16-byte load that also brings the column beyond it -- (gi0 - 2, gi0 - 1) or (gi0 + 128, gi0 + 129), the i neighbour outside the
+//     tile; the two cells share one coarse parent (INTERP).  Planes p - 1, p, p + 1 stay in registers; plane p + 1 goes to extX0[(p + 1) & 1] -- the slabX0 protocol;
+//   * on the output rows and planes, x1 of its cell on plane p by the expression tree of cheby_pair_edge_kernel: the i neighbour inside the tile from slabX0[p & 1] (lane 63's
+//     second / lane 0's first cell), the j neighbours from the adjacent lanes (rows R - 1 and R + NR only supply values), a wall in j or k gives -centre, the eight
+//     coefficient values from the packed line A.edge_coef[col][k][j][8] (Dinv as stored), rhs and -- when c1a != 0 -- x_{n-1} from the level;
+//   * x1 goes to extX1[p & 1]; then the step's one barrier.
+// Every wave of the workgroup passes the same barriers: this one the prologue's and one per plane p of the march, as the main waves do in steps of either kind.
+template <int V, int NW, bool INTERP>
+__device__ __forceinline__ void pair_edge_wave(const hpgmg_hip_level &L, const PairArgs &A, p2 (*slabX0)[NW][64], double (*extX0)[2][16], double (*extX1)[2][16],
+                                               int ti, int gi0, int R, int NRs, int K0, int KCs) {
+  constexpr bool kHelm = (V == HPGMG_HIP_7PT_VC_HELMHOLTZ);
+  const int lane = (int)threadIdx.x, side = (lane >> 4) & 1, r = lane & 15;
+  const int bd = L.dim, jS = L.jStride, kS = L.kStride;
+  const int gj = R - 1 + r;
+  const bool at_wall = side ? (gi0 + 128 == A.Di) : (gi0 == 0);
+  const bool active = lane < 32 && r < NW && r <= NRs + 1 && gj >= 0 && gj < A.Dj && !at_wall;      // the rows the main waves form x1 on (row_x1)
+  const bool forms = active && r >= 1 && r <= NRs;                                                  // ... and x2 (row_out): x1 of the edge column is read there
+  // the lane's pair starts at an even column; its own cell is the second one on side 0, the first one on side 1
+  const int gp = active ? (side ? gi0 + 128 : gi0 - 2) : 0, gjc = active ? gj : 0;
+  const int bi = gp / bd, li = gp - bi * bd, bj = gjc / bd, lj = gjc - bj * bd;
+  const int row = li + lj * jS, own = row + (side ? 0 : 1);
+  const int col = side ? 2 * ti + 1 : 2 * (ti - 1);                                                   // the column's number in the packed coefficients (cheby_pair_edge_kernel)
+  const int cjS = INTERP ? A.Lc.jStride : 0, ckS = INTERP ? A.Lc.kStride : 0;
+  auto box_at = [&](int gk) { return bi + A.nbi * (bj + A.nbj * (gk / bd)); };
+  auto x0_at = [&](int gk) -> p2 {
+    const int box = box_at(gk), lk = gk % bd;
+    p2 v = pld(pair_vec(L, A, A.x0, box) + (row + lk * kS));
+    if (INTERP) {
+      const double c = gld1(vec_origin(A.Lc, box, A.coarse_id) + ((li >> 1) + (lj >> 1) * cjS + (lk >> 1) * ckS));
+      v.x = A.prescale * v.x + c; v.y = A.prescale * v.y + c;
+    }
+    return v;
+  };
+  const int P0 = K0 - 1, P1 = K0 + KCs;
+  const int pstart = (P0 >= 0) ? P0 : P0 + 1;
+  p2 em = {0, 0}, ec = {0, 0}, ep = {0, 0};                      // x0 pair on planes p-1, p, p+1
+  if (active) {
+    ec = x0_at(pstart);
+    if (pstart - 1 >= 0) em = x0_at(pstart - 1);
+    extX0[pstart & 1][side][r] = side ? ec.x : ec.y;
+  }
+  __syncthreads();
+  for (int p = pstart; p <= P1 && p < A.Dk; p++) {
+    const bool above_in = (p + 1 < A.Dk), have_next = above_in && (p + 1 <= P1);
+    const bool out_plane = (p >= K0 && p < K0 + KCs);            // x2 is formed on this plane (in the next step): its x1 is needed
+    if (active && above_in) ep = x0_at(p + 1);
+    const double xc = side ? ec.x : ec.y;
+    const double jm_lane = __shfl_up(xc, 1, 64), jp_lane = __shfl_down(xc, 1, 64);
+    if (forms && out_plane) {
+      const int box = box_at(p), idx = own + (p % bd) * kS;
+      const double *const pk = A.edge_coef + ((size_t)(col * A.Dk + p) * A.Dj + gj) * 8;            // one 64-byte line per cell
+      const d2v v0 = *(gd2cptr)as_global(pk), v1 = *(gd2cptr)as_global(pk + 2), v2 = *(gd2cptr)as_global(pk + 4), v3 = *(gd2cptr)as_global(pk + 6);
+      const double rhs = gld1(vec_origin(L, box, A.rhs_id) + idx);
+      const double xnm1 = (A.c1a != 0.0) ? gld1(pair_vec(L, A, A.xm1, box) + idx) : xc;             // as in the main waves: not read when its coefficient is 0
+      const double left = side ? slabX0[p & 1][r][63].y : ec.x, right = side ? ec.y : slabX0[p & 1][r][0].x;
+      const double jm = (gj - 1 < 0) ? -xc : jm_lane, jp = (gj + 1 >= A.Dj) ? -xc : jp_lane;
+      const double km = (p - 1 >= 0) ? (side ? em.x : em.y) : -xc, kp = above_in ? (side ? ep.x : ep.y) : -xc;
+      const double Ax = apply_op_7pt<V>(xc, left, right, jm, jp, km, kp, v0.x, v0.y, v1.x, v1.y, v2.x, v2.y, kHelm ? v3.x : 0.0, A.a, A.b, A.h2inv);
+      extX1[p & 1][side][r] = xc + A.c1a * (xc - xnm1) + A.c2a * v3.y * (rhs - Ax);
+    }
+    if (active && have_next) extX0[(p + 1) & 1][side][r] = side ? ep.x : ep.y;
+    __syncthreads();
+    em = ec; ec = ep;
+  }
+}
+
+// EDGEW: the workgroup has NW + 1 waves, launched with dim3(64, NW + 1); the last one is the edge wave above, the others run the march unchanged but for lanes 0 / 63,
+// which take their two neighbours across a tile edge from LDS.  Such a launch has no pre-pass.  10 waves, Chebyshev, fp64 variable coefficients, whole-row boxes, one rank:
+// 11 waves are three per SIMD -- the register budget the 10-wave instances live under already; a 13th wave would put four on one SIMD.
+template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP, bool REMOTE = false, bool FORM = false, bool EDGEW = false>
+__global__ __launch_bounds__(64 * (NW + (EDGEW ? 1 : 0))) void cheby_pair_kernel(const hpgmg_hip_level L_in, const PairArgs A_in) {
   static_assert(!(REMOTE && C32) && !(REMOTE && NARROW && INTERP), "the multi-rank variant is built for fp64 coefficients; with narrow boxes the interpolation is not folded in");
   // REMOTE + INTERP: the parent is added to the cells of the brick only -- what arrives in ghost zones and deep planes was packed by its owner with ITS parents already added (pair_halo_kernel)
   constexpr bool kVC = (V != HPGMG_HIP_7PT_CC);
@@ -183,6 +258,7 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
   // 2 % slower than before whichever way it pointed.  fp64 coefficient streams of one rank; not the 16-wave instances: held to 128 registers
   // they spill 7 as they are and 27 with the division.
   static_assert(!FORM || (kVC && !C32 && !REMOTE && NW != 16), "no FORM instance of this kind");
+  static_assert(!EDGEW || (SM == PAIR_CHEBY && kVC && !C32 && !NARROW && !REMOTE && NW == 10), "no EDGEW instance of this kind");
   extern __shared__ p2 pair_lds[];                              // 3 x [2 buffers][NW rows][64 pairs] = NW x 6 KiB
   p2 (*slabX0)[NW][64] = reinterpret_cast<p2 (*)[NW][64]>(pair_lds);
   p2 (*slabX1)[NW][64] = reinterpret_cast<p2 (*)[NW][64]>(pair_lds + 2 * NW * 64);
@@ -196,10 +272,12 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
   __shared__ double *sTabScr[kPairMaxBoxes];
   __shared__ const float *sTabC32[C32 ? kPairMaxBoxes : 1];
   __shared__ double *sTabCrs[INTERP ? kPairMaxBoxes : 1];
+  // EDGEW: the edge columns' x0 (plane p, deposited one step ahead) and x1 (plane p - 1), [buffer][side][row of the slab], written by the edge wave
+  __shared__ double extX0[EDGEW ? 2 : 1][2][16], extX1[EDGEW ? 2 : 1][2][16];
   hpgmg_hip_level L = L_in;
   PairArgs A = A_in;
   {
-    const int nt = 64 * NW, tid0 = (int)threadIdx.y * 64 + (int)threadIdx.x;
+    const int nt = 64 * (NW + (EDGEW ? 1 : 0)), tid0 = (int)threadIdx.y * 64 + (int)threadIdx.x;
     for (int bx = tid0; bx < L_in.num_boxes; bx += nt) {
       sTabLvl[bx] = L_in.box_base[bx];
       sTabScr[bx] = A_in.scr_base ? A_in.scr_base[bx] : nullptr;
@@ -225,6 +303,9 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
   const int gi0 = ti * 128, R = sj * NR, K0 = ck * A.KC;
   const int NRs = (R + NR <= A.Dj) ? NR : A.Dj - R;          // output rows of this slab
   const int KCs = (K0 + A.KC <= A.Dk) ? A.KC : A.Dk - K0;    // output planes of this chunk
+  if constexpr (EDGEW) {
+    if (w == NW) { pair_edge_wave<V, NW, INTERP>(L, A, slabX0, extX0, extX1, ti, gi0, R, NRs, K0, KCs); return; }
+  }
   const int gj = R - 1 + w;
   // rows / planes on which x1 is formed, and on which x0 is known: the brick, plus one (two) layers across a remote face
   const int jlo = (REMOTE && A.rem[2]) ? -1 : 0, jhi = (REMOTE && A.rem[3]) ? A.Dj + 1 : A.Dj;
@@ -396,8 +477,14 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
       const p2 km = x0plane(p - 1) ? x0m : pneg(x0c);
       const p2 kp = above_in ? x0p : pneg(x0c);
       double left = __shfl_up(x0c.y, 1, 64), right = __shfl_down(x0c.x, 1, 64);
+      if (EDGEW) {                                               // across a tile edge: what the edge wave deposited one step ahead
+        const double eL = extX0[p & 1][0][w], eR = extX0[p & 1][1][w];
+        if (lane == 0)  left  = left_dom  ? -x0c.x : eL;
+        if (lane == 63) right = right_dom ? -x0c.y : eR;
+      } else {
       if (lane == 0)  left  = (left_dom && !left_ghost)   ? -x0c.x : x0_one(box_of(biL, bj_, p), liL, lj, p);
       if (lane == 63) right = (right_dom && !right_ghost) ? -x0c.y : x0_one(box_of(biR, bj_, p), liR, lj, p);
+      }
       // GSRB: cell (gi, gj, gk) is swept in half sweep s when (gi ^ gj ^ gk ^ s) is even; a pair starts at an even gi
       // (brick origins are multiples of the box size, so brick-local and global parities agree)
       if (!(ghost_row && ghost_plane))                          // a ghost row on a ghost plane is a brick edge: x1 there is never read
@@ -419,8 +506,14 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
       const p2 kp = x1c;                                         // x1 was formed on plane p
       double left = __shfl_up(x1m1.y, 1, 64), right = __shfl_down(x1m1.x, 1, 64);
       // across a tile edge -- and, REMOTE, across a remote i face -- x1 was written beforehand by cheby_pair_edge_kernel
+      if (EDGEW) {                                               // ... or, EDGEW, formed by the edge wave in the step before
+        const double eL = extX1[q & 1][0][w], eR = extX1[q & 1][1][w];
+        if (lane == 0)  left  = left_dom  ? -x1m1.x : eL;
+        if (lane == 63) right = right_dom ? -x1m1.y : eR;
+      } else {
       if (lane == 0)  left  = (left_dom && !left_ghost)   ? -x1m1.x : gld1(pair_vec(L, A, A.out1, box_of(biL, bj_, q)) + (liL + lj * jS + plane_off(q)));
       if (lane == 63) right = (right_dom && !right_ghost) ? -x1m1.y : gld1(pair_vec(L, A, A.out1, box_of(biR, bj_, q)) + (liR + lj * jS + plane_off(q)));
+      }
       const p2 x2 = pair_update<V, SM>(x1m1, left, right, jm, jp, km, kp, x0m, qp, A.a, A.b, A.h2inv, A.c1b, A.c2b, ((gj ^ q ^ (A.sweep_a + 1)) & 1) == 0);
       pst(pair_vec(L, A, A.out2, boxq) + shift_of(sh, A.out2) + offq, x2);
     }
@@ -532,6 +625,11 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
           if (jm_wall) jm = pneg(x0c); else if (jm_far) jm = far_c; else jm = slabX0[p & 1][w - 1][lane];
           if (jp_wall) jp = pneg(x0c); else if (jp_far) jp = far_c; else jp = slabX0[p & 1][w + 1][lane];
           double left = __shfl_up(x0c.y, 1, 64), right = __shfl_down(x0c.x, 1, 64);
+          if (EDGEW) {
+            const double eL = extX0[p & 1][0][w], eR = extX0[p & 1][1][w];
+            if (lane == 0)  left  = left_dom  ? -x0c.x : eL;
+            if (lane == 63) right = right_dom ? -x0c.y : eR;
+          } else {
           if (lane == 0) {
             if (left_dom) left = -x0c.x;
             else { left = gld1(s_x0L + po); if (INTERP) left = A.prescale * left + gld1(c_L + (lk >> 1) * ckS); }
@@ -539,6 +637,7 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
           if (lane == 63) {
             if (right_dom) right = -x0c.y;
             else { right = gld1(s_x0R + po); if (INTERP) right = A.prescale * right + gld1(c_R + (lk >> 1) * ckS); }
+          }
           }
           x1c = pair_update<V, SM>(x0c, left, right, jm, jp, x0m, x0p, xm1, qc, A.a, A.b, A.h2inv, A.c1a, A.c2a, ((gj ^ p ^ A.sweep_a) & 1) == 0);
         }
@@ -553,8 +652,14 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
           if (x2_jm_wall) jm = pneg(x1m1); else jm = slabX1[q & 1][w - 1][lane];
           if (x2_jp_wall) jp = pneg(x1m1); else jp = slabX1[q & 1][w + 1][lane];
           double left = __shfl_up(x1m1.y, 1, 64), right = __shfl_down(x1m1.x, 1, 64);
+          if (EDGEW) {
+            const double eL = extX1[q & 1][0][w], eR = extX1[q & 1][1][w];
+            if (lane == 0)  left  = left_dom  ? -x1m1.x : eL;
+            if (lane == 63) right = right_dom ? -x1m1.y : eR;
+          } else {
           if (lane == 0)  left  = left_dom  ? -x1m1.x : gld1(s_o1Lq + po);
           if (lane == 63) right = right_dom ? -x1m1.y : gld1(s_o1Rq + po);
+          }
           const p2 x2 = pair_update<V, SM>(x1m1, left, right, jm, jp, x1m2, x1c, x0m, qp, A.a, A.b, A.h2inv, A.c1b, A.c2b, ((gj ^ q ^ (A.sweep_a + 1)) & 1) == 0);
           pst_so(s_o2q, eO2 + (unsigned)po, x2);
         }
@@ -587,8 +692,14 @@ __global__ __launch_bounds__(64 * NW) void cheby_pair_kernel(const hpgmg_hip_lev
       const p2 km = in_dom(q - 1) ? x1m2 : pneg(x1m1);
       const p2 kp = pneg(x1m1);
       double left = __shfl_up(x1m1.y, 1, 64), right = __shfl_down(x1m1.x, 1, 64);
+      if (EDGEW) {                                               // ... or, EDGEW, formed by the edge wave in the step before
+        const double eL = extX1[q & 1][0][w], eR = extX1[q & 1][1][w];
+        if (lane == 0)  left  = left_dom  ? -x1m1.x : eL;
+        if (lane == 63) right = right_dom ? -x1m1.y : eR;
+      } else {
       if (lane == 0)  left  = (left_dom && !left_ghost)   ? -x1m1.x : gld1(pair_vec(L, A, A.out1, box_of(biL, bj_, q)) + (liL + lj * jS + plane_off(q)));
       if (lane == 63) right = (right_dom && !right_ghost) ? -x1m1.y : gld1(pair_vec(L, A, A.out1, box_of(biR, bj_, q)) + (liR + lj * jS + plane_off(q)));
+      }
       const p2 x2 = pair_update<V, SM>(x1m1, left, right, jm, jp, km, kp, x0m, qp, A.a, A.b, A.h2inv, A.c1b, A.c2b, ((gj ^ q ^ (A.sweep_a + 1)) & 1) == 0);
       pst(pair_vec(L, A, A.out2, boxq) + shift_of(sh, A.out2) + offq, x2);
     }

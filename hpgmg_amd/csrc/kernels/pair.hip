@@ -61,6 +61,30 @@ static int pair_launch(int grid, size_t lds, const hpgmg_hip_level *L, const Pai
   return pair_launch_instance<V, NW, C32, SM, NARROW, INTERP, false>(grid, lds, L, A);
 }
 
+// The EDGEW twin of a 10-wave Chebyshev instance (cheby_pair.hpp: an eleventh wave forms x1 on the tile-edge columns, no pre-pass): taken where it exists and applies --
+// fp64 variable coefficients, one rank, boxes of whole rows, an interior tile edge, the packed coefficient values at hand.  *taken false: the caller launches the pre-pass and the plain instance.
+static long long g_pair_edge_wave_launches = 0;
+template <int V, int SM, bool C32, bool INTERP, bool FORM>
+static int pair_launch_edge_wave_instance(int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A) {
+  constexpr int NW = 10;
+  static bool once = false;
+  if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)cheby_pair_kernel<V, NW, C32, SM, false, INTERP, false, FORM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; }
+  hipLaunchKernelGGL((cheby_pair_kernel<V, NW, C32, SM, false, INTERP, false, FORM, true>), dim3(grid), dim3(64, NW + 1), lds, g_stream, *L, A);
+  return 0;
+}
+template <int V, int SM, bool C32, bool INTERP>
+static int pair_launch_edge_wave(int nw, int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A, bool *taken) {
+  *taken = false;
+  if constexpr (V != HPGMG_HIP_7PT_CC && SM == PAIR_CHEBY && !C32) {
+    if (nw != 10 || L->dim % 128 != 0 || A.tiles_i < 2 || !A.edge_coef) return 0;
+    *taken = true;
+    g_pair_edge_wave_launches++;
+    if (A.form_dinv) return pair_launch_edge_wave_instance<V, SM, C32, INTERP, true>(grid, lds, L, A);
+    return pair_launch_edge_wave_instance<V, SM, C32, INTERP, false>(grid, lds, L, A);
+  }
+  return 0;
+}
+
 extern "C" {
 int hpgmg_hip_graph_flush(void);
 
@@ -256,11 +280,15 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
       A.edge_blocks = ((A.Dj + 63) / 64) * A.Dk * 2 * (A.tiles_i - 1); const dim3 egrid(A.edge_blocks > 0 ? grid_for(A.edge_blocks, &A.edge_per_xcd) : 1); \
       if (remote) PAIR_LAUNCH_REMOTE(VAR, SM) \
       else if (interp) { \
+        bool ew_; { const int e_ = pair_launch_edge_wave<VAR, SM, C32, true>(nw, grid, lds, L, A, &ew_); if (e_) return e_; } \
+        if (!ew_) { \
         if (A.tiles_i > 1) hipLaunchKernelGGL((cheby_pair_edge_kernel<VAR, C32, SM, true>), egrid, dim3(64), 0, g_stream, *L, A); \
-        if (L->dim % 128 == 0) PAIR_LAUNCH2(VAR, C32, SM, false, true) else PAIR_LAUNCH2(VAR, C32, SM, true, true) \
+        if (L->dim % 128 == 0) PAIR_LAUNCH2(VAR, C32, SM, false, true) else PAIR_LAUNCH2(VAR, C32, SM, true, true) } \
       } else { \
+        bool ew_; { const int e_ = pair_launch_edge_wave<VAR, SM, C32, false>(nw, grid, lds, L, A, &ew_); if (e_) return e_; } \
+        if (!ew_) { \
         if (A.tiles_i > 1) hipLaunchKernelGGL((cheby_pair_edge_kernel<VAR, C32, SM, false>), egrid, dim3(64), 0, g_stream, *L, A); \
-        if (L->dim % 128 == 0) PAIR_LAUNCH2(VAR, C32, SM, false, false) else PAIR_LAUNCH2(VAR, C32, SM, true, false) \
+        if (L->dim % 128 == 0) PAIR_LAUNCH2(VAR, C32, SM, false, false) else PAIR_LAUNCH2(VAR, C32, SM, true, false) } \
       } }
 #define PAIR_CASE(VAR) case VAR: \
     if (gsrb) { if (c32_base) PAIR_LAUNCH(VAR, true, PAIR_GSRB) else PAIR_LAUNCH(VAR, false, PAIR_GSRB) } \
@@ -301,6 +329,7 @@ void hpgmg_hip_exp_timeline(void *buf) { g_exp_timeline = (double *)buf; }
 #endif
 void hpgmg_hip_pair_launch_counts(long long out[2]) { out[0] = g_pair_launches; out[1] = g_pair_remote_launches; }
 long long hpgmg_hip_pair_formed_dinv_launches(void) { return g_pair_formed_launches; }
+long long hpgmg_hip_pair_edge_wave_launches(void) { return g_pair_edge_wave_launches; }
 
 // ---- the halo of a sweep pair across rank boundaries: one pack launch, one grouped send/recv, one unpack launch ----
 static const hpgmg_hip_level *g_halo_fold_level = nullptr;      // consumed by the next pack (hpgmg_hip_pair_halo_fold_interpolation)

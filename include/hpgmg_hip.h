@@ -228,6 +228,7 @@ int hpgmg_hip_smooth_cheby_pair(const hpgmg_hip_level *L, int variant, double *c
  * exactly these a, b, h2inv.  The launch may then form Dinv per cell from the coefficient streams it reads anyway instead of reading the vector (same expression tree,
  * same bits; one stream of ten less).  Taken by the fp64, one-rank, variable-coefficient instances of 10 and 12 waves; every other launch reads the vector as with 0. */
 long long hpgmg_hip_pair_formed_dinv_launches(void);      /* sweep-pair launches so far that formed Dinv (tests) */
+long long hpgmg_hip_pair_edge_wave_launches(void);        /* sweep-pair launches so far whose eleventh wave formed the tile-edge columns: no pre-pass (tests) */
 /* Sweep pairs across rank boundaries (boxes over the GPUs of a node, halo exchange over RCCL).  This rank's boxes form a
  * brick of brick_boxes[0..2] boxes (numbered lexicographically inside it); remote_face[f] (f = -i,+i,-j,+j,-k,+k) is 1 where the
  * brick face belongs to another rank, 0 where it is the (Dirichlet) domain boundary.  Before the launch the caller must have

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """What a plane step of cheby_pair_kernel executes, read from the gfx950 assembly (needs the compiler, no GPU).
 
-usage: tools/pair_loop_stats.py [--asm FILE.s | --src FILE.hip] [INSTANCE ...]
-  INSTANCE: the template arguments <V,NW,C32,SM,NARROW,INTERP,REMOTE,FORM>, e.g. 0,10,false,0,false,false,false,true
-  default:  the config-2 instance, its NARROW twin, its INTERP twin and the 12-wave instance
+usage: tools/pair_loop_stats.py [--asm FILE.s [--before-edgew] | --src FILE.hip] [INSTANCE ...]
+  INSTANCE: the template arguments <V,NW,C32,SM,NARROW,INTERP,REMOTE,FORM[,EDGEW]>, e.g. 0,10,false,0,false,false,false,true (EDGEW: false when left out)
+  default:  the config-2 instance of the pre-pass path, its NARROW twin, its INTERP twin and the 12-wave instance, then the EDGEW twins config 2 runs (an eleventh wave
+            forms the tile-edge columns; the loop reported is the main waves' segment step, the edge wave's own loop is the smaller one)
 Without --asm, hpgmg_amd/csrc/kernels/pair.hip (or --src) is compiled to device assembly with the flags of the Makefile.
 
 Per instance: the kernel's VGPR / SGPR counts and spill counts, and for its largest INNERMOST loop (natural loops of the control-flow graph; the one that holds no
@@ -18,12 +19,18 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULT = ["0,10,false,0,false,false,false,true", "0,10,false,0,true,false,false,true", "0,10,false,0,false,true,false,true", "0,12,false,0,false,false,false,true"]
+DEFAULT = ["0,10,false,0,false,false,false,true", "0,10,false,0,true,false,false,true", "0,10,false,0,false,true,false,true", "0,12,false,0,false,false,false,true",
+           "0,10,false,0,false,false,false,true,true", "0,10,false,0,false,true,false,true,true"]
+
+
+BEFORE_EDGEW = False      # --before-edgew: the assembly is of a commit whose kernel has eight template parameters
 
 
 def mangled(inst):
     parts = [a.strip() for a in inst.split(",")]
-    assert len(parts) == 8, "eight template arguments"
+    assert len(parts) in (8, 9), "eight template arguments, or nine with EDGEW"
+    if len(parts) == 8 and not BEFORE_EDGEW:
+        parts.append("false")
     enc = "".join("Lb%dE" % (a == "true") if a in ("true", "false") else "Li%sE" % a for a in parts)
     return "cheby_pair_kernelI" + enc + "E"
 
@@ -210,8 +217,11 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--asm", help="device assembly of pair.hip, already compiled")
     ap.add_argument("--src", default=os.path.join(ROOT, "hpgmg_amd", "csrc", "kernels", "pair.hip"))
+    ap.add_argument("--before-edgew", action="store_true", help="the assembly (--asm) comes from a commit before the EDGEW template parameter: eight arguments in the symbol")
     ap.add_argument("instances", nargs="*", default=DEFAULT)
     args = ap.parse_args()
+    global BEFORE_EDGEW
+    BEFORE_EDGEW = args.before_edgew
     lines = open(args.asm or compile_asm(args.src)).read().splitlines()
     for inst in args.instances:
         report(lines, inst)
