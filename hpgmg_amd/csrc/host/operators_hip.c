@@ -86,10 +86,12 @@ static int fused_residual_on(void) {
 /* the operand of a fused residual form is made ready: 7-point -- nothing (the kernel applies the Dirichlet rule and reads neighbouring boxes);
  * 27-point / fv4 -- the domain-boundary ghost cells (the tiled kernel reads neighbouring boxes itself).  0 = the level does not qualify;
  * 2 = x is crossing faces to other ranks on the exchange stream: FUSED_LAUNCH issues the pass as the tiles that touch no such face, the wait, the others. */
-#define FUSED_LAUNCH(READY, CALL) do {                                                                          \
+/* B: the level of the pass.  Where its alpha is known to be uniform the launch is told so (one-shot, consumed by the launch: hp_alpha_uniform_arm_residual; one rank only) */
+#define FUSED_LAUNCH(B, READY, CALL) do {                                                                       \
     if ((READY) == 2) {                                                                                          \
       hpgmg_hip_set_tile_part(1); HIP_OK(CALL); hp_overlap_end(); hpgmg_hip_set_tile_part(2); HIP_OK(CALL); hpgmg_hip_set_tile_part(0); \
-    } else HIP_OK(CALL); } while (0)
+    } else HIP_OK((hp_alpha_uniform_arm_residual(B), CALL));      /* (armed inside HIP_OK: behind the operators it issues first) */ \
+  } while (0)
 static int fused_residual_operand_form(level_type *L, backend_t *B, int x_id, int restrict_form);
 static int fused_residual_operand(level_type *L, backend_t *B, int x_id) { return fused_residual_operand_form(L, B, x_id, 0); }
 /* restrict_form: residual + restriction + zero_vector, which the 7-point plugin also has for the launch-bound levels of small boxes (one launch instead of two) */
@@ -145,7 +147,7 @@ int hp_residual_restrict_zero_fused(level_type *Lc, int id_c, level_type *Lf, in
   const int ready = fused_residual_operand_form(Lf, Bf, x_id, 1);
   if (!ready) return 0;
   TICK(Lf, residual, "residual + restriction + zero_vector (fused)");
-  FUSED_LAUNCH(ready, hpgmg_hip_residual_restrict_store(hp_stencil_dev(Bf), hp_variant(), res_id, x_id, rhs_id, a, b, 1.0 / (Lf->h * Lf->h), &Bc->dev, id_c, Bf->d_restrict_map, zero_id));
+  FUSED_LAUNCH(Bf, ready, hpgmg_hip_residual_restrict_store(hp_stencil_dev(Bf), hp_variant(), res_id, x_id, rhs_id, a, b, 1.0 / (Lf->h * Lf->h), &Bc->dev, id_c, Bf->d_restrict_map, zero_id));
   TOCK();
   return 1;
 }
@@ -225,7 +227,7 @@ int hpgmg_residual_norm_fused(level_type *L, int res_id, int x_id, int rhs_id, d
   if (!ready) return 0;
   double v = 0.0;
   { TICK(L, residual, "residual + norm (fused)");
-    FUSED_LAUNCH(ready, hpgmg_hip_residual_norm(hp_stencil_dev(B), hp_variant(), res_id, x_id, rhs_id, a, b, 1.0 / (L->h * L->h), &v));
+    FUSED_LAUNCH(B, ready, hpgmg_hip_residual_norm(hp_stencil_dev(B), hp_variant(), res_id, x_id, rhs_id, a, b, 1.0 / (L->h * L->h), &v));
     TOCK(); }
   *norm_out = hp_allreduce_scalar(L, v, HPGMG_REDUCE_MAX);
   return 1;

@@ -57,6 +57,10 @@ typedef struct {
    * path of rebuild_operator, cleared by hp_coef32_invalidate and by every write into a vector VECTOR_DINV .. VECTOR_ALPHA (hp_coef_written).  While it holds, the
    * sweep-pair launches may form Dinv in registers instead of reading it (kernels/cheby_pair.hpp: PairArgs.form_dinv). */
   int dinv_rebuilt; double dinv_a, dinv_b, dinv_h2inv;
+  /* "VECTOR_ALPHA is the one bit pattern alpha_value in every interior cell of this rank's boxes": read off the data (never assumed) by hp_alpha_record_check at the end of the
+   * 7-point Helmholtz path of rebuild_operator, right after the Dinv record is set, and cleared WITH that record (hp_dinv_record_clear): whatever invalidates Dinv
+   * invalidates it.  While it holds, the UA instances of the sweep pairs and of the wide fused residual passes take alpha from their arguments. */
+  int alpha_uniform; double alpha_value;
   int lexicographic;           /* -1 unknown, else whether local box b sits at (b % nb, (b / nb) % nb, b / nb^2) and all boxes are local */
   int *d_restrict_map;         /* fused residual + restriction: per fine box the coarse box and the coarse cell under its first cell (device) */
   struct pair_halo *halo;      /* sweep pairs across rank boundaries: brick shape, message plans, deep halos (NULL: not built / not applicable) */
@@ -130,7 +134,7 @@ typedef struct halo_images {
 /* ---- run-time switches: one table (plugin_switches.c) ---- */
 typedef enum { SW_GHOST_FREE = 0, SW_ONE_LAUNCH_GHOSTS, SW_OVERLAP, SW_PAIR_REMOTE, SW_IMAGES, SW_FUSED_SWEEPS, SW_PAIR_MIN_CELLS, SW_FUSED_RESIDUAL, SW_FUSED_TAIL,
                SW_FUSED_FTAIL, SW_FUSED_BOTTOM, SW_SMALL_FUSED, SW_SMALL_VTAIL, SW_SMALL_27PT_GSRB, SW_SMALL_OPS, SW_LAZY, SW_LAZY_REPORT, SW_TEMP_SCRATCH,
-               SW_FV4_NO_EXACT_RB, SW_GRAPH, SW_SMOOTHER_PRECISION, SW_DEFER_NORM, SW_BRICK_VISITS, SW_BRICK_SIZE, SW_BRICK_MIN_DIM, SW_BRICK_FSTEP, SW_BRICK_CHAIN, SW_BRICK_WIDE, SW_BRICK_WIDE_MAX_DIM, SW_BRICK_WIDE_TAIL_DIM, SW_FTAIL_MAX_DIM, SW_PAIR_FORM_DINV, SW_COUNT } hp_switch_id;
+               SW_FV4_NO_EXACT_RB, SW_GRAPH, SW_SMOOTHER_PRECISION, SW_DEFER_NORM, SW_BRICK_VISITS, SW_BRICK_SIZE, SW_BRICK_MIN_DIM, SW_BRICK_FSTEP, SW_BRICK_CHAIN, SW_BRICK_WIDE, SW_BRICK_WIDE_MAX_DIM, SW_BRICK_WIDE_TAIL_DIM, SW_FTAIL_MAX_DIM, SW_PAIR_FORM_DINV, SW_UNIFORM_ALPHA, SW_COUNT } hp_switch_id;
 HP_INTERNAL long long hp_switch(hp_switch_id id);                 /* the value in force: the setter's, else the environment's, else the default */
 HP_INTERNAL void hp_switch_set(hp_switch_id id, long long value);
 
@@ -187,7 +191,9 @@ HP_INTERNAL const hpgmg_hip_bc_entry *hp_bc_entries_k(level_type *L, int *n_out,
 HP_INTERNAL int hp_vcycle_legs_fused(level_type **levels, int n, int e_id, int R_id, double a, double b, int leg);
 HP_INTERNAL void hp_coef32_invalidate(level_type *L);
 HP_INTERNAL void hp_dinv_record_set(level_type *L, double a, double b, double h2inv);      /* rebuild_operator, 7-point path: VECTOR_DINV is fresh */
-HP_INTERNAL void hp_dinv_record_clear(level_type *L);
+HP_INTERNAL void hp_dinv_record_clear(level_type *L);                                      /* ... and the uniform-alpha record with it */
+HP_INTERNAL void hp_alpha_record_check(level_type *L);                                     /* rebuild_operator, 7-point Helmholtz, after hp_dinv_record_set: one synchronous pass over VECTOR_ALPHA */
+HP_INTERNAL int  hp_alpha_uniform_arm_residual(const backend_t *B);                       /* a fused residual launch of B's level is next: 1 = told the kernel library that alpha is uniform (one-shot) */
 HP_INTERNAL void hp_dinv_record_forget(level_type *L);                                     /* the level goes away */
 HP_INTERNAL void hp_dinv_record_written(const double *dst, size_t n);                      /* a raw copy into device storage: clears the record of the level whose coefficient vectors it touches */
 /* an operator is about to write vector `id` of the level (ghost zones count: the kernels read the betas' high faces there) */

@@ -39,7 +39,7 @@ static level_type *dinv_recorded[DINV_RECORDS];
 void hp_dinv_record_forget(level_type *L) { int q; for (q = 0; q < DINV_RECORDS; q++) if (dinv_recorded[q] == L) dinv_recorded[q] = NULL; }
 void hp_dinv_record_clear(level_type *L) {
   hpgmg_level_ext *X = hpgmg_level_ext_get(L);
-  if (X->backend) ((backend_t *)X->backend)->dinv_rebuilt = 0;
+  if (X->backend) { ((backend_t *)X->backend)->dinv_rebuilt = 0; ((backend_t *)X->backend)->alpha_uniform = 0; }
   hp_dinv_record_forget(L);
 }
 void hp_dinv_record_set(level_type *L, double a, double b, double h2inv) {
@@ -66,6 +66,25 @@ void hpgmg_set_pair_form_dinv(int on) { hp_switch_set(SW_PAIR_FORM_DINV, on ? 1 
 long long hpgmg_pair_formed_dinv_launches(void) { hp_lazy_flush(); return hpgmg_hip_pair_formed_dinv_launches(); }
 static int dinv_formable(const backend_t *B, double a, double b, double h2inv) {
   return hp_switch(SW_PAIR_FORM_DINV) && B->dinv_rebuilt && memcmp(&a, &B->dinv_a, sizeof a) == 0 && memcmp(&b, &B->dinv_b, sizeof b) == 0 && memcmp(&h2inv, &B->dinv_h2inv, sizeof h2inv) == 0;
+}
+
+/* ---- the record "alpha is one bit pattern" (plugin_internal.h: backend_t.alpha_uniform).  It lives inside the Dinv record's lifetime: made only where that record was just
+ * set, gone with it.  One rank for now: the decision would be safe per rank, but no multi-rank instance takes it. */
+void hpgmg_set_uniform_alpha(int on) { hp_switch_set(SW_UNIFORM_ALPHA, on ? 1 : 0); }
+long long hpgmg_uniform_alpha_launches(void) { hp_lazy_flush(); return hpgmg_hip_pair_uniform_alpha_launches() + hpgmg_hip_stencil_uniform_alpha_launches(); }
+void hp_alpha_record_check(level_type *L) {
+  backend_t *B = hp_backend_of(L);
+  int uniform = 0; double value = 0.0;
+  B->alpha_uniform = 0;
+  if (!B->dinv_rebuilt || !B->all_faces_local || L->num_my_boxes < 1) return;      /* a level that got no Dinv record gets none */
+  BLAS1(hpgmg_hip_vector_uniform(&B->dev, VECTOR_ALPHA, &uniform, &value));
+  B->alpha_uniform = uniform; B->alpha_value = value;
+}
+static int alpha_uniform_usable(const backend_t *B) { return hp_switch(SW_UNIFORM_ALPHA) && B->dinv_rebuilt && B->alpha_uniform && B->all_faces_local; }
+int hp_alpha_uniform_arm_residual(const backend_t *B) {
+  if (!alpha_uniform_usable(B) || hp_variant() != HPGMG_HIP_7PT_VC_HELMHOLTZ) return 0;
+  hpgmg_hip_stencil_uniform_alpha(B->alpha_value);
+  return 1;
 }
 
 static long long pair_remote_smooths = 0, fp32_pair_smooths = 0;
@@ -134,6 +153,7 @@ static int pair_issue(const pair_launch *p) {
   backend_t *B = p->B;
   const int v = hp_variant(), form_dinv = dinv_formable(B, p->a, p->b, p->h2inv);
   if (p->fold_Lc) hpgmg_hip_pair_fold_interpolation(p->fold_Lc, p->fold_id, 1.0);
+  if (form_dinv && !p->gsrb && alpha_uniform_usable(B)) hpgmg_hip_pair_uniform_alpha(B->alpha_value);      /* one-shot like the others: made again before each part */
   if (p->gsrb) return hpgmg_hip_smooth_gsrb_pair(&B->dev, v, (double *const *)B->d_pair_base, NULL, p->x0.scr, p->x0.id, p->edge, p->out2.scr, p->out2.id, p->rhs_id, p->a, p->b, p->h2inv, p->sweep, form_dinv);
   return hpgmg_hip_smooth_cheby_pair(&B->dev, v, (double *const *)B->d_pair_base, p->c32, p->x0.scr, p->x0.id, p->xm1.scr, p->xm1.id, p->out1.scr, p->out1.id, p->out2.scr, p->out2.id,
                                      p->rhs_id, p->a, p->b, p->h2inv, p->c1a, p->c2a, p->c1b, p->c2b, form_dinv);

@@ -167,4 +167,5 @@ void rebuild_operator(level_type *L, level_type *from, double a, double b) {
   exchange_boundary(L, VECTOR_DINV, STENCIL_SHAPE_BOX);
   if (cfg.helmholtz) exchange_boundary(L, VECTOR_L1INV, STENCIL_SHAPE_BOX);
   hp_dinv_record_set(L, a, b, 1.0 / (L->h * L->h));      /* from here until the next write into a coefficient vector, VECTOR_DINV is a function of the others */
+  if (cfg.helmholtz) hp_alpha_record_check(L);            /* ... and alpha, if it is one bit pattern now, stays that pattern */
 }

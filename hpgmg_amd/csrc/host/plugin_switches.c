@@ -42,6 +42,7 @@ static struct { const char *env; int kind; long long dflt; const char *what; lon
   [SW_BRICK_WIDE_TAIL_DIM] = { "HPGMG_TUNE_BRICK_WIDE_TAIL", K_INT, 1, "27-pt / fv4: the largest one-box level left to the single-workgroup tail (1: the 8^3, 4^3 (and 27-pt: 2^3) levels are visited as ONE brick each and only the bottom solve is left; 2 / 4 / 8: the tail starts there)" },
   [SW_FTAIL_MAX_DIM]    = { "HPGMG_TUNE_FTAIL_MAX", K_INT, 8, "7-pt: the largest level (cells per side) the single-launch F-cycle tail starts from (8: the 16^3 step of the climb is a brick launch each way, eight CUs instead of one: config 1 0.320 vs 0.328 ms with 16, config 2 the same within noise; profiles/r06i_ab_ftail.txt)" },
   [SW_PAIR_FORM_DINV]    = { "HPGMG_PAIR_FORM_DINV", K_ON, 1, "7-pt sweep pairs (fp64 streams, one rank, variable coefficients, 10 / 12 waves): Dinv is formed in registers from the coefficient streams instead of read, where VECTOR_DINV is known to be rebuild_operator's output for the same a, b; 0: always read" },
+  [SW_UNIFORM_ALPHA]     = { "HPGMG_UNIFORM_ALPHA", K_ON, 1, "7-pt Helmholtz, one rank: where rebuild_operator found alpha to be one bit pattern over the level's interior, the sweep pairs that form Dinv and the wide fused residual passes take it from their arguments instead of streaming VECTOR_ALPHA; 0: always read" },
   [SW_SMOOTHER_PRECISION]= { "HPGMG_SMOOTHER_PRECISION", K_INT, 64, "32: fp32 coefficient streams in the Chebyshev sweep pairs (BASELINE config 5: within 2e-4 of the fp64 norms, and bit-exact against the CPU oracle's fp32 mode, which rounds the same coefficients); 64: bit-exact" },
 };
 

@@ -275,6 +275,20 @@ __global__ __launch_bounds__(64) void ordered_sum_kernel(const double *partials,
   if (lane == 0) publish(result, s, seq);
 }
 
+// ---- hpgmg_hip_vector_uniform: one lane per interior cell compares the cell's BITS with those of the first interior cell of box 0 and raises *differs (every writer
+// stores the same 1: an ordinary store) where they are not the same; that first cell goes to *first
+__global__ __launch_bounds__(256) void vector_uniform_kernel(const hpgmg_hip_level L, int id, int *differs, double *first) {
+  RowIter r;
+  const int row = blockIdx.x * kRowsPerBlock + threadIdx.x / 64, lane = threadIdx.x % 64;
+  const unsigned long long want = *reinterpret_cast<const unsigned long long *>(vec_origin(L, 0, id));
+  if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<unsigned long long *>(first) = want;
+  if (!row_of(row, L.dim, L.num_boxes, r)) return;
+  const unsigned long long *v = reinterpret_cast<const unsigned long long *>(vec_origin(L, r.box, id) + r.j * L.jStride + r.k * L.kStride);
+  bool same = true;
+  for (int i = lane; i < L.dim; i += 64) same = same && (v[i] == want);
+  if (!same) *differs = 1;
+}
+
 // ---- operators.7pt.c:158-227 --------------------------------------------------------------
 struct RebuildArgs { int variable_coeff, alpha_id, l1inv_id; double a, b, h2inv; };
 __global__ __launch_bounds__(256) void rebuild7_kernel(const hpgmg_hip_level L, const RebuildArgs A, double *partials) {
@@ -502,6 +516,23 @@ int hpgmg_hip_rebuild_7pt(const hpgmg_hip_level *L, int variable_coeff, int alph
   hipLaunchKernelGGL(rebuild7_kernel, dim3(nblk), dim3(256), 0, g_stream, *L, A, partials);
   HPGMG_LAUNCH_CHECK("rebuild_7pt");
   return max_of_partials(nblk, -1e9, lambda_max_out);
+}
+
+// Is vector `id` ONE bit pattern over the interior cells of every box of the level?  An integer compare against the first interior cell of box 0: -0.0 is not 0.0, a NaN is its
+// bits.  Ghost cells are not looked at.  *uniform_out 1 / 0, *value_out that first cell as stored.  Synchronous; once per operator rebuild (plugin_problem.c).
+int hpgmg_hip_vector_uniform(const hpgmg_hip_level *L, int id, int *uniform_out, double *value_out) {
+  *uniform_out = 0; *value_out = 0.0;
+  if (int e = hpgmg_hip_graph_flush()) return e;
+  if (L->num_boxes <= 0) return 0;
+  int *differs, status = 0;
+  double *first = reduction_scratch(1);
+  if (!first) return record_error(hipErrorOutOfMemory, "vector_uniform: no scratch");
+  if (int e = status_begin(&differs)) return e;
+  hipLaunchKernelGGL(vector_uniform_kernel, dim3(rows_grid(L->num_boxes * L->dim * L->dim)), dim3(256), 0, g_stream, *L, id, differs, first);
+  HPGMG_CHECK(hipMemcpyAsync(value_out, first, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+  if (int e = status_end("vector_uniform_kernel", &status)) return e;
+  *uniform_out = status ? 0 : 1;
+  return 0;
 }
 
 }  // extern "C"

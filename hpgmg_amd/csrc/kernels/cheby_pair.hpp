@@ -63,6 +63,9 @@ struct PairArgs {
   double *edge_coef;
   // REMOTE, two-part launches (the halo exchange runs on another stream under part 1): dispatch slot -> workgroup, padded with total_blocks (null: identity)
   const int *order;
+  // UA instances (cheby_pair_kernel<..., UA = true>): alpha has this one bit pattern in every interior cell of the rank's boxes -- read from the data when the operator was
+  // rebuilt (hpgmg_hip_vector_uniform), never assumed -- and the main waves take it from here instead of streaming VECTOR_ALPHA.  Set by the launcher with the UA twin only.
+  double alpha_uniform;
 };
 
 __device__ __forceinline__ double *pair_vec(const hpgmg_hip_level &L, const PairArgs &A, VecRef r, int box) {
@@ -247,7 +250,7 @@ __device__ __forceinline__ void pair_edge_wave(const hpgmg_hip_level &L, const P
 // EDGEW: the workgroup has NW + 1 waves, launched with dim3(64, NW + 1); the last one is the edge wave above, the others run the march unchanged but for lanes 0 / 63,
 // which take their two neighbours across a tile edge from LDS.  Such a launch has no pre-pass.  10 waves, Chebyshev, fp64 variable coefficients, whole-row boxes, one rank:
 // 11 waves are three per SIMD -- the register budget the 10-wave instances live under already; a 13th wave would put four on one SIMD.
-template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP, bool REMOTE = false, bool FORM = false, bool EDGEW = false>
+template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP, bool REMOTE = false, bool FORM = false, bool EDGEW = false, bool UA = false>
 __global__ __launch_bounds__(64 * (NW + (EDGEW ? 1 : 0))) void cheby_pair_kernel(const hpgmg_hip_level L_in, const PairArgs A_in) {
   static_assert(!(REMOTE && C32) && !(REMOTE && NARROW && INTERP), "the multi-rank variant is built for fp64 coefficients; with narrow boxes the interpolation is not folded in");
   // REMOTE + INTERP: the parent is added to the cells of the brick only -- what arrives in ghost zones and deep planes was packed by its owner with ITS parents already added (pair_halo_kernel)
@@ -258,6 +261,9 @@ __global__ __launch_bounds__(64 * (NW + (EDGEW ? 1 : 0))) void cheby_pair_kernel
   // 2 % slower than before whichever way it pointed.  fp64 coefficient streams of one rank; not the 16-wave instances: held to 128 registers
   // they spill 7 as they are and 27 with the division.
   static_assert(!FORM || (kVC && !C32 && !REMOTE && NW != 16), "no FORM instance of this kind");
+  // UA: alpha is one value on the whole rank (PairArgs.alpha_uniform): the main waves do not read VECTOR_ALPHA -- the same operand bits from a kernel argument, one stream fewer.
+  // A template parameter for the reason FORM is one.  Twins of the FORM instances of the Chebyshev Helmholtz pairs only; the edge wave keeps its packed line (64 bytes either way).
+  static_assert(!UA || (FORM && kHelm && SM == PAIR_CHEBY), "no UA instance of this kind");
   static_assert(!EDGEW || (SM == PAIR_CHEBY && kVC && !C32 && !NARROW && !REMOTE && NW == 10), "no EDGEW instance of this kind");
   extern __shared__ p2 pair_lds[];                              // 3 x [2 buffers][NW rows][64 pairs] = NW x 6 KiB
   p2 (*slabX0)[NW][64] = reinterpret_cast<p2 (*)[NW][64]>(pair_lds);
@@ -390,6 +396,7 @@ __global__ __launch_bounds__(64 * (NW + (EDGEW ? 1 : 0))) void cheby_pair_kernel
   p2 far_c = {0, 0}, far_n = {0, 0};                            // far x0 row on planes p, p+1 (halo waves)
   p2 bj_c = {0, 0}, bj_n = {0, 0};                              // own beta_j row on planes p, p+1
   PlaneCoef<V> qc = {}, qp = {};                                // coefficients of planes p and p-1
+  if (UA) qc.al = p2{A.alpha_uniform, A.alpha_uniform};         // (qp takes it with every  qp = qc)
 
   // ---- prologue: planes pstart-1 and pstart of x0, beta_j of pstart, into registers / LDS
   const int pstart = in_dom(P0) ? P0 : P0 + 1;
@@ -439,7 +446,7 @@ __global__ __launch_bounds__(64 * (NW + (EDGEW ? 1 : 0))) void cheby_pair_kernel
       };
       if (!FORM) load_ahead();
       if (!FORM) qc.dinv = CoefStream<C32>(L, A, box, VECTOR_DINV, C32_DINV, sh).pair(off);
-      if (kHelm) qc.al = CoefStream<C32>(L, A, box, VECTOR_ALPHA, C32_ALPHA, sh).pair(off);
+      if (kHelm && !UA) qc.al = CoefStream<C32>(L, A, box, VECTOR_ALPHA, C32_ALPHA, sh).pair(off);
       if (kVC) {
         const CoefStream<C32> bis(L, A, box, VECTOR_BETA_I, C32_BETA_I, sh), bks(L, A, box, VECTOR_BETA_K, C32_BETA_K, sh);
         qc.bi = bis.pair(off);
@@ -602,7 +609,7 @@ __global__ __launch_bounds__(64 * (NW + (EDGEW ? 1 : 0))) void cheby_pair_kernel
           };
           if (!FORM) load_ahead();
           if (!FORM) qc.dinv = s_dinv.pair(ek);
-          if (kHelm) qc.al = s_al.pair(ek);
+          if (kHelm && !UA) qc.al = s_al.pair(ek);
           if (kVC) {
             qc.bi = s_bi.pair(ek);
             qc.bir = __shfl_down(qc.bi.x, 1, 64);

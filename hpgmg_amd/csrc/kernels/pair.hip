@@ -47,16 +47,18 @@ double *g_exp_timeline = nullptr;     // experiment build: where a kernel's chos
 }  // namespace hpgmg
 using namespace hpgmg;
 
-// one launch of the instance <V, NW, C32, SM, NARROW, INTERP> on one rank -- its FORM twin where A.form_dinv asks for it (smooth_pair sets that only where the twin exists)
-template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP, bool FORM>
+// one launch of the instance <V, NW, C32, SM, NARROW, INTERP> on one rank -- its FORM twin where A.form_dinv asks for it (smooth_pair sets that only where the twin exists),
+// and of that the UA twin (alpha from PairArgs.alpha_uniform, cheby_pair.hpp) where ua says so: Chebyshev, Helmholtz (smooth_pair: only with form_dinv)
+template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP, bool FORM, bool UA = false>
 static int pair_launch_instance(int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A) {
   static bool once = false;
-  if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)cheby_pair_kernel<V, NW, C32, SM, NARROW, INTERP, false, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NW * 6 * 64 * sizeof(p2)))); once = true; }
-  hipLaunchKernelGGL((cheby_pair_kernel<V, NW, C32, SM, NARROW, INTERP, false, FORM>), dim3(grid), dim3(64, NW), lds, g_stream, *L, A);
+  if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)cheby_pair_kernel<V, NW, C32, SM, NARROW, INTERP, false, FORM, false, UA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NW * 6 * 64 * sizeof(p2)))); once = true; }
+  hipLaunchKernelGGL((cheby_pair_kernel<V, NW, C32, SM, NARROW, INTERP, false, FORM, false, UA>), dim3(grid), dim3(64, NW), lds, g_stream, *L, A);
   return 0;
 }
 template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP>
-static int pair_launch(int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A) {
+static int pair_launch(int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A, bool ua) {
+  if constexpr (V == HPGMG_HIP_7PT_VC_HELMHOLTZ && SM == PAIR_CHEBY && !C32 && NW != 16) { if (A.form_dinv && ua) return pair_launch_instance<V, NW, C32, SM, NARROW, INTERP, true, true>(grid, lds, L, A); }
   if constexpr (V != HPGMG_HIP_7PT_CC && !C32 && NW != 16) { if (A.form_dinv) return pair_launch_instance<V, NW, C32, SM, NARROW, INTERP, true>(grid, lds, L, A); }
   return pair_launch_instance<V, NW, C32, SM, NARROW, INTERP, false>(grid, lds, L, A);
 }
@@ -64,21 +66,22 @@ static int pair_launch(int grid, size_t lds, const hpgmg_hip_level *L, const Pai
 // The EDGEW twin of a 10-wave Chebyshev instance (cheby_pair.hpp: an eleventh wave forms x1 on the tile-edge columns, no pre-pass): taken where it exists and applies --
 // fp64 variable coefficients, one rank, boxes of whole rows, an interior tile edge, the packed coefficient values at hand.  *taken false: the caller launches the pre-pass and the plain instance.
 static long long g_pair_edge_wave_launches = 0;
-template <int V, int SM, bool C32, bool INTERP, bool FORM>
+template <int V, int SM, bool C32, bool INTERP, bool FORM, bool UA = false>
 static int pair_launch_edge_wave_instance(int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A) {
   constexpr int NW = 10;
   static bool once = false;
-  if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)cheby_pair_kernel<V, NW, C32, SM, false, INTERP, false, FORM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; }
-  hipLaunchKernelGGL((cheby_pair_kernel<V, NW, C32, SM, false, INTERP, false, FORM, true>), dim3(grid), dim3(64, NW + 1), lds, g_stream, *L, A);
+  if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)cheby_pair_kernel<V, NW, C32, SM, false, INTERP, false, FORM, true, UA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; }
+  hipLaunchKernelGGL((cheby_pair_kernel<V, NW, C32, SM, false, INTERP, false, FORM, true, UA>), dim3(grid), dim3(64, NW + 1), lds, g_stream, *L, A);
   return 0;
 }
 template <int V, int SM, bool C32, bool INTERP>
-static int pair_launch_edge_wave(int nw, int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A, bool *taken) {
+static int pair_launch_edge_wave(int nw, int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A, bool ua, bool *taken) {
   *taken = false;
   if constexpr (V != HPGMG_HIP_7PT_CC && SM == PAIR_CHEBY && !C32) {
     if (nw != 10 || L->dim % 128 != 0 || A.tiles_i < 2 || !A.edge_coef) return 0;
     *taken = true;
     g_pair_edge_wave_launches++;
+    if constexpr (V == HPGMG_HIP_7PT_VC_HELMHOLTZ) { if (A.form_dinv && ua) return pair_launch_edge_wave_instance<V, SM, C32, INTERP, true, true>(grid, lds, L, A); }
     if (A.form_dinv) return pair_launch_edge_wave_instance<V, SM, C32, INTERP, true>(grid, lds, L, A);
     return pair_launch_edge_wave_instance<V, SM, C32, INTERP, false>(grid, lds, L, A);
   }
@@ -118,8 +121,10 @@ int hpgmg_hip_coef32_refresh(const hpgmg_hip_level *L, float *const *c32_base, i
 static bool g_pair_halo_set = false;
 static int g_pair_rem[6], g_pair_brick[3];
 static const double *g_pair_deep = nullptr, *g_pair_deep_beta = nullptr;
-static long long g_pair_launches = 0, g_pair_remote_launches = 0, g_pair_formed_launches = 0;
+static long long g_pair_launches = 0, g_pair_remote_launches = 0, g_pair_formed_launches = 0, g_pair_ua_launches = 0;
 static int g_pair_discard_x1 = 0;     // consumed by the next Chebyshev pair launch: its out1 vector is scratch, do not store x1
+static int g_pair_ua_set = 0;         // consumed by the next pair launch (hpgmg_hip_pair_uniform_alpha): alpha is g_pair_ua_value in every interior cell of the level
+static double g_pair_ua_value = 0.0;
 static const hpgmg_hip_level *g_pair_interp_level = nullptr;
 static int g_pair_interp_id = 0;
 static double g_pair_interp_prescale = 1.0;
@@ -180,7 +185,8 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
   const bool remote = g_pair_halo_set;
   const int discard_x1 = g_pair_discard_x1;
   const hpgmg_hip_level *const interp_level = g_pair_interp_level;
-  g_pair_halo_set = false; g_pair_discard_x1 = 0; g_pair_interp_level = nullptr;
+  const int ua_asked = g_pair_ua_set;
+  g_pair_halo_set = false; g_pair_discard_x1 = 0; g_pair_interp_level = nullptr; g_pair_ua_set = 0;
   HPGMG_SKIP_IF_REPLAY();
   const int Di = remote ? g_pair_brick[0] * L->dim : L->dim_i, Dj = remote ? g_pair_brick[1] * L->dim : L->dim_j, Dk = remote ? g_pair_brick[2] * L->dim : L->dim_k;
   if (!pair_supported_dims(L, variant, Di, Dj, Dk)) return record_error(hipErrorInvalidValue, "smooth_cheby_pair: level not supported");
@@ -223,6 +229,9 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
   // dinv_is_rebuilt: the caller vouches that VECTOR_DINV is what rebuild7_kernel made of the current coefficient vectors with these a, b, h2inv; the instances that
   // can (cheby_pair.hpp: the FORM instances -- fp64 coefficient streams, one rank, variable coefficients, 10 or 12 waves) then form it instead of reading it
   A.form_dinv = (dinv_is_rebuilt && !remote && !c32_base && variant != HPGMG_HIP_7PT_CC && nw != 16) ? 1 : 0;
+  // the caller vouches that alpha is g_pair_ua_value in every interior cell: the UA twin of a FORM instance, where there is one (Chebyshev, Helmholtz), takes it from the arguments
+  const bool ua = (ua_asked && A.form_dinv && !gsrb && variant == HPGMG_HIP_7PT_VC_HELMHOLTZ);
+  if (ua) A.alpha_uniform = g_pair_ua_value;
   const bool interp = (interp_level != nullptr);
   if (interp) {
     const hpgmg_hip_level *C = interp_level;
@@ -267,7 +276,7 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
   // (the waves per workgroup are a template parameter of the kernel: one instance per candidate)
 #define PAIR_NW_SWITCH(...) switch (nw) { case 10: { constexpr int NWC = 10; __VA_ARGS__ } break; case 12: { constexpr int NWC = 12; __VA_ARGS__ } break; default: { constexpr int NWC = 16; __VA_ARGS__ } break; }
 #define PAIR_LAUNCH2(VAR, C32, SM, NARROW, INTERP) PAIR_NW_SWITCH( \
-      { const int e_ = pair_launch<VAR, NWC, C32, SM, NARROW, INTERP>(grid, lds, L, A); if (e_) return e_; } )
+      { const int e_ = pair_launch<VAR, NWC, C32, SM, NARROW, INTERP>(grid, lds, L, A, ua); if (e_) return e_; } )
 #define PAIR_LAUNCH_REMOTE_IP(VAR, SM, NRW, IP) { \
       const int ecols = 2 * (A.tiles_i - 1) + (A.rem[0] ? 1 : 0) + (A.rem[1] ? 1 : 0); \
       A.edge_blocks = ((A.Dj + 63) / 64) * A.Dk * ecols; const int egrid_r = grid_for(A.edge_blocks, &A.edge_per_xcd); \
@@ -280,12 +289,12 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
       A.edge_blocks = ((A.Dj + 63) / 64) * A.Dk * 2 * (A.tiles_i - 1); const dim3 egrid(A.edge_blocks > 0 ? grid_for(A.edge_blocks, &A.edge_per_xcd) : 1); \
       if (remote) PAIR_LAUNCH_REMOTE(VAR, SM) \
       else if (interp) { \
-        bool ew_; { const int e_ = pair_launch_edge_wave<VAR, SM, C32, true>(nw, grid, lds, L, A, &ew_); if (e_) return e_; } \
+        bool ew_; { const int e_ = pair_launch_edge_wave<VAR, SM, C32, true>(nw, grid, lds, L, A, ua, &ew_); if (e_) return e_; } \
         if (!ew_) { \
         if (A.tiles_i > 1) hipLaunchKernelGGL((cheby_pair_edge_kernel<VAR, C32, SM, true>), egrid, dim3(64), 0, g_stream, *L, A); \
         if (L->dim % 128 == 0) PAIR_LAUNCH2(VAR, C32, SM, false, true) else PAIR_LAUNCH2(VAR, C32, SM, true, true) } \
       } else { \
-        bool ew_; { const int e_ = pair_launch_edge_wave<VAR, SM, C32, false>(nw, grid, lds, L, A, &ew_); if (e_) return e_; } \
+        bool ew_; { const int e_ = pair_launch_edge_wave<VAR, SM, C32, false>(nw, grid, lds, L, A, ua, &ew_); if (e_) return e_; } \
         if (!ew_) { \
         if (A.tiles_i > 1) hipLaunchKernelGGL((cheby_pair_edge_kernel<VAR, C32, SM, false>), egrid, dim3(64), 0, g_stream, *L, A); \
         if (L->dim % 128 == 0) PAIR_LAUNCH2(VAR, C32, SM, false, false) else PAIR_LAUNCH2(VAR, C32, SM, true, false) } \
@@ -305,7 +314,7 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
 #undef PAIR_NW_SWITCH
 #undef PAIR_LAUNCH_REMOTE
 #undef PAIR_LAUNCH_REMOTE_IP
-  if (part != 1) { g_pair_launches++; if (remote) g_pair_remote_launches++; if (A.form_dinv) g_pair_formed_launches++; }      // the two parts of a launch count once (part 2 is never empty: it holds the workgroups at the remote faces)
+  if (part != 1) { g_pair_launches++; if (remote) g_pair_remote_launches++; if (A.form_dinv) g_pair_formed_launches++; if (ua) g_pair_ua_launches++; }      // the two parts of a launch count once (part 2 is never empty: it holds the workgroups at the remote faces)
   profile_end(prof, 2 * cells, part == 1);           // one launch = two sweeps over every cell
   HPGMG_LAUNCH_CHECK("cheby_pair_kernel");
   return 0;
@@ -324,6 +333,9 @@ void hpgmg_hip_pair_set_halo(const int brick_boxes[3], const int remote_face[6],
   g_pair_deep = deep; g_pair_deep_beta = deep_beta; g_pair_halo_set = true;
 }
 void hpgmg_hip_pair_discard_x1(void) { g_pair_discard_x1 = 1; }
+// the NEXT sweep-pair launch (consumed by it, launched or not) may take alpha = value, the one bit pattern of every interior cell of the level, from its arguments
+void hpgmg_hip_pair_uniform_alpha(double value) { g_pair_ua_set = 1; g_pair_ua_value = value; }
+long long hpgmg_hip_pair_uniform_alpha_launches(void) { return g_pair_ua_launches; }
 #ifdef HPGMG_EXP_TIMELINE
 void hpgmg_hip_exp_timeline(void *buf) { g_exp_timeline = (double *)buf; }
 #endif

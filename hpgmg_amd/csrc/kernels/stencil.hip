@@ -192,8 +192,10 @@ struct alignas(16) d2 { double x, y; };
 __device__ __forceinline__ d2 ld2(const double *p) { return *reinterpret_cast<const d2 *>(p); }
 __device__ __forceinline__ void st2(double *p, d2 v) { *reinterpret_cast<d2 *>(p) = v; }
 
-template <int V, int MODE, int WJ>
+// UA (the two fused residual forms of the Helmholtz operator): alpha is the one value F.alpha_uniform in every interior cell of the level, and is not read.
+template <int V, int MODE, int WJ, bool UA = false>
 __global__ __launch_bounds__(64 * WJ) void stencil7_wide_kernel(const hpgmg_hip_level L, const StencilArgs P, const FusedArgs F) {
+  static_assert(!UA || (V == HPGMG_HIP_7PT_VC_HELMHOLTZ && (MODE == MODE_RESIDUAL_RESTRICT || MODE == MODE_RESIDUAL_NORM)), "no UA instance of this kind");
   __shared__ d2 slab[2][2 * WJ][64];                          // plane copy: [buffer][row of the slab][i pair]
   __shared__ double wg_max[WJ];
   // zero_vector(coarse, zero_id) -- whole padded boxes, ghosts included -- by the workgroups appended after the stencil grid (physical
@@ -230,7 +232,7 @@ __global__ __launch_bounds__(64 * WJ) void stencil7_wide_kernel(const hpgmg_hip_
   double *out = ((kRestrict && !F.store_res) || (kNorm && F.no_store)) ? nullptr : vec_origin(L, box, P.xout_id);
   const double *__restrict__ rhs = (MODE == MODE_APPLY) ? nullptr : vec_origin(L, box, P.rhs_id);
   const double *__restrict__ dinv = kSmooth ? vec_origin(L, box, VECTOR_DINV) : nullptr;
-  const double *__restrict__ alpha = kHelm ? vec_origin(L, box, VECTOR_ALPHA) : nullptr;
+  const double *__restrict__ alpha = (kHelm && !UA) ? vec_origin(L, box, VECTOR_ALPHA) : nullptr;
   const double *__restrict__ beta_i = kVC ? vec_origin(L, box, VECTOR_BETA_I) : nullptr;
   const double *__restrict__ beta_j = kVC ? vec_origin(L, box, VECTOR_BETA_J) : nullptr;
   const double *__restrict__ beta_k = kVC ? vec_origin(L, box, VECTOR_BETA_K) : nullptr;
@@ -312,7 +314,7 @@ __global__ __launch_bounds__(64 * WJ) void stencil7_wide_kernel(const hpgmg_hip_
       const int dm = defer_plane ? 3 : DM;                                                                                   \
       d2 bi = {0, 0}, al = {0, 0}; double bir = 0;                                                                           \
       if (kVC) { bi = ld2(beta_i + IDX); bir = __shfl_down(bi.x, 1, 64); if (lane == 63) bir = beta_i[IDX + 2]; }            \
-      if (kHelm) al = ld2(alpha + IDX);                                                                                     \
+      if (kHelm) { if (UA) al = d2{F.alpha_uniform, F.alpha_uniform}; else al = ld2(alpha + IDX); }                         \
       if (MODE == MODE_GSRB) {                                                                                              \
         const int pp = (JROW ^ k ^ colour000) & 1;              /* the cell of this pair whose colour is swept */           \
         const double c = pp ? XC.y : XC.x;                                                                                  \
@@ -917,8 +919,10 @@ static int wide_fused_ok(const hpgmg_hip_level *L, int variant) {
   if (variant != HPGMG_HIP_7PT_VC_HELMHOLTZ && variant != HPGMG_HIP_7PT_VC_POISSON && variant != HPGMG_HIP_7PT_CC) return 0;
   return L->num_boxes > 0 && g_ghost_free && L->box_nbr && !g_defer_mode && L->dim % 128 == 0 && L->jStride % 2 == 0 && L->kStride % 2 == 0 && L->volume % 2 == 0 && (L->flags & 1);
 }
+// ua: the caller vouched (hpgmg_hip_stencil_uniform_alpha) that alpha is F.alpha_uniform in every interior cell: the Helmholtz pass takes its UA twin
+static long long g_wide_ua_launches = 0;
 template <int MODE>
-static int launch_wide_fused(const hpgmg_hip_level *L, int variant, StencilArgs P, FusedArgs F, int extra_blocks) {
+static int launch_wide_fused(const hpgmg_hip_level *L, int variant, StencilArgs P, FusedArgs F, int extra_blocks, bool ua) {
   constexpr int wj = 8;
   P.ghost_free = 1;
   P.tiles_i = L->dim / 128; P.tiles_j = L->dim / (2 * wj); P.kchunk = 16; P.chunks_k = (L->dim + 15) / 16;
@@ -934,7 +938,10 @@ static int launch_wide_fused(const hpgmg_hip_level *L, int variant, StencilArgs 
   }
   grid += extra_blocks;                                                      // the extra (zeroing) workgroups follow the stencil grid
   switch (variant) {
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ: hipLaunchKernelGGL((stencil7_wide_kernel<HPGMG_HIP_7PT_VC_HELMHOLTZ, MODE, wj>), dim3(grid), dim3(64, wj), 0, g_stream, *L, P, F); break;
+    case HPGMG_HIP_7PT_VC_HELMHOLTZ:
+      if (ua) { hipLaunchKernelGGL((stencil7_wide_kernel<HPGMG_HIP_7PT_VC_HELMHOLTZ, MODE, wj, true>), dim3(grid), dim3(64, wj), 0, g_stream, *L, P, F); if (g_tile_part != 1) g_wide_ua_launches++; }
+      else hipLaunchKernelGGL((stencil7_wide_kernel<HPGMG_HIP_7PT_VC_HELMHOLTZ, MODE, wj>), dim3(grid), dim3(64, wj), 0, g_stream, *L, P, F);
+      break;
     case HPGMG_HIP_7PT_VC_POISSON:   hipLaunchKernelGGL((stencil7_wide_kernel<HPGMG_HIP_7PT_VC_POISSON, MODE, wj>), dim3(grid), dim3(64, wj), 0, g_stream, *L, P, F); break;
     default:                         hipLaunchKernelGGL((stencil7_wide_kernel<HPGMG_HIP_7PT_CC, MODE, wj>), dim3(grid), dim3(64, wj), 0, g_stream, *L, P, F); break;
   }
@@ -1080,6 +1087,12 @@ int hpgmg_hip_residual_fused_supported(const hpgmg_hip_level *L, int variant) {
 int hpgmg_hip_residual_restrict_supported(const hpgmg_hip_level *L, int variant) {
   return hpgmg_hip_residual_fused_supported(L, variant) || (!tiled_variant(variant) && small_fused_ok(L, variant));
 }
+// The NEXT fused residual launch (hpgmg_hip_residual_restrict / _restrict_store / _norm; consumed by it, launched or not) may take alpha = value, the one bit pattern of every
+// interior cell of the level, from its arguments: the wide Helmholtz pass then runs its UA twin.  Every other form of the launch ignores the request.
+static int g_wide_ua_set = 0;
+static double g_wide_ua_value = 0.0;
+void hpgmg_hip_stencil_uniform_alpha(double value) { g_wide_ua_set = 1; g_wide_ua_value = value; }
+long long hpgmg_hip_stencil_uniform_alpha_launches(void) { return g_wide_ua_launches; }
 // residual (never stored) -> restriction into vector coarse_id of Lc, plus zero_vector(Lc, zero_id) when zero_id >= 0: the end of
 // MGVCycle's down leg (mg.c:1150-1153) in one pass over the fine level.  map[4 b .. 4 b + 3] = coarse box and coarse (i, j, k) under fine box b's first cell.
 int hpgmg_hip_residual_restrict_store(const hpgmg_hip_level *L, int variant, int res_id, int x_id, int rhs_id, double a, double b, double h2inv,
@@ -1091,6 +1104,8 @@ int hpgmg_hip_residual_restrict(const hpgmg_hip_level *L, int variant, int x_id,
 // res_id >= 0 (7-point only): the residual is stored as residual() would store it as well
 int hpgmg_hip_residual_restrict_store(const hpgmg_hip_level *L, int variant, int res_id, int x_id, int rhs_id, double a, double b, double h2inv,
                                       const hpgmg_hip_level *Lc, int coarse_id, const int *map, int zero_id) {
+  const bool ua = (g_wide_ua_set != 0 && variant == HPGMG_HIP_7PT_VC_HELMHOLTZ);
+  g_wide_ua_set = 0;
   HPGMG_SKIP_IF_REPLAY();
   if (tiled_variant(variant)) {
     if (!hpgmg_hip_residual_fused_supported(L, variant) || Lc->num_boxes <= 0 || res_id >= 0) return record_error(hipErrorInvalidValue, "residual_restrict: level not supported");
@@ -1104,11 +1119,14 @@ int hpgmg_hip_residual_restrict_store(const hpgmg_hip_level *L, int variant, int
   StencilArgs P = {}; P.xn_id = x_id; P.xout_id = (res_id >= 0) ? res_id : x_id; P.rhs_id = rhs_id; P.a = a; P.b = b; P.h2inv = h2inv;
   FusedArgs F = {}; F.Lc = *Lc; F.coarse_id = coarse_id; F.zero_id = zero_id; F.map = map; F.store_res = (res_id >= 0);
   F.zero_chunks_per_box = (Lc->volume + 4095) / 4096;
+  if (ua) F.alpha_uniform = g_wide_ua_value;
   if (!wide_fused_ok(L, variant)) return launch_small_fused(L, variant, P, F, zero_id >= 0 ? F.zero_chunks_per_box * Lc->num_boxes : 0);
-  return launch_wide_fused<MODE_RESIDUAL_RESTRICT>(L, variant, P, F, zero_id >= 0 ? F.zero_chunks_per_box * Lc->num_boxes : 0);
+  return launch_wide_fused<MODE_RESIDUAL_RESTRICT>(L, variant, P, F, zero_id >= 0 ? F.zero_chunks_per_box * Lc->num_boxes : 0, ua);
 }
 // residual stored to res_id (not stored when res_id < 0) AND its max-abs: residual() + norm() of the convergence check (mg.c:1321-1323) in one pass
 int hpgmg_hip_residual_norm(const hpgmg_hip_level *L, int variant, int res_id, int x_id, int rhs_id, double a, double b, double h2inv, double *norm_out) {
+  const bool ua = (g_wide_ua_set != 0 && variant == HPGMG_HIP_7PT_VC_HELMHOLTZ);
+  g_wide_ua_set = 0;
   if (int e = hpgmg_hip_graph_flush()) return e;
   *norm_out = 0.0;
   if (tiled_variant(variant)) {
@@ -1127,7 +1145,8 @@ int hpgmg_hip_residual_norm(const hpgmg_hip_level *L, int variant, int res_id, i
   FusedArgs F = {}; F.partials = reduction_scratch(blocks); F.no_store = (res_id < 0);
   if (res_id < 0) P.xout_id = x_id;
   if (!F.partials) return record_error(hipErrorOutOfMemory, "residual_norm: scratch");
-  if (int e = launch_wide_fused<MODE_RESIDUAL_NORM>(L, variant, P, F, 0)) return e;
+  if (ua) F.alpha_uniform = g_wide_ua_value;
+  if (int e = launch_wide_fused<MODE_RESIDUAL_NORM>(L, variant, P, F, 0, ua)) return e;
   if (g_tile_part == 1) return 0;                 // the first part of a two-part launch: the tiles of the second part have not written their maxima yet
   return max_of_partials(blocks, 0.0, norm_out);
 }

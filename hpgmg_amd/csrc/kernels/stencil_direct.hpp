@@ -26,6 +26,7 @@ struct FusedArgs {
   double *partials;             // MODE_RESIDUAL_NORM: one max per workgroup
   int no_store;                 // MODE_RESIDUAL_NORM: the residual itself is not wanted, only its norm
   int store_res;                // MODE_RESIDUAL_RESTRICT: ALSO store the residual (to xout_id): the exact state of residual() + restriction()
+  double alpha_uniform;         // stencil7_wide_kernel, UA instances: alpha of every interior cell of the level (read from the data at the operator rebuild), which they do not read
 };
 
 struct StencilArgs {

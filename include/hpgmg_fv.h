@@ -225,6 +225,10 @@ long long   hpgmg_fp32_pair_smooths(void);     /* smooth() calls run on fp32-rou
 void        hpgmg_set_pair_form_dinv(int on);  /* 7-pt sweep pairs: 1 = form Dinv in registers from the coefficient streams where VECTOR_DINV is known to be rebuild_operator's output for the
                                                   same a, b (bit-identical; HPGMG_PAIR_FORM_DINV), 0 = always read the vector */
 long long   hpgmg_pair_formed_dinv_launches(void);     /* sweep-pair launches that formed Dinv so far (tests; a postponed smooth() is issued first) */
+void        hpgmg_set_uniform_alpha(int on);   /* 7-pt Helmholtz: 1 = where rebuild_operator found alpha to be one bit pattern over every interior cell of the level, the sweep pairs that
+                                                  form Dinv and the wide fused residual passes take it from their arguments instead of reading VECTOR_ALPHA (bit-identical;
+                                                  HPGMG_UNIFORM_ALPHA), 0 = always read the vector */
+long long   hpgmg_uniform_alpha_launches(void);        /* sweep-pair and fused residual launches that took alpha from their arguments so far (tests; postponed operators are issued first) */
 long long   hpgmg_fused_residuals_remote(void); /* 7-point: fused residual passes (residual + restriction, residual + norm) run on levels with faces owned by other ranks (tests) */
 long long   hpgmg_fv4_rb_smooths(void);        /* fv4: smooth() calls run as one-pass red + black sweeps; hpgmg_rb27_passes(): such passes of the 27-point smoother (tests) */
 long long   hpgmg_rb27_passes(void);

@@ -229,6 +229,16 @@ int hpgmg_hip_smooth_cheby_pair(const hpgmg_hip_level *L, int variant, double *c
  * same bits; one stream of ten less).  Taken by the fp64, one-rank, variable-coefficient instances of 10 and 12 waves; every other launch reads the vector as with 0. */
 long long hpgmg_hip_pair_formed_dinv_launches(void);      /* sweep-pair launches so far that formed Dinv (tests) */
 long long hpgmg_hip_pair_edge_wave_launches(void);        /* sweep-pair launches so far whose eleventh wave formed the tile-edge columns: no pre-pass (tests) */
+/* Uniform alpha.  hpgmg_hip_vector_uniform: is vector `id` one BIT pattern over the interior cells of every box (compared as integers with the first interior cell of box 0,
+ * which comes back in *value_out as stored)?  Synchronous.  A caller that knows alpha to be that value tells the NEXT sweep-pair launch (_pair_uniform_alpha) or the NEXT fused
+ * residual launch (_stencil_uniform_alpha: hpgmg_hip_residual_restrict / _restrict_store / _norm); the request is consumed by that launch whether it launches or not.  Where a UA
+ * instance exists -- the Chebyshev pairs of the Helmholtz operator that also form Dinv; the two wide fused residual passes of the Helmholtz operator -- the launch takes alpha
+ * from its arguments and does not read VECTOR_ALPHA: the same operand bits, the same results.  Every other launch ignores the request. */
+int hpgmg_hip_vector_uniform(const hpgmg_hip_level *L, int id, int *uniform_out, double *value_out);
+void hpgmg_hip_pair_uniform_alpha(double value);
+void hpgmg_hip_stencil_uniform_alpha(double value);
+long long hpgmg_hip_pair_uniform_alpha_launches(void);    /* sweep-pair launches so far that ran a UA instance (tests) */
+long long hpgmg_hip_stencil_uniform_alpha_launches(void); /* fused residual launches so far that ran a UA instance (tests) */
 /* Sweep pairs across rank boundaries (boxes over the GPUs of a node, halo exchange over RCCL).  This rank's boxes form a
  * brick of brick_boxes[0..2] boxes (numbered lexicographically inside it); remote_face[f] (f = -i,+i,-j,+j,-k,+k) is 1 where the
  * brick face belongs to another rank, 0 where it is the (Dirichlet) domain boundary.  Before the launch the caller must have

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """What a plane step of cheby_pair_kernel executes, read from the gfx950 assembly (needs the compiler, no GPU).
 
-usage: tools/pair_loop_stats.py [--asm FILE.s [--before-edgew] | --src FILE.hip] [INSTANCE ...]
-  INSTANCE: the template arguments <V,NW,C32,SM,NARROW,INTERP,REMOTE,FORM[,EDGEW]>, e.g. 0,10,false,0,false,false,false,true (EDGEW: false when left out)
-  default:  the config-2 instance of the pre-pass path, its NARROW twin, its INTERP twin and the 12-wave instance, then the EDGEW twins config 2 runs (an eleventh wave
-            forms the tile-edge columns; the loop reported is the main waves' segment step, the edge wave's own loop is the smaller one)
+usage: tools/pair_loop_stats.py [--asm FILE.s [--before-edgew | --before-ua] | --src FILE.hip] [INSTANCE ...]
+  INSTANCE: the template arguments <V,NW,C32,SM,NARROW,INTERP,REMOTE,FORM[,EDGEW[,UA]]>, e.g. 0,10,false,0,false,false,false,true (EDGEW, UA: false when left out)
+  default:  the config-2 instance of the pre-pass path, its NARROW twin, its INTERP twin and the 12-wave instance, then the EDGEW twins (an eleventh wave
+            forms the tile-edge columns; the loop reported is the main waves' segment step, the edge wave's own loop is the smaller one), then the UA twin of each
+            (alpha from the arguments: the EDGEW ones are what config 2 runs)
 Without --asm, hpgmg_amd/csrc/kernels/pair.hip (or --src) is compiled to device assembly with the flags of the Makefile.
 
 Per instance: the kernel's VGPR / SGPR counts and spill counts, and for its largest INNERMOST loop (natural loops of the control-flow graph; the one that holds no
@@ -21,16 +22,20 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT = ["0,10,false,0,false,false,false,true", "0,10,false,0,true,false,false,true", "0,10,false,0,false,true,false,true", "0,12,false,0,false,false,false,true",
            "0,10,false,0,false,false,false,true,true", "0,10,false,0,false,true,false,true,true"]
+DEFAULT = DEFAULT + [d + (",false,true" if d.count(",") == 7 else ",true") for d in DEFAULT]
 
 
 BEFORE_EDGEW = False      # --before-edgew: the assembly is of a commit whose kernel has eight template parameters
+BEFORE_UA = False         # --before-ua: ... nine (no UA)
 
 
 def mangled(inst):
     parts = [a.strip() for a in inst.split(",")]
-    assert len(parts) in (8, 9), "eight template arguments, or nine with EDGEW"
-    if len(parts) == 8 and not BEFORE_EDGEW:
-        parts.append("false")
+    assert len(parts) in (8, 9, 10), "eight template arguments, nine with EDGEW, ten with UA"
+    want = 8 if BEFORE_EDGEW else (9 if BEFORE_UA else 10)
+    if len(parts) > want:
+        return "cheby_pair_kernel_has_no_such_instance"
+    parts += ["false"] * (want - len(parts))
     enc = "".join("Lb%dE" % (a == "true") if a in ("true", "false") else "Li%sE" % a for a in parts)
     return "cheby_pair_kernelI" + enc + "E"
 
@@ -218,10 +223,11 @@ def main():
     ap.add_argument("--asm", help="device assembly of pair.hip, already compiled")
     ap.add_argument("--src", default=os.path.join(ROOT, "hpgmg_amd", "csrc", "kernels", "pair.hip"))
     ap.add_argument("--before-edgew", action="store_true", help="the assembly (--asm) comes from a commit before the EDGEW template parameter: eight arguments in the symbol")
+    ap.add_argument("--before-ua", action="store_true", help="the assembly (--asm) comes from a commit before the UA template parameter: nine arguments in the symbol")
     ap.add_argument("instances", nargs="*", default=DEFAULT)
     args = ap.parse_args()
-    global BEFORE_EDGEW
-    BEFORE_EDGEW = args.before_edgew
+    global BEFORE_EDGEW, BEFORE_UA
+    BEFORE_EDGEW, BEFORE_UA = args.before_edgew, args.before_ua
     lines = open(args.asm or compile_asm(args.src)).read().splitlines()
     for inst in args.instances:
         report(lines, inst)
