@@ -38,7 +38,7 @@ static int lazy_enabled(void) {
 }
 /* LZ_SMALL: BLAS-1 calls, apply_op and residual on a level of ONE box of side <= 8 wait for the dot product or norm that follows them -- what a
  * host-driven Krylov solver on the bottom level issues between two scalars it needs (the reference's solvers/bicgstab.c, "Route B"; host/solvers.c
- * with HPGMG_FUSED_BOTTOM=0) -- and go out with it as ONE launch (kernels/stencil.hip: small_ops_kernel): 6 launches per BiCGStab iteration
+ * with HPGMG_FUSED_BOTTOM=0) -- and go out with it as ONE launch (kernels/small_levels.hip: small_ops_kernel): 6 launches per BiCGStab iteration
  * instead of ~18.  HPGMG_SMALL_OPS=0 / hpgmg_set_small_ops(0) turn it off. */
 static long long small_ops_groups = 0;
 void hpgmg_set_small_ops(int on) { hp_lazy_flush(); hp_switch_set(SW_SMALL_OPS, on ? 1 : 0); }

@@ -14,7 +14,7 @@ void hp_cheby_coefficients(const level_type *L, int degree, double *c1, double *
 }
 
 /* Small levels of the 27-point / fv2 / fv4 plugins: smooth(), residual() or apply_op() with their exchange_boundary + apply_BCs steps as
- * ONE single-workgroup launch (kernels/stencil.hip: small_level_kernel).
+ * ONE single-workgroup launch (kernels/small_levels.hip: small_level_kernel).
  * Returns 0 when the level does not qualify (too large, messages needed, 7-point plugin: that one has the LDS-resident tail kernel).
  * OFF by default (HPGMG_SMALL_FUSED=1 enables; bit-identical, covered by the GPU tests): measured on MI355X it is SLOWER than the
  * launches it replaces -- fv4 GSRB `7 8` 17.1 vs 12.7 ms, 27-pt GSRB 9.9 vs 6.2 ms per F-cycle -- because a 16^3 level in 8 boxes has

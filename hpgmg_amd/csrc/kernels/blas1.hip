@@ -10,6 +10,7 @@
 // (BiCGStab) and in untimed setup, so one lane per tile is enough.
 #include "reduce.hpp"
 #include "knobs.hpp"
+#include "launch_dispatch.hpp"
 
 namespace hpgmg {
 
@@ -479,9 +480,7 @@ static int ordered_sum(const hpgmg_hip_level *L, int id_a, int id_b, double *out
     if (L->dim <= 128)      hipLaunchKernelGGL((tile_sum_wave_kernel<2>), dim3(ntiles), dim3(64), lds, g_stream, *L, id_a, id_b, partials);
     else if (L->dim <= 256) hipLaunchKernelGGL((tile_sum_wave_kernel<4>), dim3(ntiles), dim3(64), lds, g_stream, *L, id_a, id_b, partials);
     else if (L->dim <= 64 * kSumMaxChunks) {
-      static bool once = false;
-      if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)tile_sum_wave_kernel<kSumMaxChunks>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)2 * kSumGroup * 64 * kSumMaxChunks * sizeof(double)))); once = true; }
-      hipLaunchKernelGGL((tile_sum_wave_kernel<kSumMaxChunks>), dim3(ntiles), dim3(64), lds, g_stream, *L, id_a, id_b, partials);
+      if (int e = launch_lds<tile_sum_wave_kernel<kSumMaxChunks>>((size_t)2 * kSumGroup * 64 * kSumMaxChunks * sizeof(double), dim3(ntiles), dim3(64), lds, *L, id_a, id_b, partials)) return e;
     }
     else hipLaunchKernelGGL((tile_sum_kernel<false>), dim3((ntiles + 63) / 64), dim3(64), 0, g_stream, *L, id_a, id_b, partials, t.slot, 0ULL);
     hipLaunchKernelGGL(ordered_sum_kernel, dim3(1), dim3(64), 0, g_stream, (const double *)partials, ntiles, t.slot, t.seq);

@@ -1,5 +1,5 @@
 // block_ops.hpp -- entry routines of the block-list executors (ghost-exchange copies and the boundary conditions), shared by the
-// streaming kernels of blocks.hip (one workgroup per list entry) and the single-workgroup small-level kernels of stencil.hip (one
+// streaming kernels of blocks.hip (one workgroup per list entry) and the single-workgroup small-level kernels of small_levels.hip (one
 // wave per entry).  Reference semantics per entry: operators/blockCopy.c:6-156, boundary_fd.c:6-205, boundary_fv.c:101-569.
 #pragma once
 #include "common.hpp"
@@ -25,7 +25,7 @@ __device__ __forceinline__ Side resolve_write(const hpgmg_hip_level &L, int id, 
 }
 
 // Every list executor below is an ENTRY routine: lanes tid, tid + nth, ... of the caller work through entry e.  The streaming kernels
-// (blocks.hip) give one workgroup to an entry; the single-workgroup small-level kernels (stencil.hip) give a wave to an entry.
+// (blocks.hip) give one workgroup to an entry; the single-workgroup small-level kernels (small_levels.hip) give a wave to an entry.
 template <bool kIncrement>
 __device__ __forceinline__ void copy_entry(const hpgmg_hip_level &L, int id, const blockCopy_type &e, double prescale, int tid, int nth) {
   const Side r = resolve_read(L, id, e), w = resolve_write(L, id, e);

@@ -32,6 +32,7 @@
 // tests/test_gpu_operators.py runs both, tools/stress_bricks.py repeats a cycle hundreds of times and compares the bytes.
 #include "common.hpp"
 #include "knobs.hpp"
+#include "launch_dispatch.hpp"
 #include "stencil_math.hpp"
 #include "dense_levels.hpp"
 #include "brick_records.hpp"
@@ -399,11 +400,8 @@ bool brick_error_pending(void) { return g_error && *(volatile unsigned *)g_error
 template <int DIR, int B> constexpr size_t brick_lds_bytes() { return ((size_t)2 * BrickGeom<B>::Halo + (DIR == DIR_FDOWN ? (size_t)(B / 2 + 2) * (B / 2 + 2) * (B / 2 + 2) : 0)) * sizeof(double); }
 template <int V, int SM, int DIR, int B>
 static int brick_launch(const BrickArgs &A) {
-  static bool once = false;
   const size_t lds = brick_lds_bytes<DIR, B>();
-  if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)brick_chain_kernel<V, SM, DIR, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; }
-  hipLaunchKernelGGL((brick_chain_kernel<V, SM, DIR, B>), dim3(A.lv[0].nwg), dim3(BrickGeom<B>::Threads), lds, g_stream, A);
-  return 0;
+  return launch_lds<brick_chain_kernel<V, SM, DIR, B>>(lds, dim3(A.lv[0].nwg), dim3(BrickGeom<B>::Threads), lds, A);
 }
 // workgroups of the (variant, smoother) kernels the device holds at once: the smallest figure of the three directions
 template <int V, int SM, int B>
@@ -423,6 +421,8 @@ static int brick_launch_dir(const BrickArgs &A, int dir, int brick) {
   if (brick == 16) return dir == 0 ? brick_launch<V, SM, 0, 16>(A) : (dir == 1 ? brick_launch<V, SM, 1, 16>(A) : brick_launch<V, SM, 2, 16>(A));
   return dir == 0 ? brick_launch<V, SM, 0, 8>(A) : (dir == 1 ? brick_launch<V, SM, 1, 8>(A) : brick_launch<V, SM, 2, 8>(A));
 }
+
+static_assert(BV_CHEBY == 0 && BV_GSRB == 1 && BV_JACOBI == 2, "k7ptSmootherKeys decodes key % 3 as a BV_* smoother");
 
 }  // namespace hpgmg
 using namespace hpgmg;
@@ -452,19 +452,8 @@ int hpgmg_hip_brick_visit_error_clear(void) {
 // How many workgroups of the (variant, smoother) brick kernels this device holds at once, less a margin of one eighth for whatever else is running: a launch
 // of more than that many bricks would wait for workgroups that cannot start (the caller then takes the launch-by-launch path).
 int hpgmg_hip_brick_chain_capacity(int variant, int smoother, int brick) {
-  int cap;
-  switch (variant * 3 + smoother) {
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ * 3 + BV_CHEBY:  cap = brick_capacity_of<HPGMG_HIP_7PT_VC_HELMHOLTZ, BV_CHEBY>(brick); break;
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ * 3 + BV_GSRB:   cap = brick_capacity_of<HPGMG_HIP_7PT_VC_HELMHOLTZ, BV_GSRB>(brick); break;
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ * 3 + BV_JACOBI: cap = brick_capacity_of<HPGMG_HIP_7PT_VC_HELMHOLTZ, BV_JACOBI>(brick); break;
-    case HPGMG_HIP_7PT_VC_POISSON * 3 + BV_CHEBY:    cap = brick_capacity_of<HPGMG_HIP_7PT_VC_POISSON, BV_CHEBY>(brick); break;
-    case HPGMG_HIP_7PT_VC_POISSON * 3 + BV_GSRB:     cap = brick_capacity_of<HPGMG_HIP_7PT_VC_POISSON, BV_GSRB>(brick); break;
-    case HPGMG_HIP_7PT_VC_POISSON * 3 + BV_JACOBI:   cap = brick_capacity_of<HPGMG_HIP_7PT_VC_POISSON, BV_JACOBI>(brick); break;
-    case HPGMG_HIP_7PT_CC * 3 + BV_CHEBY:            cap = brick_capacity_of<HPGMG_HIP_7PT_CC, BV_CHEBY>(brick); break;
-    case HPGMG_HIP_7PT_CC * 3 + BV_GSRB:             cap = brick_capacity_of<HPGMG_HIP_7PT_CC, BV_GSRB>(brick); break;
-    case HPGMG_HIP_7PT_CC * 3 + BV_JACOBI:           cap = brick_capacity_of<HPGMG_HIP_7PT_CC, BV_JACOBI>(brick); break;
-    default: return 0;
-  }
+  int cap = 0;
+  if (!with_variant(k7ptSmootherKeys,variant * 3 + smoother, &cap, [&](auto key) { return brick_capacity_of<key / 3, key % 3>(brick); })) return 0;
   return cap - cap / 8;
 }
 
@@ -490,20 +479,9 @@ int hpgmg_hip_brick_chain(int n, const hpgmg_hip_brick_level *levels, const hpgm
   A.top_e_zero = (dir == 0 && top_e_zero) ? 1 : 0; A.below_zero = below_zero ? 1 : 0;
   { const int rc = brick_records_for_launch(&A.Rc); if (rc) return rc; }
   A.absent_wg = brick_test_absent_wg();
-  int rc;
-  const int key = variant * 3 + smoother;
-  switch (key) {
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ * 3 + BV_CHEBY:  rc = brick_launch_dir<HPGMG_HIP_7PT_VC_HELMHOLTZ, BV_CHEBY>(A, dir, brick); break;
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ * 3 + BV_GSRB:   rc = brick_launch_dir<HPGMG_HIP_7PT_VC_HELMHOLTZ, BV_GSRB>(A, dir, brick); break;
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ * 3 + BV_JACOBI: rc = brick_launch_dir<HPGMG_HIP_7PT_VC_HELMHOLTZ, BV_JACOBI>(A, dir, brick); break;
-    case HPGMG_HIP_7PT_VC_POISSON * 3 + BV_CHEBY:    rc = brick_launch_dir<HPGMG_HIP_7PT_VC_POISSON, BV_CHEBY>(A, dir, brick); break;
-    case HPGMG_HIP_7PT_VC_POISSON * 3 + BV_GSRB:     rc = brick_launch_dir<HPGMG_HIP_7PT_VC_POISSON, BV_GSRB>(A, dir, brick); break;
-    case HPGMG_HIP_7PT_VC_POISSON * 3 + BV_JACOBI:   rc = brick_launch_dir<HPGMG_HIP_7PT_VC_POISSON, BV_JACOBI>(A, dir, brick); break;
-    case HPGMG_HIP_7PT_CC * 3 + BV_CHEBY:            rc = brick_launch_dir<HPGMG_HIP_7PT_CC, BV_CHEBY>(A, dir, brick); break;
-    case HPGMG_HIP_7PT_CC * 3 + BV_GSRB:             rc = brick_launch_dir<HPGMG_HIP_7PT_CC, BV_GSRB>(A, dir, brick); break;
-    case HPGMG_HIP_7PT_CC * 3 + BV_JACOBI:           rc = brick_launch_dir<HPGMG_HIP_7PT_CC, BV_JACOBI>(A, dir, brick); break;
-    default: return record_error(hipErrorInvalidValue, "brick_chain: variant / smoother");
-  }
+  int rc = 0;
+  if (!with_variant(k7ptSmootherKeys,variant * 3 + smoother, &rc, [&](auto key) { return brick_launch_dir<key / 3, key % 3>(A, dir, brick); }))
+    return record_error(hipErrorInvalidValue, "brick_chain: variant / smoother");
   if (rc) return rc;
   HPGMG_LAUNCH_CHECK("brick_chain_kernel");
   brick_count_visits(n);

@@ -21,6 +21,7 @@
 // Records, tags, epochs, the error words and the co-residency guard: brick_records.hpp.  Arithmetic: the expression trees of the per-operator kernels
 // (fv4_math.hpp fv4_sum, stencil_direct.hpp apply_op_27pt, block_ops.hpp bc_*_cell / interp_rule, restriction.c:54-57), so every vector is bit-identical to
 // the per-operator path; tests/test_gpu_operators.py runs both against the oracle.
+#include "launch_dispatch.hpp"
 #include "stencil_direct.hpp"
 #include "dense_levels.hpp"
 #include "brick_records.hpp"
@@ -447,11 +448,8 @@ __global__ __launch_bounds__((WideGeom<V, B>::Threads), (B == 8 ? 3 : 1)) void b
 template <int V, int DIR, int B> constexpr size_t wide_lds_bytes() { return ((size_t)2 * WideGeom<V, B>::Cells + WideGeom<V, B>::BetaDoubles + (DIR == BW_UP ? WideGeom<V, B>::CoarseCells : 0)) * sizeof(double); }
 template <int V, int SM, int DIR, int B>
 static int wide_launch(const WideArgs &A) {
-  static bool once = false;
   const size_t lds = wide_lds_bytes<V, DIR, B>();
-  if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)brick_wide_kernel<V, SM, DIR, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; }
-  hipLaunchKernelGGL((brick_wide_kernel<V, SM, DIR, B>), dim3(A.lv[0].nwg), dim3(WideGeom<V, B>::Threads), lds, g_stream, A);
-  return 0;
+  return launch_lds<brick_wide_kernel<V, SM, DIR, B>>(lds, dim3(A.lv[0].nwg), dim3(WideGeom<V, B>::Threads), lds, A);
 }
 // (bricks of 2^3: the 27-point operator only)
 template <int V, int SM, int DIR>
@@ -469,6 +467,9 @@ static int wide_capacity() {
   }
   return cap;
 }
+// variant * 2 + smoother: the 27-point and the two fv4 variants (3..5) times BW_CHEBY / BW_GSRB (0..1)
+constexpr variant_list<6, 7, 8, 9, 10, 11> kWideKeys{};
+static_assert(HPGMG_HIP_27PT_CC == 3 && HPGMG_HIP_FV4_VC_POISSON == 5, "kWideKeys lists variants 3..5");
 
 }  // namespace hpgmg
 using namespace hpgmg;
@@ -488,16 +489,8 @@ int hpgmg_hip_brick_wide_supported(const hpgmg_hip_level *L, int variant) {
 }
 // workgroups of the (variant, smoother) kernels this device holds at once, less an eighth (hpgmg_hip_brick_chain_capacity)
 int hpgmg_hip_brick_wide_capacity(int variant, int smoother) {
-  int cap;
-  switch (variant * 2 + smoother) {
-    case HPGMG_HIP_27PT_CC * 2 + BW_CHEBY:           cap = wide_capacity<HPGMG_HIP_27PT_CC, BW_CHEBY>(); break;
-    case HPGMG_HIP_27PT_CC * 2 + BW_GSRB:            cap = wide_capacity<HPGMG_HIP_27PT_CC, BW_GSRB>(); break;
-    case HPGMG_HIP_FV4_VC_HELMHOLTZ * 2 + BW_CHEBY:  cap = wide_capacity<HPGMG_HIP_FV4_VC_HELMHOLTZ, BW_CHEBY>(); break;
-    case HPGMG_HIP_FV4_VC_HELMHOLTZ * 2 + BW_GSRB:   cap = wide_capacity<HPGMG_HIP_FV4_VC_HELMHOLTZ, BW_GSRB>(); break;
-    case HPGMG_HIP_FV4_VC_POISSON * 2 + BW_CHEBY:    cap = wide_capacity<HPGMG_HIP_FV4_VC_POISSON, BW_CHEBY>(); break;
-    case HPGMG_HIP_FV4_VC_POISSON * 2 + BW_GSRB:     cap = wide_capacity<HPGMG_HIP_FV4_VC_POISSON, BW_GSRB>(); break;
-    default: return 0;
-  }
+  int cap = 0;
+  if (!with_variant(kWideKeys, variant * 2 + smoother, &cap, [&](auto key) { return wide_capacity<key / 2, key % 2>(); })) return 0;
   return cap - cap / 8;
 }
 
@@ -524,22 +517,13 @@ int hpgmg_hip_brick_wide_chain(int n, const hpgmg_hip_brick_level *levels, const
   A.top_e_zero = (dir == 0 && top_e_zero) ? 1 : 0; A.below_zero = below_zero ? 1 : 0;
   { const int rc = brick_records_for_launch(&A.Rc); if (rc) return rc; }
   A.absent_wg = brick_test_absent_wg();
-  int rc;
-#define WIDE_CASE(VV, SS) case VV * 2 + SS: \
-    if (brick == 8)      rc = (dir == 0) ? wide_launch<VV, SS, BW_DOWN, 8>(A) : wide_launch<VV, SS, BW_UP, 8>(A); \
-    else if (brick == 4) rc = (dir == 0) ? wide_launch<VV, SS, BW_DOWN, 4>(A) : wide_launch<VV, SS, BW_UP, 4>(A); \
-    else                 rc = (dir == 0) ? wide_launch2<VV, SS, BW_DOWN>(A) : wide_launch2<VV, SS, BW_UP>(A); \
-    break
-  switch (variant * 2 + smoother) {
-    WIDE_CASE(HPGMG_HIP_27PT_CC, BW_CHEBY);
-    WIDE_CASE(HPGMG_HIP_27PT_CC, BW_GSRB);
-    WIDE_CASE(HPGMG_HIP_FV4_VC_HELMHOLTZ, BW_CHEBY);
-    WIDE_CASE(HPGMG_HIP_FV4_VC_HELMHOLTZ, BW_GSRB);
-    WIDE_CASE(HPGMG_HIP_FV4_VC_POISSON, BW_CHEBY);
-    WIDE_CASE(HPGMG_HIP_FV4_VC_POISSON, BW_GSRB);
-    default: return record_error(hipErrorInvalidValue, "brick_wide_chain: variant / smoother");
-  }
-#undef WIDE_CASE
+  int rc = 0;
+  if (!with_variant(kWideKeys, variant * 2 + smoother, &rc, [&](auto key) {
+        constexpr int VV = key / 2, SS = key % 2;
+        if (brick == 8) return (dir == 0) ? wide_launch<VV, SS, BW_DOWN, 8>(A) : wide_launch<VV, SS, BW_UP, 8>(A);
+        if (brick == 4) return (dir == 0) ? wide_launch<VV, SS, BW_DOWN, 4>(A) : wide_launch<VV, SS, BW_UP, 4>(A);
+        return (dir == 0) ? wide_launch2<VV, SS, BW_DOWN>(A) : wide_launch2<VV, SS, BW_UP>(A); }))
+    return record_error(hipErrorInvalidValue, "brick_wide_chain: variant / smoother");
   if (rc) return rc;
   HPGMG_LAUNCH_CHECK("brick_wide_kernel");
   brick_count_visits(n);

@@ -5,13 +5,11 @@
 #include <vector>
 #include "common.hpp"
 #include "knobs.hpp"
+#include "launch_dispatch.hpp"
+#include "stencil_direct.hpp"      // profile_begin / profile_end
 #include "fv4_tile.hpp"
 #include "fv4_rb.hpp"
 
-namespace hpgmg {
-int  profile_begin(long long cells);          // stencil.hip: hipEvent pair around a smoother launch (bench.py's roofline)
-void profile_end(int p, long long cells, bool first_part = false);
-}
 using namespace hpgmg;
 
 extern "C" {
@@ -79,9 +77,10 @@ int hpgmg_hip_fv4_rb_prepass(const hpgmg_hip_level *L, int variant, double *cons
   Fv4SpecialArgs S = {};
   S.x = vec_sel(L, scr_base, x_scratch, x_id); S.tg = vec_sel(L, scr_base, 1, tg_id); S.rhs_id = rhs_id; S.a = a; S.b = b; S.h2inv = h2inv; S.sweep = sweep;
   S.cells = special_cells; S.n = n_special > 0 ? n_special : 0;
+  int e = 0;
   if (n_special > 0 && n_k <= 0) {
-    if (variant == HPGMG_HIP_FV4_VC_HELMHOLTZ) hipLaunchKernelGGL((fv4_special_kernel<HPGMG_HIP_FV4_VC_HELMHOLTZ>), dim3((n_special + 255) / 256), dim3(256), 0, g_stream, *L, S);
-    else hipLaunchKernelGGL((fv4_special_kernel<HPGMG_HIP_FV4_VC_POISSON>), dim3((n_special + 255) / 256), dim3(256), 0, g_stream, *L, S);
+    if (!with_variant(kFv4Variants, variant, &e, [&](auto v) { hipLaunchKernelGGL((fv4_special_kernel<v>), dim3((n_special + 255) / 256), dim3(256), 0, g_stream, *L, S); return 0; }))
+      return record_error(hipErrorInvalidValue, "fv4_rb_prepass: variant");
     HPGMG_LAUNCH_CHECK("fv4_special_kernel");
   }
   if (n_k <= 0) return 0;                                  // no k wall on this rank's boxes (periodic)
@@ -89,17 +88,16 @@ int hpgmg_hip_fv4_rb_prepass(const hpgmg_hip_level *L, int variant, double *cons
   P.xn_id = x_id; P.xout_id = tg_id; P.rhs_id = rhs_id; P.a = a; P.b = b; P.h2inv = h2inv; P.sweep = sweep; P.copy_other_colour = 1; P.ghost_free = 1;
   P.x_base = x_scratch ? scr_base : nullptr; P.out_base = scr_base;
   P.kchunk = 4; P.chunks_k = 2; P.k_origin = 0; P.k_step = L->dim - 4; P.wall_only = 1;
-#define FV4_PRE_CASE(VAR, TJ, TI) { \
-    P.tiles_i = L->dim / TI; P.tiles_j = L->dim / TJ; P.total_blocks = L->num_boxes * P.chunks_k * P.tiles_j * P.tiles_i; \
-    const int grid = grid_for(P.total_blocks, &P.per_xcd); \
-    const size_t lds = (size_t)11 * (TI + 4) * (TJ + 4) * sizeof(double); \
-    const int sp_blocks = (S.n + TI * TJ - 1) / (TI * TJ); \
-    static bool once = false; if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)fv4_rb_prepass_kernel<VAR, TJ, TI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; } \
-    hipLaunchKernelGGL((fv4_rb_prepass_kernel<VAR, TJ, TI>), dim3(grid + sp_blocks), dim3(TI, TJ), lds, g_stream, *L, P, S, sp_blocks); }
-  const bool wide = L->dim % 64 == 0;
-  if (variant == HPGMG_HIP_FV4_VC_HELMHOLTZ) { if (wide) FV4_PRE_CASE(HPGMG_HIP_FV4_VC_HELMHOLTZ, 8, 64) else FV4_PRE_CASE(HPGMG_HIP_FV4_VC_HELMHOLTZ, 16, 32) }
-  else                                       { if (wide) FV4_PRE_CASE(HPGMG_HIP_FV4_VC_POISSON, 8, 64) else FV4_PRE_CASE(HPGMG_HIP_FV4_VC_POISSON, 16, 32) }
-#undef FV4_PRE_CASE
+  // tiles of 64 x 8 cells on boxes of side 64 m, of 32 x 16 otherwise
+  const bool listed = with_variant(kFv4Variants, variant, &e, [&](auto v) { return with_bool(L->dim % 64 == 0, [&](auto wide) {
+    constexpr int TI = wide ? 64 : 32, TJ = wide ? 8 : 16;
+    P.tiles_i = L->dim / TI; P.tiles_j = L->dim / TJ; P.total_blocks = L->num_boxes * P.chunks_k * P.tiles_j * P.tiles_i;
+    const int grid = grid_for(P.total_blocks, &P.per_xcd);
+    const size_t lds = (size_t)11 * (TI + 4) * (TJ + 4) * sizeof(double);
+    const int sp_blocks = (S.n + TI * TJ - 1) / (TI * TJ);
+    return launch_lds<fv4_rb_prepass_kernel<v, TJ, TI>>(lds, dim3(grid + sp_blocks), dim3(TI, TJ), lds, *L, P, S, sp_blocks); }); });
+  if (!listed) return record_error(hipErrorInvalidValue, "fv4_rb_prepass: variant");
+  if (e) return e;
   HPGMG_LAUNCH_CHECK("fv4_rb_prepass_kernel");
   hpgmg_hip_level Ls = *L;
   Ls.box_base = scr_base;
@@ -135,12 +133,11 @@ int hpgmg_hip_smooth_gsrb_fv4_rb(const hpgmg_hip_level *L, int variant, double *
   A.timeline = g_fv4rb_timeline; A.timeline_wg = (int)knob(K_EXP_TIMELINE_WG);
 #endif
   const int prof = profile_begin(whole_cells);               // (the caller's size threshold is on the whole launch; a part reports its share of the cells)
-#define FV4_RB_CASE(VAR, TI_) { \
-    constexpr size_t lds = fv4rb::Geom<TI_>::LDS_BYTES; \
-    static bool once = false; if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)fv4_rb_kernel<VAR, TI_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; } \
-    hipLaunchKernelGGL((fv4_rb_kernel<VAR, TI_>), dim3(grid), dim3(TI_, 8), lds, g_stream, *L, A); }
-  if (variant == HPGMG_HIP_FV4_VC_HELMHOLTZ) FV4_RB_CASE(HPGMG_HIP_FV4_VC_HELMHOLTZ, 64) else FV4_RB_CASE(HPGMG_HIP_FV4_VC_POISSON, 64)
-#undef FV4_RB_CASE
+  constexpr size_t lds = fv4rb::Geom<64>::LDS_BYTES;
+  int e = 0;
+  if (!with_variant(kFv4Variants, variant, &e, [&](auto v) { return launch_lds<fv4_rb_kernel<v, 64>>(lds, dim3(grid), dim3(64, 8), lds, *L, A); }))
+    return record_error(hipErrorInvalidValue, "smooth_gsrb_fv4_rb: variant");
+  if (e) return e;
   g_rb4_launches++;
   profile_end(prof, 2 * cells, g_tile_part == 1);       // one launch = two half sweeps over every cell
   HPGMG_LAUNCH_CHECK("fv4_rb_kernel");

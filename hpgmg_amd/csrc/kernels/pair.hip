@@ -1,8 +1,10 @@
 // pair.hip -- launchers of the two-sweeps-per-pass kernel of the 7-point operator (cheby_pair.hpp: Chebyshev sweep pairs, chebyshev.c:43-99, and
 // pairs of in-place GSRB half sweeps, gsrb.c:24-132), of its pre-pass, of the packed pre-pass coefficients, of the two-part launches across rank
 // boundaries, and the pack / unpack kernel of its halo messages.  A translation unit of its own (split from stencil.hip in round 4).
+// Every launch of the kernel goes through launch_lds (launch_dispatch.hpp); which of its instances a launch takes is chosen by the macros of smooth_pair.
 #include "stencil_direct.hpp"
 #include "knobs.hpp"
+#include "launch_dispatch.hpp"
 #include "cheby_pair.hpp"
 
 namespace hpgmg {
@@ -51,10 +53,7 @@ using namespace hpgmg;
 // and of that the UA twin (alpha from PairArgs.alpha_uniform, cheby_pair.hpp) where ua says so: Chebyshev, Helmholtz (smooth_pair: only with form_dinv)
 template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP, bool FORM, bool UA = false>
 static int pair_launch_instance(int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A) {
-  static bool once = false;
-  if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)cheby_pair_kernel<V, NW, C32, SM, NARROW, INTERP, false, FORM, false, UA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NW * 6 * 64 * sizeof(p2)))); once = true; }
-  hipLaunchKernelGGL((cheby_pair_kernel<V, NW, C32, SM, NARROW, INTERP, false, FORM, false, UA>), dim3(grid), dim3(64, NW), lds, g_stream, *L, A);
-  return 0;
+  return launch_lds<cheby_pair_kernel<V, NW, C32, SM, NARROW, INTERP, false, FORM, false, UA>>((size_t)NW * 6 * 64 * sizeof(p2), dim3(grid), dim3(64, NW), lds, *L, A);
 }
 template <int V, int NW, bool C32, int SM, bool NARROW, bool INTERP>
 static int pair_launch(int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A, bool ua) {
@@ -69,10 +68,7 @@ static long long g_pair_edge_wave_launches = 0;
 template <int V, int SM, bool C32, bool INTERP, bool FORM, bool UA = false>
 static int pair_launch_edge_wave_instance(int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A) {
   constexpr int NW = 10;
-  static bool once = false;
-  if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)cheby_pair_kernel<V, NW, C32, SM, false, INTERP, false, FORM, true, UA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); once = true; }
-  hipLaunchKernelGGL((cheby_pair_kernel<V, NW, C32, SM, false, INTERP, false, FORM, true, UA>), dim3(grid), dim3(64, NW + 1), lds, g_stream, *L, A);
-  return 0;
+  return launch_lds<cheby_pair_kernel<V, NW, C32, SM, false, INTERP, false, FORM, true, UA>>(lds, dim3(grid), dim3(64, NW + 1), lds, *L, A);
 }
 template <int V, int SM, bool C32, bool INTERP>
 static int pair_launch_edge_wave(int nw, int grid, size_t lds, const hpgmg_hip_level *L, const PairArgs &A, bool ua, bool *taken) {
@@ -282,8 +278,7 @@ static int smooth_pair(const hpgmg_hip_level *L, int variant, int gsrb, int swee
       A.edge_blocks = ((A.Dj + 63) / 64) * A.Dk * ecols; const int egrid_r = grid_for(A.edge_blocks, &A.edge_per_xcd); \
       if (ecols > 0) hipLaunchKernelGGL((cheby_pair_edge_kernel<VAR, false, SM, IP, true>), dim3(egrid_r), dim3(64), 0, g_stream, *L, A); \
       PAIR_NW_SWITCH( \
-      static bool once = false; if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)cheby_pair_kernel<VAR, NWC, false, SM, NRW, IP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)NWC * 6 * 64 * sizeof(p2)))); once = true; } \
-      hipLaunchKernelGGL((cheby_pair_kernel<VAR, NWC, false, SM, NRW, IP, true>), dim3(grid), dim3(64, NWC), lds, g_stream, *L, A); ) }
+      { const int e_ = launch_lds<cheby_pair_kernel<VAR, NWC, false, SM, NRW, IP, true>>((size_t)NWC * 6 * 64 * sizeof(p2), dim3(grid), dim3(64, NWC), lds, *L, A); if (e_) return e_; } ) }
 #define PAIR_LAUNCH_REMOTE(VAR, SM) { if (L->dim % 128 != 0) PAIR_LAUNCH_REMOTE_IP(VAR, SM, true, false) else if (interp) PAIR_LAUNCH_REMOTE_IP(VAR, SM, false, true) else PAIR_LAUNCH_REMOTE_IP(VAR, SM, false, false) }
 #define PAIR_LAUNCH(VAR, C32, SM) { \
       A.edge_blocks = ((A.Dj + 63) / 64) * A.Dk * 2 * (A.tiles_i - 1); const dim3 egrid(A.edge_blocks > 0 ? grid_for(A.edge_blocks, &A.edge_per_xcd) : 1); \

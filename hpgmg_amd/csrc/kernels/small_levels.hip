@@ -4,6 +4,7 @@
 // of a V-cycle below a level of one box (mg.c:1145-1164: small_vtail_kernel).  A translation unit of its own (split from stencil.hip in round 4).
 #include "reduce.hpp"
 #include "knobs.hpp"
+#include "launch_dispatch.hpp"
 #include "stencil_direct.hpp"
 
 namespace hpgmg {
@@ -634,6 +635,8 @@ __global__ __launch_bounds__(512) void small_vtail_kernel(const hpgmg_hip_small_
 }  // namespace hpgmg
 using namespace hpgmg;
 
+static constexpr size_t kSmallLdsMax = 150 * 1024;      // dynamic LDS the single-workgroup kernels are allowed: the limit of their size checks and of launch_lds
+
 extern "C" {
 int hpgmg_hip_graph_flush(void);
 
@@ -656,26 +659,17 @@ int hpgmg_hip_small_level_op(const hpgmg_hip_level *L, int variant, int mode, in
   const int threads = cells >= 1024 ? 1024 : (cells >= 256 ? 256 : 64);
   // one box whose vectors fit the LDS: work on an image of it there
   const size_t image = (size_t)kSmallSlots * (size_t)L->volume * sizeof(double);
-  A.lds_resident = (!knob(K_SMALL_NO_LDS) && L->num_boxes == 1 && A.n_copy == 0 && image <= 150 * 1024) ? 1 : 0;
+  A.lds_resident = (!knob(K_SMALL_NO_LDS) && L->num_boxes == 1 && A.n_copy == 0 && image <= kSmallLdsMax) ? 1 : 0;
 #ifdef HPGMG_EXP_TIMELINE
   A.timeline = (unsigned long long *)g_exp_timeline;
 #endif
   const size_t lds = A.lds_resident ? image : 0;
   const int threads_used = A.lds_resident ? 1024 : threads;        // the image is copied by every lane there is
   if (!A.lds_resident) return record_error(hipErrorInvalidValue, "small_level_op: a level of one box whose vectors fit the LDS");
-#define SMALL_CASE(VAR) { \
-    static bool once = false; if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)small_level_kernel<VAR>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); once = true; } \
-    hipLaunchKernelGGL((small_level_kernel<VAR>), dim3(1), dim3(threads_used), lds, g_stream, *L, A); }
-  switch (variant) {
-    case HPGMG_HIP_27PT_CC:          SMALL_CASE(HPGMG_HIP_27PT_CC) break;
-    case HPGMG_HIP_FV4_VC_HELMHOLTZ: SMALL_CASE(HPGMG_HIP_FV4_VC_HELMHOLTZ) break;
-    case HPGMG_HIP_FV4_VC_POISSON:   SMALL_CASE(HPGMG_HIP_FV4_VC_POISSON) break;
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ: SMALL_CASE(HPGMG_HIP_7PT_VC_HELMHOLTZ) break;
-    case HPGMG_HIP_7PT_VC_POISSON:   SMALL_CASE(HPGMG_HIP_7PT_VC_POISSON) break;
-    case HPGMG_HIP_7PT_CC:           SMALL_CASE(HPGMG_HIP_7PT_CC) break;
-    default: return record_error(hipErrorInvalidValue, "small_level_op: variant");
-  }
-#undef SMALL_CASE
+  int e = 0;
+  if (!with_variant(kAllVariants, variant, &e, [&](auto v) { return launch_lds<small_level_kernel<v>>(kSmallLdsMax, dim3(1), dim3(threads_used), lds, *L, A); }))
+    return record_error(hipErrorInvalidValue, "small_level_op: variant");
+  if (e) return e;
   HPGMG_LAUNCH_CHECK("small_level_kernel");
   return 0;
 }
@@ -695,20 +689,11 @@ int hpgmg_hip_bottom_bicgstab(const hpgmg_hip_level *L, int variant, int x_id, i
   const int tune_threads = (int)knob(K_BOTTOM_THREADS);
   const int threads = (cells > 256 || tune_threads >= 512) ? 512 : (cells > 64 || tune_threads >= 256 ? 256 : 64);
   const size_t lds = ((size_t)5 * L->volume + 1100) * sizeof(double);
-  if (lds > 150 * 1024) return record_error(hipErrorInvalidValue, "bottom_bicgstab: box too large for the LDS image");
-#define BOTTOM_CASE(VAR) { \
-    static bool once = false; if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)bottom_bicgstab_kernel<VAR>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); once = true; } \
-    hipLaunchKernelGGL((bottom_bicgstab_kernel<VAR>), dim3(1), dim3(threads), lds, g_stream, *L, A); }
-  switch (variant) {
-    case HPGMG_HIP_27PT_CC:          BOTTOM_CASE(HPGMG_HIP_27PT_CC) break;
-    case HPGMG_HIP_FV4_VC_HELMHOLTZ: BOTTOM_CASE(HPGMG_HIP_FV4_VC_HELMHOLTZ) break;
-    case HPGMG_HIP_FV4_VC_POISSON:   BOTTOM_CASE(HPGMG_HIP_FV4_VC_POISSON) break;
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ: BOTTOM_CASE(HPGMG_HIP_7PT_VC_HELMHOLTZ) break;
-    case HPGMG_HIP_7PT_VC_POISSON:   BOTTOM_CASE(HPGMG_HIP_7PT_VC_POISSON) break;
-    case HPGMG_HIP_7PT_CC:           BOTTOM_CASE(HPGMG_HIP_7PT_CC) break;
-    default: return record_error(hipErrorInvalidValue, "bottom_bicgstab: variant");
-  }
-#undef BOTTOM_CASE
+  if (lds > kSmallLdsMax) return record_error(hipErrorInvalidValue, "bottom_bicgstab: box too large for the LDS image");
+  int e = 0;
+  if (!with_variant(kAllVariants, variant, &e, [&](auto v) { return launch_lds<bottom_bicgstab_kernel<v>>(kSmallLdsMax, dim3(1), dim3(threads), lds, *L, A); }))
+    return record_error(hipErrorInvalidValue, "bottom_bicgstab: variant");
+  if (e) return e;
   HPGMG_LAUNCH_CHECK("bottom_bicgstab_kernel");
   return 0;
 }
@@ -737,24 +722,16 @@ int hpgmg_hip_small_ops(const hpgmg_hip_level *L, int variant, int n, const int 
   if (wants) if (int e = scalar_begin(&A.t)) return e;
   const int cells = L->dim * L->dim * L->dim;
   const int threads = cells > 64 ? 512 : (A.n_bc > 4 ? 512 : 64);           // one cell per lane (no striding); the boundary entries are a wave's work each
-#define SMALL_OPS_CASE(VAR) hipLaunchKernelGGL((small_ops_kernel<VAR>), dim3(1), dim3(threads), 0, g_stream, *L, A);
-  switch (variant) {
-    case HPGMG_HIP_27PT_CC:          SMALL_OPS_CASE(HPGMG_HIP_27PT_CC) break;
-    case HPGMG_HIP_FV4_VC_HELMHOLTZ: SMALL_OPS_CASE(HPGMG_HIP_FV4_VC_HELMHOLTZ) break;
-    case HPGMG_HIP_FV4_VC_POISSON:   SMALL_OPS_CASE(HPGMG_HIP_FV4_VC_POISSON) break;
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ: SMALL_OPS_CASE(HPGMG_HIP_7PT_VC_HELMHOLTZ) break;
-    case HPGMG_HIP_7PT_VC_POISSON:   SMALL_OPS_CASE(HPGMG_HIP_7PT_VC_POISSON) break;
-    case HPGMG_HIP_7PT_CC:           SMALL_OPS_CASE(HPGMG_HIP_7PT_CC) break;
-    default: return record_error(hipErrorInvalidValue, "small_ops: variant");
-  }
-#undef SMALL_OPS_CASE
+  int e = 0;
+  if (!with_variant(kAllVariants, variant, &e, [&](auto v) { hipLaunchKernelGGL((small_ops_kernel<v>), dim3(1), dim3(threads), 0, g_stream, *L, A); return 0; }))
+    return record_error(hipErrorInvalidValue, "small_ops: variant");
   g_small_ops_launches++;
   HPGMG_LAUNCH_CHECK("small_ops_kernel");
   return wants ? scalar_wait(A.t, value_out, value2_out) : 0;
 }
 // V-cycle tail below a level of one box (small_vtail_kernel).  The argument block lives in device memory: it is the same for every visit of
 // a chain in a solve, so a few of them are kept and uploaded only when their contents change.
-long long hpgmg_hip_small_vtail_lds_limit(void) { return 150 * 1024 / (long long)sizeof(double); }
+long long hpgmg_hip_small_vtail_lds_limit(void) { return (long long)(kSmallLdsMax / sizeof(double)); }
 long long hpgmg_hip_small_vtail_lds_doubles(const hpgmg_hip_small_tail_args *T) {
   long long need = 0;
   for (int l = 0; l + 1 < T->n; l++) { const long long v = 8LL * T->lv[l].L.volume + T->lv[l + 1].L.volume; if (v > need) need = v; }
@@ -791,18 +768,12 @@ int hpgmg_hip_small_vtail(const hpgmg_hip_small_tail_args *T, int variant) {
 #ifdef HPGMG_EXP_TIMELINE
   tl = (unsigned long long *)g_exp_timeline;
 #endif
-#define VTAIL_CASE(VAR) { \
-    static bool once = false; if (!once) { HPGMG_CHECK(hipFuncSetAttribute((const void *)small_vtail_kernel<VAR>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); once = true; } \
-    hipLaunchKernelGGL((small_vtail_kernel<VAR>), dim3(1), dim3(512), lds, g_stream, (const hpgmg_hip_small_tail_args *)dev_copy[slot], tl); }
-  switch (variant) {
-    case HPGMG_HIP_27PT_CC:          VTAIL_CASE(HPGMG_HIP_27PT_CC) break;
-    case HPGMG_HIP_FV4_VC_HELMHOLTZ: VTAIL_CASE(HPGMG_HIP_FV4_VC_HELMHOLTZ) break;
-    case HPGMG_HIP_FV4_VC_POISSON:   VTAIL_CASE(HPGMG_HIP_FV4_VC_POISSON) break;
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ: VTAIL_CASE(HPGMG_HIP_7PT_VC_HELMHOLTZ) break;
-    case HPGMG_HIP_7PT_VC_POISSON:   VTAIL_CASE(HPGMG_HIP_7PT_VC_POISSON) break;
-    default: return record_error(hipErrorInvalidValue, "small_vtail: variant");
-  }
-#undef VTAIL_CASE
+  // (HPGMG_HIP_7PT_CC is in the lists of the three launchers above and not in this one: small_vtail_kernel has never had that instance)
+  constexpr variant_list<HPGMG_HIP_27PT_CC, HPGMG_HIP_FV4_VC_HELMHOLTZ, HPGMG_HIP_FV4_VC_POISSON, HPGMG_HIP_7PT_VC_HELMHOLTZ, HPGMG_HIP_7PT_VC_POISSON> kVtailVariants{};
+  int e = 0;
+  if (!with_variant(kVtailVariants, variant, &e, [&](auto v) { return launch_lds<small_vtail_kernel<v>>(kSmallLdsMax, dim3(1), dim3(512), lds, (const hpgmg_hip_small_tail_args *)dev_copy[slot], tl); }))
+    return record_error(hipErrorInvalidValue, "small_vtail: variant");
+  if (e) return e;
   g_small_vtail_launches++;
   HPGMG_LAUNCH_CHECK("small_vtail_kernel");
   return 0;

@@ -1,7 +1,7 @@
 // stencil27_tile.hpp -- the 27-point constant-coefficient operator (reference operators.27pt.c:48-51,60-91) as an LDS-staged,
 // k-marching kernel for boxes whose side is a multiple of 64 (TI = 64) or of 32 (TI = 32: a wave is two rows of a 32 x TJ tile).
 //
-// stencil27_kernel (stencil.hip) keeps the three 3 x 3 planes around a cell in registers and re-reads 9 values per step through
+// stencil27_kernel (stencil_untiled.hpp) keeps the three 3 x 3 planes around a cell in registers and re-reads 9 values per step through
 // the vector L1: 72 B of L1 traffic per cell and step, which bounds it (8.8 TB/s of L1 traffic at 1.10 ms per coloured half sweep of
 // 512^3).  Here a 64 x TJ workgroup owns a 64 (i) x TJ (j) tile of a box and marches in +k with planes k-1, k, k+1 of x in LDS
 // (ring of three (TJ+2) x 66 tiles): a lane stores its own value (loaded one step earlier into a register) and at most one halo

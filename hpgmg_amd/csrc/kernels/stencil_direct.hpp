@@ -1,7 +1,8 @@
-// stencil_direct.hpp -- what the translation units of the stencil launchers share (stencil.hip, pair.hip, small_levels.hip): the operating
-// modes and argument records of the single-sweep kernels, the per-cell "direct" form of apply_op_ijk for every operator (pointer types are
-// template parameters, so the single-workgroup kernels can run it on LDS images), the 3 x 3 plane helpers of the 27-point operator, and
-// the launch-profiling hooks.  Reference: operators.7pt.c:49-89, operators.27pt.c:60-91, operators.fv4.c:55-134.
+// stencil_direct.hpp -- what the translation units of the stencil launchers share (stencil.hip and its kernel headers stencil7.hpp, stencil7_wide.hpp,
+// stencil_untiled.hpp; pair.hip, small_levels.hip, fv4_rb.hip, brick_wide.hip): the operating modes and argument records of the single-sweep
+// kernels, the per-cell "direct" form of apply_op_ijk for every operator (pointer types are template parameters, so the single-workgroup
+// kernels can run it on LDS images), the 3 x 3 plane helpers of the 27-point operator, and the one declaration of the launch-profiling
+// hooks (profile.hip).  Reference: operators.7pt.c:49-89, operators.27pt.c:60-91, operators.fv4.c:55-134.
 #pragma once
 #include <stdlib.h>
 #include <cstring>
@@ -63,7 +64,7 @@ __device__ __forceinline__ double fold_coarse(const InterpFold &F, int box, int 
 template <bool kMayAlias> struct src_ptr { typedef const double *__restrict__ type; };
 template <> struct src_ptr<true> { typedef const double *type; };
 
-int  profile_begin(long long cells);          // stencil.hip: hipEvent pair around a smoother launch (bench.py's roofline)
+int  profile_begin(long long cells);          // profile.hip: hipEvent pair around a smoother launch (bench.py's roofline)
 void profile_end(int p, long long cells, bool first_part = false);
 #ifdef HPGMG_EXP_TIMELINE
 extern double *g_exp_timeline;     // experiment build: where a kernel's chosen workgroup records its step timeline (pair.hip)

@@ -19,6 +19,7 @@
 // Ghost handling is the ghost-free form (neighbour box / Dirichlet -x, see stencil.hip), which
 // requires every face neighbour to be local: the host only uses this kernel then.
 #include "reduce.hpp"
+#include "launch_dispatch.hpp"
 #include "stencil_math.hpp"
 #include "dense_levels.hpp"
 
@@ -589,24 +590,15 @@ int hpgmg_hip_vcycle_tail(int n, const hpgmg_hip_level *const *levels, const dou
     if (q > (int)sizeof(A.ops)) return record_error(hipErrorInvalidValue, "vcycle_tail: F-cycle sequence too long");
     A.nops = q;
   }
-#define TAIL_CASE(V, SM) do { if (leg == 4) { if (cpl == 1) hipLaunchKernelGGL((ftail_kernel<V, SM, 1>), dim3(1), dim3(kTailThreadsSmall), 0, g_stream, A); \
-                                              else hipLaunchKernelGGL((ftail_kernel<V, SM, kCellsPerLane>), dim3(1), dim3(kTailThreads), 0, g_stream, A); } \
-                              else { if (cpl == 1) hipLaunchKernelGGL((tail_kernel<V, SM, 1>), dim3(1), dim3(kTailThreadsSmall), 0, g_stream, A); \
-                                     else hipLaunchKernelGGL((tail_kernel<V, SM, kCellsPerLane>), dim3(1), dim3(kTailThreads), 0, g_stream, A); } } while (0)
-  const int key = variant * 3 + smoother;
-  switch (key) {
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ * 3 + SM_CHEBY:  TAIL_CASE(HPGMG_HIP_7PT_VC_HELMHOLTZ, SM_CHEBY); break;
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ * 3 + SM_GSRB:   TAIL_CASE(HPGMG_HIP_7PT_VC_HELMHOLTZ, SM_GSRB); break;
-    case HPGMG_HIP_7PT_VC_HELMHOLTZ * 3 + SM_JACOBI: TAIL_CASE(HPGMG_HIP_7PT_VC_HELMHOLTZ, SM_JACOBI); break;
-    case HPGMG_HIP_7PT_VC_POISSON * 3 + SM_CHEBY:    TAIL_CASE(HPGMG_HIP_7PT_VC_POISSON, SM_CHEBY); break;
-    case HPGMG_HIP_7PT_VC_POISSON * 3 + SM_GSRB:     TAIL_CASE(HPGMG_HIP_7PT_VC_POISSON, SM_GSRB); break;
-    case HPGMG_HIP_7PT_VC_POISSON * 3 + SM_JACOBI:   TAIL_CASE(HPGMG_HIP_7PT_VC_POISSON, SM_JACOBI); break;
-    case HPGMG_HIP_7PT_CC * 3 + SM_CHEBY:            TAIL_CASE(HPGMG_HIP_7PT_CC, SM_CHEBY); break;
-    case HPGMG_HIP_7PT_CC * 3 + SM_GSRB:             TAIL_CASE(HPGMG_HIP_7PT_CC, SM_GSRB); break;
-    case HPGMG_HIP_7PT_CC * 3 + SM_JACOBI:           TAIL_CASE(HPGMG_HIP_7PT_CC, SM_JACOBI); break;
-    default: return record_error(hipErrorInvalidValue, "vcycle_tail: variant/smoother");
-  }
-#undef TAIL_CASE
+  static_assert(SM_CHEBY == 0 && SM_GSRB == 1 && SM_JACOBI == 2, "k7ptSmootherKeys decodes key % 3 as an SM_* smoother");
+  int e = 0;
+  if (!with_variant(k7ptSmootherKeys, variant * 3 + smoother, &e, [&](auto key) {
+        constexpr int V = key / 3, SM = key % 3;
+        if (leg == 4) { if (cpl == 1) hipLaunchKernelGGL((ftail_kernel<V, SM, 1>), dim3(1), dim3(kTailThreadsSmall), 0, g_stream, A);
+                        else hipLaunchKernelGGL((ftail_kernel<V, SM, kCellsPerLane>), dim3(1), dim3(kTailThreads), 0, g_stream, A); }
+        else { if (cpl == 1) hipLaunchKernelGGL((tail_kernel<V, SM, 1>), dim3(1), dim3(kTailThreadsSmall), 0, g_stream, A);
+               else hipLaunchKernelGGL((tail_kernel<V, SM, kCellsPerLane>), dim3(1), dim3(kTailThreads), 0, g_stream, A); }
+        return 0; })) return record_error(hipErrorInvalidValue, "vcycle_tail: variant/smoother");
   HPGMG_LAUNCH_CHECK("tail_kernel");
   return 0;
 }

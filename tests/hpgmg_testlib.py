@@ -206,4 +206,12 @@ VARIANTS = {
     "fv4-gsrb-helm": dict(op=H.OP_FV4, smoother=H.SMOOTH_GSRB, helmholtz=1, variable_coeff=1),
     "fv4-cheby": dict(op=H.OP_FV4, smoother=H.SMOOTH_CHEBY, helmholtz=0, variable_coeff=1),
     "fv2-cheby": dict(op=H.OP_FV2, smoother=H.SMOOTH_CHEBY, helmholtz=0, variable_coeff=1),
+    # configurations without a reference golden file: compared with the oracle (tests/test_gpu_fcycle_parity.py, the kernel instances no other entry selects)
+    "7pt-gsrb-helm": dict(op=H.OP_7PT, smoother=H.SMOOTH_GSRB, helmholtz=1, variable_coeff=1),
+    "7pt-jacobi-helm": dict(op=H.OP_7PT, smoother=H.SMOOTH_JACOBI, helmholtz=1, variable_coeff=1),
+    "7ptcc-gsrb": dict(op=H.OP_7PT, smoother=H.SMOOTH_GSRB, helmholtz=0, variable_coeff=0),
+    "7ptcc-jacobi": dict(op=H.OP_7PT, smoother=H.SMOOTH_JACOBI, helmholtz=0, variable_coeff=0),
+    "fv4-cheby-helm": dict(op=H.OP_FV4, smoother=H.SMOOTH_CHEBY, helmholtz=1, variable_coeff=1),
+    "fv2-cheby-helm": dict(op=H.OP_FV2, smoother=H.SMOOTH_CHEBY, helmholtz=1, variable_coeff=1),
+    "fv2cc-cheby": dict(op=H.OP_FV2, smoother=H.SMOOTH_CHEBY, helmholtz=0, variable_coeff=0),
 }

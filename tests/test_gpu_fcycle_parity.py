@@ -191,7 +191,8 @@ def test_vcycle_tail_below_a_one_box_level_is_one_launch_and_gives_the_same_norm
         hip.lib.hpgmg_set_brick_wide(1)
 
 
-@pytest.mark.parametrize("variant,args", [("7pt-cheby", "4 8"), ("7pt-gsrb", "5 8"), ("fv4-gsrb", "4 8"), ("27pt-cheby", "5 8"), ("fv2-cheby", "4 8")])
+@pytest.mark.parametrize("variant,args", [("7pt-cheby", "4 8"), ("7pt-gsrb", "5 8"), ("fv4-gsrb", "4 8"), ("27pt-cheby", "5 8"), ("fv2-cheby", "4 8"),
+                                          ("7pt-cheby-helm", "5 8"), ("7ptcc-cheby", "5 8")])      # small_ops_kernel's Helmholtz and constant-coefficient 7-point instances
 def test_host_driven_bottom_solve_through_the_small_operator_queue(hip, variant, args):
     """The bottom solve driven from the host (hpgmg_set_fused_bottom(0): host/solvers.c BiCGStab calling mul_vectors, apply_op, dot, add_vectors,
     norm ... as the reference's solvers/bicgstab.c does through operators.h).  On a level of one small box the void operators wait for the dot product
@@ -254,6 +255,68 @@ def test_hip_equals_oracle_live(hip, oracle):
             assert np.array_equal(lh.interior(vid), lo.interior(vid)), vid
     finally:
         sh.destroy(); so.destroy()
+
+
+# Kernel instances that no configuration with a golden file selects (profiles/r15a_dispatch_coverage.txt), each at the smallest F-cycle that reaches it.
+# switches: plugin setters moved off their default for the run (name without hpgmg_set_, value), put back afterwards.
+ORACLE_ONLY = {
+    # 64^3 in boxes of 32^3: the 64^3 .. 16^3 levels are brick launches (brick_chain_kernel), the levels below the 7-point tail (tail_kernel, ftail_kernel)
+    "7pt-gsrb-helm": ("7pt-gsrb-helm", "5 8", {}),
+    "7pt-jacobi-helm": ("7pt-jacobi-helm", "5 8", {}),
+    "7ptcc-gsrb": ("7ptcc-gsrb", "5 8", {}),
+    "7ptcc-jacobi": ("7ptcc-jacobi", "5 8", {}),
+    # 32^3 in boxes of 16^3, fv4 Helmholtz: brick_wide_kernel (GSRB, Chebyshev) with bottom_bicgstab_kernel below; without bricks small_level_kernel and
+    # small_vtail_kernel; without the tail launch small_level_kernel and bottom_bicgstab_kernel on their own; the host-driven bottom solve: small_ops_kernel
+    "fv4-gsrb-helm": ("fv4-gsrb-helm", "4 8", {}),
+    "fv4-cheby-helm": ("fv4-cheby-helm", "4 8", {}),
+    "fv4-gsrb-helm-no-bricks": ("fv4-gsrb-helm", "4 8", {"brick_wide": 0}),
+    "fv4-gsrb-helm-no-bricks-no-tail": ("fv4-gsrb-helm", "4 8", {"brick_wide": 0, "small_vtail": 0}),
+    "fv4-gsrb-helm-host-bottom": ("fv4-gsrb-helm", "4 8", {"fused_bottom": 0}),
+    # the fv2 plugin runs the 7-point kernels' direct and single-workgroup forms: its Helmholtz and constant-coefficient configurations select their
+    # 7PT_VC_HELMHOLTZ / 7PT_CC instances (stencil_direct_kernel's black-box probe, small_level_kernel, small_vtail_kernel, bottom_bicgstab_kernel, small_ops_kernel).
+    # small_vtail_kernel has no 7PT_CC instance and the plugin does not ask before it launches the tail: constant coefficients run with the tail launch off.
+    "fv2-cheby-helm": ("fv2-cheby-helm", "4 8", {}),
+    "fv2-cheby-helm-no-tail": ("fv2-cheby-helm", "4 8", {"small_vtail": 0}),
+    "fv2-cheby-helm-host-bottom": ("fv2-cheby-helm", "4 8", {"fused_bottom": 0}),
+    "fv2cc-cheby-no-tail": ("fv2cc-cheby", "4 8", {"small_vtail": 0}),
+    "fv2cc-cheby-host-bottom": ("fv2cc-cheby", "4 8", {"small_vtail": 0, "fused_bottom": 0}),
+}
+SWITCH_DEFAULT = {"brick_wide": 1, "small_vtail": 2, "fused_bottom": 1}
+_oracle_fcycles = {}
+
+
+def oracle_fcycle(oracle, variant, args):
+    """The oracle's norms of one configuration, computed once for the cases that share it."""
+    if (variant, args) not in _oracle_fcycles:
+        oracle.configure(**VARIANTS[variant])
+        so = oracle.solver_cli(*map(int, args.split()))
+        try:
+            _oracle_fcycles[variant, args] = (so.three_sizes(), so.richardson())
+        finally:
+            so.destroy()
+    return _oracle_fcycles[variant, args]
+
+
+@pytest.mark.parametrize("case", list(ORACLE_ONLY))
+def test_hip_fcycle_equals_the_oracle_where_no_golden_file_exists(hip, oracle, case):
+    """The same three F-cycles and the Richardson error on both builds of the host layer, compared as doubles."""
+    import ctypes
+    variant, args, switches = ORACLE_ONLY[case]
+    want = oracle_fcycle(oracle, variant, args)
+    for name, value in switches.items():
+        setter = getattr(hip.lib, "hpgmg_set_" + name)
+        setter.argtypes = [ctypes.c_int]
+        setter(value)
+    try:
+        hip.configure(**VARIANTS[variant])
+        sh = hip.solver_cli(*map(int, args.split()))
+        try:
+            assert (sh.three_sizes(), sh.richardson()) == want
+        finally:
+            sh.destroy()
+    finally:
+        for name in switches:
+            getattr(hip.lib, "hpgmg_set_" + name)(SWITCH_DEFAULT[name])
 
 
 @pytest.mark.parametrize("variant,args", [("7pt-cheby-helm", "8 8"), ("7pt-cheby", "8 8"), ("27pt-gsrb", "7 8"), ("27pt-gsrb", "7 64"), ("fv4-gsrb", "7 64")])

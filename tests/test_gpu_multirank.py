@@ -22,6 +22,7 @@ GOLD = load_golden("fcycle_norms.json")
     (2, "7pt-cheby-helm", 4, 4, "7pt-cheby-helm 4 8"),
     (2, "7pt-gsrb", 4, 4, "7pt-gsrb 4 8"),
     (4, "7pt-cheby", 4, 2, "7pt-cheby 4 8"),
+    (2, "7ptcc-cheby", 4, 4, "7ptcc-cheby 4 8"),        # the constant-coefficient instance of the shell launches (stencil7_shell_kernel)
     (2, "7pt-cheby-helm", 7, 4, "7pt-cheby-helm 7 8"),    # bench.py --gpus 2 at full size: 2 x 4 boxes of 128^3 (wide kernel + shell launches)
     (4, "7pt-cheby", 4, 8, "7pt-cheby 4 27"),          # bench.py --gpus 4 in small: 27 boxes over 4 ranks (7/7/7/6), 48^3
     (2, "27pt-cheby", 4, 4, "27pt-cheby 4 8"),

@@ -206,7 +206,8 @@ def test_interpolation_folded_into_the_first_sweep_pair(hip, oracle, variant, ge
 
 
 @pytest.mark.parametrize("variant,geom", [("7pt-cheby-helm", (2, 64)), ("7pt-cheby-helm", (2, 32)), ("7pt-cheby", (2, 16)), ("7ptcc-cheby", (3, 16)), ("7pt-cheby-helm", (1, 64)),
-                                          ("7pt-cheby", (4, 8)), ("7pt-cheby-helm", (2, 2)), ("7pt-cheby", (1, 32))])
+                                          ("7pt-cheby", (4, 8)), ("7pt-cheby-helm", (2, 2)), ("7pt-cheby", (1, 32)),
+                                          ("7pt-cheby", (2, 64)), ("7ptcc-cheby", (1, 64))])      # the other two variants of the tile kernel's fold
 def test_interpolation_folded_into_single_chebyshev_sweeps(hip, oracle, variant, geom):
     """The same hook on the levels the sweep-pair kernel does not take (config 2's 128^3 ... 32^3 levels): sweep 0 reads x_n and sweep 1 reads x_{n-1} as stored +
     the coarse value above the cell (InterpFold: the LDS-tiled kernel for boxes of 64^3, the plain one below), interpolation_vcycle is no launch of its own.
@@ -707,7 +708,8 @@ def test_higher_order_boundary_conditions(hip, oracle, variant, geom, bc, shape)
 
 @pytest.mark.parametrize("ghost_free", [1, 0])
 @pytest.mark.parametrize("variant,geom", [("fv4-gsrb", (2, 64)), ("27pt-gsrb", (2, 64)), ("fv4-cheby", (1, 64)), ("27pt-cheby", (3, 64)), ("fv4-gsrb", (4, 32)), ("fv4-cheby", (1, 32)), ("27pt-gsrb", (4, 32)), ("27pt-cheby", (2, 32)),
-                                          ("fv4-gsrb", (2, 64, "periodic")), ("27pt-gsrb", (1, 64, "periodic")), ("fv4-gsrb", (3, 32, "periodic"))])
+                                          ("fv4-gsrb", (2, 64, "periodic")), ("27pt-gsrb", (1, 64, "periodic")), ("fv4-gsrb", (3, 32, "periodic")),
+                                          ("fv4-gsrb-helm", (2, 64)), ("fv4-gsrb-helm", (2, 32))])      # the Helmholtz instances of fv4_tile_kernel, both tile shapes
 def test_lds_tiled_kernels_of_the_27pt_and_fv4_plugins(hip, oracle, variant, geom, ghost_free):
     """Boxes of 64^3 and more (32^3 in narrower tiles) run the LDS-tiled kernels (fv4_tile.hpp, stencil27_tile.hpp): smooth, residual and apply_op against the
     oracle, bit for bit.  ghost_free=1 (default): x outside a box is read from the neighbouring box, only apply_BCs runs before a
@@ -805,7 +807,8 @@ def test_fv4_red_and_black_half_sweeps_in_one_pass(hip, oracle, variant, geom):
 
 
 @pytest.mark.parametrize("variant,geom", [("27pt-cheby", (2, 8)), ("27pt-gsrb", (1, 4)), ("fv4-gsrb", (2, 8)), ("fv4-gsrb", (2, 16)), ("fv4-cheby", (1, 8)),
-                                           ("fv2-cheby", (2, 8)), ("fv4-gsrb", (1, 2)), ("27pt-cheby", (1, 2)), ("fv4-gsrb", (2, 32))])
+                                           ("fv2-cheby", (2, 8)), ("fv4-gsrb", (1, 2)), ("27pt-cheby", (1, 2)), ("fv4-gsrb", (2, 32)),
+                                           ("fv4-gsrb-helm", (2, 8))])      # the Helmholtz instance of stencil_direct_kernel
 def test_other_plugins_operator_by_operator(hip, oracle, variant, geom):
     """27pt / fv2 / fv4: black-box rebuild (with extrapolate_betas for fv4), smooth, residual, and the tensor-product
     interpolations, compared over whole padded boxes (so with the reference's exchange + BCs before every stencil launch: the default

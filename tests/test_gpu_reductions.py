@@ -1,5 +1,5 @@
 """BLAS-1 and every reduction that returns a maximum or an ordered sum, held to the CPU oracle at the edges of their launch shape (kernels/blas1.hip,
-kernels/reduce.hip final_max_kernel and the result slot, kernels/pcg.hip pcg_update_kernel, the fused residual + norm of kernels/stencil.hip, stencil27_tile.hpp and fv4_tile.hpp).  Every
+kernels/reduce.hip final_max_kernel and the result slot, kernels/pcg.hip pcg_update_kernel, the fused residual + norm of kernels/stencil7_wide.hpp (launched from kernels/stencil.hip), stencil27_tile.hpp and fv4_tile.hpp).  Every
 comparison is bitwise: all builds have -ffp-contract=off, a maximum is exact in any order and the sums have one order (misc.c:261-269).  The NumPy
 restatements and the launch arithmetic are tests/reduction_lib.py's, pinned on the CPU by tests/test_oracle_reductions.py; every test asserts the path
 it claims against those plans.

@@ -1,5 +1,5 @@
 """Uniform alpha (HPGMG_UNIFORM_ALPHA / hpgmg_set_uniform_alpha): where rebuild_operator finds VECTOR_ALPHA to be ONE bit pattern over every interior cell of the
-level, the sweep pairs that form Dinv (kernels/cheby_pair.hpp, UA instances) and the two wide fused residual passes (kernels/stencil.hip) take alpha from their arguments
+level, the sweep pairs that form Dinv (kernels/cheby_pair.hpp, UA instances) and the two wide fused residual passes (kernels/stencil7_wide.hpp, launched from kernels/stencil.hip) take alpha from their arguments
 instead of streaming the vector.  The vector is the contract: whichever instance runs, the bits are those of the oracle, which always reads it.  Every comparison here is
 bit for bit; hpgmg_uniform_alpha_launches() says which instance ran.  The uniform value is 0.7, not 1.0: a kernel that dropped the term or assumed 1.0 fails.
 
