@@ -94,6 +94,7 @@ def _declare_driver_api(lib):
         "hpgmg_level_set_eigenvalue": (None, [vp, c_dbl]),
         "hpgmg_level_box_low": (None, [vp, c_int, P(c_int)]),
         "hpgmg_level_list_counts": (c_int, [vp, c_int, c_int, P(c_int)]),
+        "hpgmg_level_list_entry": (c_int, [vp, c_int, c_int, c_int, c_int, P(c_int)]),
         "hpgmg_level_read_vector": (None, [vp, c_int, c_int, vp]),
         "hpgmg_level_write_vector": (None, [vp, c_int, c_int, vp]),
         "hpgmg_level_create": (vp, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl]),

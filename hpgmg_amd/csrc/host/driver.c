@@ -302,6 +302,25 @@ int hpgmg_level_list_counts(const level_type *L, int which, int idx, int out[3])
   out[0] = C->num_blocks[0]; out[1] = C->num_blocks[1]; out[2] = C->num_blocks[2];
   return C->num_sends + C->num_recvs;
 }
+int hpgmg_level_list_entry(const level_type *L, int which, int idx, int phase, int n, int out[11]) {
+  const blockCopy_type *e = NULL;
+  if (n < 0) return -1;
+  if (which == 3) {
+    if (idx < 0 || idx >= STENCIL_MAX_SHAPES || n >= L->boundary_condition.num_blocks[idx]) return -1;
+    e = &L->boundary_condition.blocks[idx][n];
+  } else {
+    const communicator_type *C = NULL;
+    if (which == 0 && idx >= 0 && idx < STENCIL_MAX_SHAPES) C = &L->exchange_ghosts[idx];
+    else if (which == 1 && idx >= 0 && idx < 4) C = &L->restriction[idx];
+    else if (which == 2) C = &L->interpolation;
+    if (!C || phase < 0 || phase > 2 || n >= C->num_blocks[phase]) return -1;
+    e = &C->blocks[phase][n];
+  }
+  out[0] = e->dim.i; out[1] = e->dim.j; out[2] = e->dim.k;
+  out[3] = e->read.box; out[4] = e->read.i; out[5] = e->read.j; out[6] = e->read.k;
+  out[7] = e->write.box; out[8] = e->write.i; out[9] = e->write.j; out[10] = e->write.k;
+  return 0;
+}
 void hpgmg_level_read_vector(level_type *L, int box, int id, double *host_out) {
   hpgmg_vector_download(host_out, L->my_boxes[box].vectors[id], (size_t)L->box_volume);
 }

@@ -306,8 +306,9 @@ void interpolation_fcycle(level_type *Lf, int id_f, double prescale, level_type 
     return;
   }
   if (c.op != HPGMG_OP_7PT) hp_no_kernel("interpolation_fcycle for this operator");
-  /* ghost-free form (interpolation_p1.c:71-72 without its two launches): every coarse box local, Dirichlet, box-to-box entries only -- the kernel reads a
-   * coarse neighbour where it lives and applies apply_BCs_p1's rule in registers, as the 7-point stencils do (HPGMG_GHOST_FREE=0: the three-step form) */
+  /* interpolation_p1.c:71-72: the coarse operand's ghost zones are filled first -- exchange_boundary + apply_BCs_p1 as ONE launch where the level qualifies
+   * (hp_exchange_and_bcs_one_launch: ghost-free mode, no messages, Dirichlet, every condition's sources local), otherwise the two operators (HPGMG_GHOST_FREE=0
+   * always).  The interpolation kernel then reads every coarse neighbour from the ghost zone, as the reference does */
   if (!hp_exchange_and_bcs_one_launch(Lc, id_c, STENCIL_SHAPE_BOX, 1, 1)) { exchange_boundary(Lc, id_c, STENCIL_SHAPE_BOX); apply_BCs_p1(Lc, id_c, STENCIL_SHAPE_BOX); }
   interpolation_lists(Lf, id_f, prescale, Lc, id_c, 1, 0x7);
 }

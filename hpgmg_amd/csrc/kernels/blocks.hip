@@ -166,7 +166,11 @@ __global__ __launch_bounds__(256) void interp_tensor_kernel(const hpgmg_hip_leve
             // follows old's -- the old value is fetched only for results that are zeros
             if (prescale != 0.0) load_fine();
             double v0 = prescale * f0 + a0, v1 = prescale * f1 + a1;
-            if (!ZEROED && prescale == 0.0 && (v0 == 0.0 || v1 == 0.0)) { load_fine(); v0 = prescale * f0 + a0; v1 = prescale * f1 + a1; }
+            if (!ZEROED && prescale == 0.0 && (v0 == 0.0 || v1 == 0.0)) {      // (only the zero of a pair is formed again: its partner keeps dropping a non-finite old value)
+              load_fine();
+              if (v0 == 0.0) v0 = prescale * f0 + a0;
+              if (v1 == 0.0) v1 = prescale * f1 + a1;
+            }
             if (pairs) store_pair<NT>(fw, v0, v1);
             else { fw[0] = v0; fw[1] = v1; }
           }
@@ -205,8 +209,8 @@ __global__ __launch_bounds__(256) void restrict_blocks_kernel(const hpgmg_hip_le
   restrict_entry<TYPE>(Lc, id_c, Lf, id_f, list[blockIdx.x]);
 }
 // restriction of a list + zero_vector(coarse, zero_id) in one launch (the down-leg of MGVCycle does both, mg.c:1152-1153):
-// workgroups [0, n) take the list entries, the rest clear the coarse vector -- whole padded boxes, ghosts included
-// (misc.c:6-44; the alignment padding between rows is never read and already zero, so each box is one contiguous run)
+// workgroups [0, n) take the list entries, the rest clear the coarse vector -- interior and ghost cells, as zero_vector does (misc.c:6-44);
+// each walks a run of 4096 doubles of a box and leaves out the alignment padding, which zero_vector does not touch either
 __global__ __launch_bounds__(256) void restrict_cell_zero_kernel(const hpgmg_hip_level Lc, int id_c, const hpgmg_hip_level Lf, int id_f,
                                                                  const blockCopy_type *__restrict__ list, int n, int zero_id, int chunks_per_box) {
   if ((int)blockIdx.x < n) { restrict_entry<RESTRICT_CELL>(Lc, id_c, Lf, id_f, list[blockIdx.x]); return; }
@@ -214,7 +218,11 @@ __global__ __launch_bounds__(256) void restrict_cell_zero_kernel(const hpgmg_hip
   if (box >= Lc.num_boxes) return;
   double *v = Lc.box_base[box] + (size_t)zero_id * (size_t)Lc.volume;
   const int lo = chunk * 4096, hi = (lo + 4096 < Lc.volume) ? lo + 4096 : Lc.volume;
-  for (int t = lo + (int)threadIdx.x; t < hi; t += 256) v[t] = 0.0;
+  const int w = Lc.dim + 2 * Lc.ghosts, jS = Lc.jStride, kS = Lc.kStride;
+  for (int t = lo + (int)threadIdx.x; t < hi; t += 256) {
+    const int k = t / kS, r = t - k * kS, j = r / jS;
+    if (k < w && j < w && r - j * jS < w) v[t] = 0.0;
+  }
 }
 
 // interpolation_p0.c:43 (ORDER 0, piecewise constant) and interpolation_p1.c:40-70 (ORDER 1, trilinear).
@@ -279,7 +287,12 @@ __global__ __launch_bounds__(256) void interp_blocks_kernel(const hpgmg_hip_leve
           double f0 = 0.0, f1 = 0.0;
           if (prescale != 0.0) load_fine(f0, f1);
           blend(f0, f1);
-          if (!ZEROED && prescale == 0.0 && (v[0] == 0.0 || v[1] == 0.0)) { load_fine(f0, f1); blend(f0, f1); }
+          if (!ZEROED && prescale == 0.0 && (v[0] == 0.0 || v[1] == 0.0)) {      // (only the zero of a pair is formed again: its partner keeps dropping a non-finite old value)
+            const double k0 = v[0], k1 = v[1];
+            load_fine(f0, f1); blend(f0, f1);
+            if (k0 != 0.0) v[0] = k0;
+            if (k1 != 0.0) v[1] = k1;
+          }
           if (pairs) store_pair<NT>(fw, v[0], v[1]);
           else { fw[0] = v[0]; fw[1] = v[1]; }
         }

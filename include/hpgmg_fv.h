@@ -181,6 +181,9 @@ int    hpgmg_level_must_subtract_mean(const level_type *level);      /* 1: the c
 void   hpgmg_level_set_eigenvalue(level_type *level, double dominant_eigenvalue_of_DinvA);   /* what rebuild_operator would have left (tests of a Chebyshev smoother on given coefficients) */
 void   hpgmg_level_box_low(const level_type *level, int box, int out[3]);
 int    hpgmg_level_list_counts(const level_type *level, int which, int shape_or_type, int out[3]);
+/* entry n of phase 0 / 1 / 2 of the same list (which 3: the boundary list, phase ignored): out = dim.i, dim.j, dim.k, read.box, read.i, read.j, read.k,
+ * write.box, write.i, write.j, write.k.  Returns 0, or -1 where there is no such entry (out untouched) */
+int    hpgmg_level_list_entry(const level_type *level, int which, int shape_or_type, int phase, int n, int out[11]);
 /* whole padded box volume of one vector <-> host array of box_volume doubles */
 void   hpgmg_level_read_vector(level_type *level, int box, int id, double *host_out);
 void   hpgmg_level_write_vector(level_type *level, int box, int id, const double *host_in);
