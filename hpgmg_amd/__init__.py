@@ -53,6 +53,7 @@ WHERE_HOST, WHERE_PLUGIN = 0, 1
  USER_NOT_READY, USER_UNSUPPORTED) = 0, -1, -2, -3, -4, -5, -6, -7
 USER_FMG, USER_MG, USER_PCG, USER_FPCG = 0, 1, 2, 3
 FACE_DIRICHLET, FACE_NEUMANN, FACE_ROBIN = 0, 1, 3
+MEAN_HARMONIC, MEAN_ARITHMETIC = 0, 1      # the face mean of a cell-centred conductivity (HPGMG_MEAN_* of include/hpgmg_operators.h)
 
 
 class HipLevel(ctypes.Structure):
@@ -177,6 +178,11 @@ def _declare_driver_api(lib):
         # coefficient sensitivities
         "hpgmg_user_sensitivity": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_int]),
         "hpgmg_dense_unpack_sensitivity": (c_int, [vp, c_int, c_int, vp, c_dbl, c_dbl, c_int, vp, vp, vp, vp, vp, vp, c_int]),
+        # cell-centred conductivities
+        "hpgmg_user_set_cell_coefficients": (c_int, [vp, vp, vp, c_int, vp, c_int]),
+        "hpgmg_user_cell_sensitivity": (c_int, [vp, vp, vp, vp, c_int, vp, vp, vp, c_int]),
+        "hpgmg_dense_pack_cell_mean": (c_int, [vp, vp, c_int, c_int, c_int, vp]),
+        "hpgmg_dense_unpack_cell_sensitivity": (c_int, [vp, c_int, c_int, vp, c_int, vp, c_dbl, c_dbl, c_int, vp, vp, vp, vp, c_int]),
         # implicit time stepping
         "hpgmg_user_set_shift": (c_int, [vp, c_dbl]),
         "hpgmg_user_start": (c_int, [vp, vp, vp, vp, c_int, c_dbl, c_dbl]),

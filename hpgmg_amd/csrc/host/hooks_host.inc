@@ -1,7 +1,7 @@
 /*
  * hooks_host.inc -- the portable host forms of the dense-array, boundary-value, time-march and CG hooks (include/hpgmg_operators.h hpgmg_dense_*,
  * hpgmg_boundary_*, hpgmg_step_*, hpgmg_pcg_*): box by box through the plugin's hpgmg_vector_upload / download.  They are weak, so that a plugin with kernels
- * for them (the HIP plugin: host/plugin_dense.c, host/plugin_pcg.c; its kernels: kernels/dense_io.hip, dense_boundary.hip, dense_flux.hip, pcg.hip) replaces them while one without (the CPU oracle, whose memory is host memory
+ * for them (the HIP plugin: host/plugin_dense.c, host/plugin_pcg.c; its kernels: kernels/dense_io.hip, dense_boundary.hip, dense_flux.hip, dense_cells.hip, pcg.hip) replaces them while one without (the CPU oracle, whose memory is host memory
  * for either `where`) gets these.  The boundary arithmetic itself is include/hpgmg_boundary_math.h, shared with those kernels.
  * A part of host/driver.c's translation unit, included there.
  */
@@ -397,6 +397,97 @@ __attribute__((weak)) int hpgmg_dense_unpack_sensitivity(level_type *L, int u_id
   }
   free(u); free(gh); free(kh);
   return bad ? HPGMG_DENSE_NOT_FINITE : 0;
+}
+
+/* ------------------------------------------------------------------ cell-centred conductivities (include/hpgmg_operators.h; DESIGN.md §11.10)
+ * The pack IS the face route: the three face arrays of means (include/hpgmg_boundary_math.h bnd_mean; a wall face its cell's own value), then the
+ * existing packs.  The status is formed here, entry by entry and mean by mean: the existing packs' own check of a mean would call the mean of a
+ * negative and a positive cell "not finite". */
+static int cell_mean_refused(const level_type *L, const double *kcell, int where, int mean, int mask, const void *wall) {
+  if (L->num_ranks != 1 || !kcell || L->dim.i != L->dim.j || L->dim.i != L->dim.k) return 1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return 1;
+  if (mean != HPGMG_MEAN_HARMONIC && mean != HPGMG_MEAN_ARITHMETIC) return 1;
+  return mask < 0 || mask > 63 || (mask && (!wall || L->boundary_condition.type != BC_DIRICHLET));
+}
+__attribute__((weak)) int hpgmg_dense_pack_cell_mean(level_type *L, const double *kcell, int where, int mean, int mask, double *wall) {
+  if (cell_mean_refused(L, kcell, where, mean, mask, wall)) return -1;
+  const int n = L->dim.i, walls = L->boundary_condition.type == BC_DIRICHLET, ne = dense_extent(n, walls);
+  const size_t nn = (size_t)n, cells = nn * nn * nn, len = nn * nn * (size_t)ne, ks[3] = { 1, nn, nn * nn };
+  double *face = (double *)malloc(3 * len * sizeof(double));
+  int axis, i, j, k, e, status = 0;
+  size_t at;
+  for (at = 0; at < cells; at++) status |= bnd_cell_bits(kcell[at]);
+  for (axis = 0; axis < 3; axis++) {      /* the array of that axis is one longer along it when the level has walls: (n, n, ne), (n, ne, n), (ne, n, n) */
+    const int ei = axis == 0 ? ne : n, ej = axis == 1 ? ne : n, ek = axis == 2 ? ne : n;
+    double *F = face + axis * len;
+    for (k = 0; k < ek; k++) for (j = 0; j < ej; j++) for (i = 0; i < ei; i++) {
+      const int c = axis == 0 ? i : axis == 1 ? j : k;
+      const size_t hi_at = ((size_t)k * nn + (size_t)j) * nn + (size_t)i;          /* the cell on the face's high side (c == n: there is none) */
+      double *out = F + ((size_t)k * ej + (size_t)j) * ei + (size_t)i;
+      if (walls && c == 0) *out = kcell[hi_at];
+      else if (walls && c == n) *out = kcell[hi_at - ks[axis]];
+      else {
+        const double lo = c ? kcell[hi_at - ks[axis]] : kcell[hi_at + (nn - 1) * ks[axis]], hi = kcell[hi_at], m = bnd_mean(mean, lo, hi);
+        status |= bnd_mean_bits(lo, hi, m);
+        *out = m;
+      }
+    }
+  }
+  for (axis = 0; axis < 3; axis++) {
+    const int id = axis == 0 ? VECTOR_BETA_I : axis == 1 ? VECTOR_BETA_J : VECTOR_BETA_K, layout = HPGMG_DENSE_FACE_I + axis;
+    e = mask ? hpgmg_dense_pack_walls(L, id, face + axis * len, HPGMG_WHERE_HOST, layout, HPGMG_DENSE_CHECK_POSITIVE, mask, wall)
+             : hpgmg_dense_pack(L, id, face + axis * len, HPGMG_WHERE_HOST, layout, HPGMG_DENSE_CHECK_POSITIVE);
+    if (e < 0) { free(face); return -1; }
+  }
+  free(face);
+  return status;
+}
+
+/* D G summed over the six faces of each cell in the written order; G as hpgmg_dense_unpack_sensitivity above forms it */
+__attribute__((weak)) int hpgmg_dense_unpack_cell_sensitivity(level_type *L, int u_id, int lam_id, const double *kcell, int mean, const double *g, double a,
+                                                              double b, int mask, const double *wall, const double *kappa, double *d_alpha, double *d_k,
+                                                              int where) {
+  if (L->num_ranks != 1 || u_id < 0 || u_id >= L->numVectors || lam_id < 0 || lam_id >= L->numVectors || !kcell || !d_k) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  if (mean != HPGMG_MEAN_HARMONIC && mean != HPGMG_MEAN_ARITHMETIC) return -1;
+  if (mask < 0 || mask > 63 || (mask && !wall) || L->dim.i != L->dim.j || L->dim.i != L->dim.k || L->box_ghosts < 1) return -1;
+  const int walls = L->boundary_condition.type == BC_DIRICHLET;
+  if (!walls && (g || mask)) return -1;
+  const int n = L->dim.i, g0 = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t len = (size_t)6 * n * n, vol = (size_t)L->box_volume, nn = (size_t)n;
+  const double w2 = bnd_sens_weight(b, L->h), w = bnd_weight(b, L->h), wn = bnd_weight_neumann(b, L->h), h = L->h;
+  double *gh = g ? bnd_download(g, len) : NULL, *kh = mask && kappa ? bnd_download(kappa, len) : NULL;
+  double *u = (double *)malloc(vol * 2 * sizeof(double)), *lam = u + vol;
+  int box, i, j, k, axis, bad = 0, status = 0;
+  for (box = 0; box < L->num_my_boxes; box++) {
+    const box_type *B = &L->my_boxes[box];
+    hpgmg_vector_download(u, B->vectors[u_id], vol);
+    hpgmg_vector_download(lam, B->vectors[lam_id], vol);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int gc[3] = { B->low.i + i, B->low.j + j, B->low.k + k }, ijk = (i + g0) + (j + g0) * jS + (k + g0) * kS, vs[3] = { 1, jS, kS };
+      const size_t cell = ((size_t)gc[2] * nn + (size_t)gc[1]) * nn + (size_t)gc[0], ks[3] = { 1, nn, nn * nn };
+      const double uc = u[ijk], lc = lam[ijk], kc = kcell[cell];
+      double GD[6];
+      status |= bnd_cell_bits(kc);
+      for (axis = 0; axis < 3; axis++) {
+        if (walls && gc[axis] == 0) GD[2 * axis] = sens_wall_host(2 * axis, bnd_entry(n, 2 * axis, gc[0], gc[1], gc[2]), uc, lc, w, wn, h, mask, gh, kh, &bad);          /* D = 1.0 */
+        else {
+          const double klo = gc[axis] ? kcell[cell - ks[axis]] : kcell[cell + (nn - 1) * ks[axis]];
+          status |= bnd_mean_bits(klo, kc, bnd_mean(mean, klo, kc));          /* each mean once: by the cell on its high side */
+          GD[2 * axis] = bnd_sens_interior(w2, u[ijk - vs[axis]], uc, lam[ijk - vs[axis]], lc) * bnd_mean_dhi(mean, klo, kc);
+        }
+        if (walls && gc[axis] == n - 1) GD[2 * axis + 1] = sens_wall_host(2 * axis + 1, bnd_entry(n, 2 * axis + 1, gc[0], gc[1], gc[2]), uc, lc, w, wn, h, mask, gh, kh, &bad);          /* D = 1.0 */
+        else {
+          const double khi = gc[axis] < n - 1 ? kcell[cell + ks[axis]] : kcell[cell - (nn - 1) * ks[axis]];
+          GD[2 * axis + 1] = bnd_sens_interior(w2, uc, u[ijk + vs[axis]], lc, lam[ijk + vs[axis]]) * bnd_mean_dlo(mean, kc, khi);
+        }
+      }
+      if (d_alpha) d_alpha[cell] = bnd_sens_alpha(a, uc, lc);
+      d_k[cell] = ((((GD[0] + GD[1]) + GD[2]) + GD[3]) + GD[4]) + GD[5];
+    }
+  }
+  free(u); free(gh); free(kh);
+  return status | (bad ? HPGMG_DENSE_NOT_FINITE : 0);
 }
 
 /* ------------------------------------------------------------------ the implicit time march (include/hpgmg_operators.h; DESIGN.md §11.8)

@@ -1,7 +1,7 @@
 /*
  * plugin_dense.c -- hpgmg_dense_pack / hpgmg_dense_unpack / hpgmg_dense_unpack_flux / hpgmg_dense_unpack_sensitivity of the operator plugin
  * (include/hpgmg_operators.h): one launch of kernels/dense_io.hip per array (the three flux arrays: one of kernels/dense_flux.hip; the four
- * sensitivity arrays: one of kernels/dense_sensitivity.hip).  A device array is read / written in place; a host array is copied once into the level's staging buffer
+ * sensitivity arrays: one of kernels/dense_sensitivity.hip; a cell-centred conductivity: kernels/dense_cells.hip).  A device array is read / written in place; a host array is copied once into the level's staging buffer
  * (allocated on first use, freed with the level) and packed from there, or unpacked into it and copied out once.  They replace the weak
  * host defaults of host/hooks_host.inc, which go box by box through hpgmg_vector_upload / download.  The boundary-value hooks below likewise
  * (their arithmetic: include/hpgmg_boundary_math.h, shared with the kernels and the host defaults).
@@ -110,6 +110,42 @@ int hpgmg_dense_unpack_sensitivity(level_type *L, int u_id, int lam_id, const do
   HIP_OK(hpgmg_hip_memcpy_d2h(d_beta_j, stage + len, len * sizeof(double)));
   HIP_OK(hpgmg_hip_memcpy_d2h(d_beta_k, stage + 2 * len, len * sizeof(double)));
   if (d_alpha) HIP_OK(hpgmg_hip_memcpy_d2h(d_alpha, stage + 3 * len, cells * sizeof(double)));
+  return status;
+}
+
+/* cell-centred conductivities: one launch of kernels/dense_cells.hip each.  A host kcell is staged like any pack's array; the
+ * cell sensitivities' host outputs follow it in the staging buffer (3 cells in all: within the 3 len + cells the sensitivities above size it to) */
+int hpgmg_dense_pack_cell_mean(level_type *L, const double *kcell, int where, int mean, int mask, double *wall) {
+  int status = 0;
+  if (L->dim.i != L->dim.j || L->dim.i != L->dim.k || (mean != HPGMG_MEAN_HARMONIC && mean != HPGMG_MEAN_ARITHMETIC)) return -1;
+  if (mask < 0 || mask > 63 || (mask && (!wall || L->boundary_condition.type != BC_DIRICHLET))) return -1;
+  if (!(kcell = dense_source(L, VECTOR_BETA_I, kcell, where, (size_t)L->dim.i * L->dim.j * L->dim.k))) return -1;
+  hp_coef_written(L, VECTOR_BETA_I);      /* and J, K: one record covers the coefficient vectors */
+  HIP_OK(hpgmg_hip_dense_pack_cell_mean(&hp_backend_of(L)->dev, VECTOR_BETA_I, VECTOR_BETA_J, VECTOR_BETA_K, kcell, mean, mask, mask ? wall : NULL, &status));
+  return status;
+}
+
+int hpgmg_dense_unpack_cell_sensitivity(level_type *L, int u_id, int lam_id, const double *kcell, int mean, const double *g, double a, double b, int mask,
+                                        const double *wall, const double *kappa, double *d_alpha, double *d_k, int where) {
+  int status = 0;
+  if (L->num_ranks != 1 || u_id < 0 || u_id >= L->numVectors || lam_id < 0 || lam_id >= L->numVectors || !kcell || !d_k) return -1;
+  if (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return -1;
+  if (mean != HPGMG_MEAN_HARMONIC && mean != HPGMG_MEAN_ARITHMETIC) return -1;
+  if (mask < 0 || mask > 63 || (mask && !wall) || L->dim.i != L->dim.j || L->dim.i != L->dim.k || L->box_ghosts < 1) return -1;
+  if (L->boundary_condition.type != BC_DIRICHLET && (g || mask)) return -1;
+  backend_t *B = hp_backend_of(L);
+  const double w2 = bnd_sens_weight(b, L->h), w = bnd_weight(b, L->h), wn = bnd_weight_neumann(b, L->h);
+  if (where == HPGMG_WHERE_PLUGIN) {
+    HIP_OK(hpgmg_hip_dense_unpack_cell_sensitivity(&B->dev, u_id, lam_id, kcell, mean, g, a, w2, w, wn, L->h, mask, mask ? kappa : NULL, d_alpha, d_k, &status));
+    return status;
+  }
+  const size_t cells = (size_t)L->dim.i * L->dim.j * L->dim.k;
+  double *stage = dense_stage(B, 3 * cells);
+  HIP_OK(hpgmg_hip_memcpy_h2d(stage, kcell, cells * sizeof(double)));
+  HIP_OK(hpgmg_hip_dense_unpack_cell_sensitivity(&B->dev, u_id, lam_id, stage, mean, g, a, w2, w, wn, L->h, mask, mask ? kappa : NULL,
+                                                 d_alpha ? stage + 2 * cells : NULL, stage + cells, &status));
+  HIP_OK(hpgmg_hip_memcpy_d2h(d_k, stage + cells, cells * sizeof(double)));
+  if (d_alpha) HIP_OK(hpgmg_hip_memcpy_d2h(d_alpha, stage + 2 * cells, cells * sizeof(double)));
   return status;
 }
 

@@ -212,40 +212,59 @@ int hpgmg_user_set_coefficients(hpgmg_user_solver *us, const double *alpha, cons
   return hpgmg_user_set_coefficients_robin(us, alpha, beta_i, beta_j, beta_k, NULL, where);
 }
 
-int hpgmg_user_set_coefficients_robin(hpgmg_user_solver *us, const double *alpha, const double *beta_i, const double *beta_j, const double *beta_k,
-                                      const double *kappa, int where) {
-  hpgmg_solver *s = &us->s;
-  level_type *L = &s->level_h;
-  const int helmholtz = s->a != 0.0;
-  if (!beta_i || !beta_j || !beta_k || (helmholtz && !alpha) || (!helmholtz && alpha)) return HPGMG_USER_BAD_ARGUMENT;
+/* What set_coefficients_robin and set_cell_coefficients share.  user_coef_begin: the alpha / a and kappa / robin_mask rules and the configuration; then
+ * the operator, a live march and a lifted right-hand side are invalid, and kappa is taken.  HPGMG_USER_OK: go on and pack (under USER_QUIET, which the
+ * caller holds); anything else is the call's result.  user_coef_end: st the packs' status bits so far (< 0: one was refused); alpha last, then every
+ * level's operator. */
+static int user_coef_begin(hpgmg_user_solver *us, const double *alpha, const double *kappa, int where) {
+  const int helmholtz = us->s.a != 0.0;
+  int e;
+  if ((helmholtz && !alpha) || (!helmholtz && alpha)) return HPGMG_USER_BAD_ARGUMENT;
   if ((us->robin_mask != 0) != (kappa != NULL)) return HPGMG_USER_BAD_ARGUMENT;
   if (kappa && where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN) return HPGMG_USER_BAD_ARGUMENT;
   if (!user_config_ok()) return HPGMG_USER_CONFLICT;
-  int st = 0, e;
-  USER_QUIET(us);
   us->operator_ok = 0;
   us->march = 0;
   if (us->bnd) us->rhs_ok = 0;           /* the lifted f and every phi_l were made with the old beta: a new set_rhs_dirichlet is needed */
-  if (kappa) {
-    if ((e = user_take_kappa(us, kappa, where)) < 0) goto refused;
-    if (e) { USER_LOUD(); return user_pack_status(e); }
+  if (kappa && (e = user_take_kappa(us, kappa, where)) != 0) return user_pack_status(e);
+  return HPGMG_USER_OK;
+}
+static int user_coef_end(hpgmg_user_solver *us, const double *alpha, int where, int st) {
+  int e;
+  if (st < 0) return HPGMG_USER_BAD_ARGUMENT;
+  if (us->s.a != 0.0) {
+    if ((e = hpgmg_dense_pack(&us->s.level_h, VECTOR_ALPHA, alpha, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_NONNEGATIVE)) < 0) return HPGMG_USER_BAD_ARGUMENT;
+    st |= e;
   }
-  if ((e = user_pack_beta(us, VECTOR_BETA_I, beta_i, where, HPGMG_DENSE_FACE_I)) < 0) goto refused;
-  st |= e;
-  if ((e = user_pack_beta(us, VECTOR_BETA_J, beta_j, where, HPGMG_DENSE_FACE_J)) < 0) goto refused;
-  st |= e;
-  if ((e = user_pack_beta(us, VECTOR_BETA_K, beta_k, where, HPGMG_DENSE_FACE_K)) < 0) goto refused;
-  st |= e;
-  if (helmholtz && (e = hpgmg_dense_pack(L, VECTOR_ALPHA, alpha, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_NONNEGATIVE)) < 0) goto refused;
-  if (helmholtz) st |= e;
-  if (st) { USER_LOUD(); return user_pack_status(st); }
+  if (st) return user_pack_status(st);
   user_rebuild(us);
   us->operator_ok = us->coef_given = 1;
-  USER_LOUD();
   return HPGMG_USER_OK;
-refused:
+}
+
+int hpgmg_user_set_coefficients_robin(hpgmg_user_solver *us, const double *alpha, const double *beta_i, const double *beta_j, const double *beta_k,
+                                      const double *kappa, int where) {
+  if (!beta_i || !beta_j || !beta_k) return HPGMG_USER_BAD_ARGUMENT;
+  USER_QUIET(us);
+  int st = user_coef_begin(us, alpha, kappa, where), e;
+  if (st == HPGMG_USER_OK) {
+    if ((e = user_pack_beta(us, VECTOR_BETA_I, beta_i, where, HPGMG_DENSE_FACE_I)) >= 0) st |= e;
+    if (e >= 0 && (e = user_pack_beta(us, VECTOR_BETA_J, beta_j, where, HPGMG_DENSE_FACE_J)) >= 0) st |= e;
+    if (e >= 0 && (e = user_pack_beta(us, VECTOR_BETA_K, beta_k, where, HPGMG_DENSE_FACE_K)) >= 0) st |= e;
+    st = user_coef_end(us, alpha, where, e < 0 ? -1 : st);
+  }
   USER_LOUD();
-  return HPGMG_USER_BAD_ARGUMENT;
+  return st;
+}
+
+/* cell-centred conductivities (DESIGN.md §11.10): set_coefficients_robin with the three packs replaced by the one of the cell-mean hook */
+int hpgmg_user_set_cell_coefficients(hpgmg_user_solver *us, const double *alpha, const double *kcell, int mean, const double *kappa, int where) {
+  if (!us || !kcell || (mean != HPGMG_MEAN_HARMONIC && mean != HPGMG_MEAN_ARITHMETIC)) return HPGMG_USER_BAD_ARGUMENT;
+  USER_QUIET(us);
+  int st = user_coef_begin(us, alpha, kappa, where);
+  if (st == HPGMG_USER_OK) st = user_coef_end(us, alpha, where, hpgmg_dense_pack_cell_mean(&us->s.level_h, kcell, where, mean, us->mask, us->wall0));
+  USER_LOUD();
+  return st;
 }
 
 /* the bodies of set_rhs / set_rhs_dirichlet: a march packs its F = f + T(g) through them too, and goes on (DESIGN.md §11.8) */
@@ -468,11 +487,12 @@ int hpgmg_user_flux(hpgmg_user_solver *us, const double *u, const double *g, dou
 
 /* coefficient sensitivities (DESIGN.md §11.9): u into the operand vector, lam into VECTOR_R (apply's scratch: every solve sets it from f before
  * reading it), then one pass over both.  Nothing else is written: VECTOR_U, VECTOR_F, rhs_ok and a live march stay as they were. */
-int hpgmg_user_sensitivity(hpgmg_user_solver *us, const double *u, const double *lam, const double *g, double *d_alpha, double *d_beta_i, double *d_beta_j,
-                           double *d_beta_k, int where) {
+static int user_sensitivity(hpgmg_user_solver *us, const double *u, const double *lam, const double *kcell, int mean, const double *g, double *d_alpha,
+                            double *d_beta_i, double *d_beta_j, double *d_beta_k, double *d_k, int where) {      /* kcell: into d_k; else into the d_beta */
   hpgmg_solver *s = &us->s;
   level_type *L = &s->level_h;
-  if (!u || !lam || !d_beta_i || !d_beta_j || !d_beta_k || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
+  if (!u || !lam || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
+  if (kcell ? !d_k || (mean != HPGMG_MEAN_HARMONIC && mean != HPGMG_MEAN_ARITHMETIC) : !d_beta_i || !d_beta_j || !d_beta_k) return HPGMG_USER_BAD_ARGUMENT;
   if ((d_alpha != NULL) != (s->a != 0.0)) return HPGMG_USER_BAD_ARGUMENT;
   if (g && us->bc != BC_DIRICHLET) return HPGMG_USER_UNSUPPORTED;
   if (!us->operator_ok || !us->coef_given) return HPGMG_USER_NOT_READY;      /* no coefficient arrays (yet, or after a refused set_coefficients) */
@@ -481,14 +501,27 @@ int hpgmg_user_sensitivity(hpgmg_user_solver *us, const double *u, const double 
   int st = user_pack_status(hpgmg_dense_pack(L, us->x_id, u, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
   if (st == HPGMG_USER_OK) st = user_pack_status(hpgmg_dense_pack(L, VECTOR_R, lam, where, HPGMG_DENSE_CELL, HPGMG_DENSE_CHECK_FINITE));
   if (st == HPGMG_USER_OK) {
+    const double *wall = us->mask ? us->wall[0] : NULL;
     if (g) { user_bnd_alloc(us); user_bnd_take(us, us->app_g, g, where); }
     exchange_boundary(L, us->x_id, stencil_get_shape());      /* the neighbours across box faces and the periodic wrap; no ghost outside the domain is read */
     exchange_boundary(L, VECTOR_R, stencil_get_shape());
-    st = user_pack_status(hpgmg_dense_unpack_sensitivity(L, us->x_id, VECTOR_R, g ? us->app_g : NULL, s->a, s->b, us->mask, us->mask ? us->wall[0] : NULL,
-                                                         USER_KAPPA(us, 0), d_alpha, d_beta_i, d_beta_j, d_beta_k, where));
+    if (kcell) st = user_pack_status(hpgmg_dense_unpack_cell_sensitivity(L, us->x_id, VECTOR_R, kcell, mean, g ? us->app_g : NULL, s->a, s->b, us->mask, wall,
+                                                                         USER_KAPPA(us, 0), d_alpha, d_k, where));
+    else st = user_pack_status(hpgmg_dense_unpack_sensitivity(L, us->x_id, VECTOR_R, g ? us->app_g : NULL, s->a, s->b, us->mask, wall, USER_KAPPA(us, 0), d_alpha,
+                                                              d_beta_i, d_beta_j, d_beta_k, where));
   }
   USER_LOUD();
   return st;
+}
+int hpgmg_user_sensitivity(hpgmg_user_solver *us, const double *u, const double *lam, const double *g, double *d_alpha, double *d_beta_i, double *d_beta_j,
+                           double *d_beta_k, int where) {
+  return user_sensitivity(us, u, lam, NULL, 0, g, d_alpha, d_beta_i, d_beta_j, d_beta_k, NULL, where);
+}
+/* the same with the chain rule through the face mean of a cell field (DESIGN.md §11.10): d_k in place of the three face arrays */
+int hpgmg_user_cell_sensitivity(hpgmg_user_solver *us, const double *u, const double *lam, const double *kcell, int mean, const double *g, double *d_alpha,
+                                double *d_k, int where) {
+  if (!kcell) return HPGMG_USER_BAD_ARGUMENT;
+  return user_sensitivity(us, u, lam, kcell, mean, g, d_alpha, NULL, NULL, NULL, d_k, where);
 }
 
 

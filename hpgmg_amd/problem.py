@@ -44,8 +44,8 @@ solver created with a != 0: one step is one solve with a = 1 / (theta dt), which
 diagonal is rebuilt, no coefficient array is packed).  step(f, boundary=g) advances to the next time, f and g being those of that time, with
 V-cycles warm-started from the state; dt= / theta= change the step.  The state u and the rate w stay in the library, on the device, between
 calls: get_solution() and rate() return them, StepInfo.rate is max |w| and StepInfo.t the time since start().  The rate is exact for the state
-the solve stopped at, whatever rtol.  set_coefficients, set_rhs and solve end a march; get_solution, rate, apply, flux, sensitivity and
-set_shift do not.  DESIGN.md §11.8.
+the solve stopped at, whatever rtol.  set_coefficients, set_cell_coefficients, set_rhs and solve end a march; get_solution, rate, apply, flux,
+sensitivity, cell_sensitivity and set_shift do not.  DESIGN.md §11.8.
 
 Sensitivities: apply(u, boundary=g) = A0 u - T(g) is affine in alpha, in every beta entry and in a Neumann / Robin wall's own beta.
 sensitivity(u, lam, boundary=g) returns (d_alpha, d_beta_i, d_beta_j, d_beta_k), G_p = d/dp sum_c lam_c apply(u, boundary=g)_c for every
@@ -59,6 +59,13 @@ coefficient entry p, in the shapes of set_coefficients' arguments (d_alpha is No
 None of them reads a beta.  If J depends on the solution u of A u = f + T(g), and lam solves A lam = dJ/du with no boundary data (the operator is
 symmetric: the adjoint solve is solve()), then dJ/dp = -G_p and dJ/df = lam -- also on the singular solvers, whose solve subtracts the mean of
 any right-hand side.  hpgmg_amd.autograd.solve wraps exactly that as a differentiable torch function.  DESIGN.md §11.9.
+
+Cell-centred conductivities: set_cell_coefficients(alpha, k, mean="harmonic") takes the coefficient as ONE (N,N,N) array, a conductivity,
+permeability or density per cell, in place of the three face arrays: the beta of a face between two cells (box-to-box, periodic wrap) is their
+harmonic mean 2 lo hi / (lo + hi) -- or, mean="arithmetic", (lo + hi) / 2 -- and a wall face of any kind has its cell's own value.  It is
+set_coefficients with those face arrays, bit for bit.  cell_sensitivity(u, lam, k, mean=..., boundary=g) returns (d_alpha, d_k): sensitivity()
+with the chain rule through the mean, d_k[c] the sum over the six faces of cell c of G_face d beta_face / d k_c, so that dJ/dk = -d_k.
+hpgmg_amd.autograd.solve_cells is the differentiable solve on a cell field.  DESIGN.md §11.10.
 
 NumPy arrays take the host path.  torch tensors on the library's GPU (float64, contiguous) are read and written in place, and results come
 back as tensors on that device.  torch must be imported before this package loads its libraries: both bring a HIP runtime
@@ -76,6 +83,7 @@ _BC = {"dirichlet": H.BC_DIRICHLET, "periodic": H.BC_PERIODIC}
 _FACE = {"dirichlet": H.FACE_DIRICHLET, "neumann": H.FACE_NEUMANN, "convective": H.FACE_ROBIN}
 _SMOOTHER = {"cheby": H.SMOOTH_CHEBY, "chebyshev": H.SMOOTH_CHEBY, "gsrb": H.SMOOTH_GSRB, "jacobi": H.SMOOTH_JACOBI}
 _OPERATOR = {"7pt": H.OP_7PT, "27pt": H.OP_27PT, "fv4": H.OP_FV4, "fv2": H.OP_FV2}
+_MEAN = {"harmonic": H.MEAN_HARMONIC, "arithmetic": H.MEAN_ARITHMETIC}
 _METHOD = {"fmg": H.USER_FMG, "mg": H.USER_MG, "pcg": H.USER_PCG, "fpcg": H.USER_FPCG}
 _STATUS = {H.USER_BAD_ARGUMENT: "refused by the library", H.USER_CONFLICT: "the process is configured for another live solver",
            H.USER_MULTI_RANK: "only one rank is supported", H.USER_NOT_FINITE: "holds a value that is not finite",
@@ -305,6 +313,53 @@ class Solver:
             self._check(st, self._first_bad(named, st))
         self._check(st, "alpha, beta_i, beta_j, beta_k" + (", robin" if robin is not None else ""))
 
+    def _mean(self, mean):
+        if not isinstance(mean, str) or mean not in _MEAN:
+            raise ValueError(f"mean: {mean!r} is not one of {sorted(_MEAN)}")
+        return _MEAN[mean]
+
+    @staticmethod
+    def _entries_ok(x, strict):
+        """Every entry finite and > 0 (strict) or >= 0: what the library asks of k and of alpha entry by entry."""
+        v = x.detach().cpu().numpy() if _is_tensor(x) else x
+        return bool(np.isfinite(v).all() and ((v > 0.0).all() if strict else (v >= 0.0).all()))
+
+    @staticmethod
+    def _mean_bad(st, mean):
+        """k's entries pass and the library still refused it: a face mean of two neighbouring cells."""
+        return f"a {mean} mean of two neighbouring cells " + ("overflows" if st == H.USER_NOT_FINITE else "underflows to zero")
+
+    def set_cell_coefficients(self, alpha, k, mean="harmonic", robin=None):
+        """set_coefficients from ONE cell-centred array k (N,N,N), > 0: the beta of a face between two cells (box-to-box and the periodic wrap
+        included) is their mean -- "harmonic": 2 lo hi / (lo + hi), "arithmetic": (lo + hi) / 2 -- and a wall face of any kind has its cell's
+        own value.  Bit for bit set_coefficients with those three face arrays, in one pass over k.  alpha, robin: as set_coefficients takes them.
+        DESIGN.md §11.10."""
+        if (alpha is None) != (self.a == 0.0):
+            raise ValueError("alpha: required when a != 0 (Helmholtz), must be None when a == 0 (Poisson)")
+        if robin is None and self.robin_faces:
+            raise ValueError("robin: required when a face is 'convective' (kappa of du/dn + kappa u = g: a (6,N,N) array or 6 numbers)")
+        if robin is not None and not self.robin_faces:
+            raise ValueError("robin: this solver has no 'convective' face (bc=)")
+        m = self._mean(mean)
+        pk, where, kind = self._arg(k, (self.n,) * 3, "k")
+        self.coefficient_version += 1
+        pa = self._arg(alpha, (self.n,) * 3, "alpha", kind)[0] if alpha is not None else None
+        pr = None
+        if robin is not None:
+            robin = self._kappa(robin, kind, k)
+            pr = self._arg(robin, (6, self.n, self.n), "robin", kind)[0]
+        self._sync_torch(kind)
+        st = self.lib.hpgmg_user_set_cell_coefficients(self._ptr, pa, pk, m, pr, where)
+        if st in (H.USER_NOT_FINITE, H.USER_OUT_OF_RANGE):
+            if robin is not None and self._kappa_bad(robin):      # the library checks kappa first
+                raise ValueError(f"robin: {self._kappa_bad(robin)}")
+            if not self._entries_ok(k, True):
+                self._check(st, "k")
+            if alpha is not None and not self._entries_ok(alpha, False):
+                self._check(st, "alpha")
+            raise ValueError(f"k: {self._mean_bad(st, mean)}")
+        self._check(st, "alpha, k" + (", robin" if robin is not None else ""))
+
     def _boundary(self, g, kind):
         """(pointer of) the boundary values g: (6,N,N), of the same kind as the call's other arrays; Dirichlet only."""
         if self.bc != "dirichlet":
@@ -474,6 +529,41 @@ class Solver:
             named = [("u", u, 0.0, False), ("lam", lam, 0.0, False)] + ([("boundary", boundary, 0.0, False)] if boundary is not None else [])
             self._check(st, self._first_bad(named, st))
         self._check(st, "u, lam, boundary" if boundary is not None else "u, lam")
+        return out
+
+    def cell_sensitivity(self, u, lam, k, mean="harmonic", boundary=None, out=None):
+        """(d_alpha, d_k) for coefficients set with set_cell_coefficients(alpha, k, mean): d_alpha as sensitivity() returns it (None on a Poisson
+        solver), and d_k[c] = sum over the six faces of cell c of G_face d beta_face / d k_c -- sensitivity()'s face arrays gathered through the
+        derivative of the mean (1 on a wall), in one pass.  With u the solution for `boundary` and lam the solution of
+        A lam = dJ/du without boundary data, dJ/dk = -d_k.  k is passed, not remembered: the chain rule is evaluated at the array handed in.
+        out: an optional pair of arrays of u's kind to write into (out[0] None on a Poisson solver)."""
+        m = self._mean(mean)
+        pu, where, kind = self._arg(u, (self.n,) * 3, "u")
+        pl = self._arg(lam, (self.n,) * 3, "lam", kind)[0]
+        pk = self._arg(k, (self.n,) * 3, "k", kind)[0]
+        pg = self._boundary(boundary, kind) if boundary is not None else None
+        helm = self.a != 0.0
+        if out is None:
+            out = (self._out(None, kind, u, "out[0]") if helm else None, self._out(None, kind, u, "out[1]"))
+        else:
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                raise ValueError("out: expected a pair (d_alpha, d_k) of arrays")
+            out = tuple(out)
+            if (out[0] is None) == helm:
+                raise ValueError("out[0]: d_alpha is required when a != 0 (Helmholtz), must be None when a == 0 (Poisson)")
+            if out[1] is None:
+                raise ValueError("out[1]: d_k is required")
+        po = [None if q is None else self._arg(q, (self.n,) * 3, f"out[{slot}]", kind)[0] for slot, q in enumerate(out)]
+        self._sync_torch(kind)
+        st = self.lib.hpgmg_user_cell_sensitivity(self._ptr, pu, pl, pk, m, pg, po[0], po[1], where)
+        if st in (H.USER_NOT_FINITE, H.USER_OUT_OF_RANGE):
+            for name, x in (("u", u), ("lam", lam), ("boundary", boundary)):      # these need only be finite; k also > 0
+                if x is not None and not np.isfinite(x.detach().cpu().numpy() if _is_tensor(x) else x).all():
+                    self._check(H.USER_NOT_FINITE, name)
+            if not self._entries_ok(k, True):
+                self._check(st, "k")
+            raise ValueError(f"k: {self._mean_bad(st, mean)}")      # every entry passes: a face mean of k does not
+        self._check(st, "u, lam, k, boundary" if boundary is not None else "u, lam, k")
         return out
 
     # ---- implicit time stepping (module docstring; DESIGN.md §11.8)

@@ -1,7 +1,7 @@
 /*
  * hpgmg_boundary_math.h -- INTERNAL: the arithmetic of the dense-array boundary hooks (include/hpgmg_operators.h hpgmg_dense_*, hpgmg_boundary_*;
  * DESIGN.md §11.1, §11.2, §11.5, §11.6), written once for the host defaults (host/hooks_host.inc), the HIP plugin (host/plugin_dense.c) and its kernels
- * (kernels/dense_boundary.hip, kernels/dense_flux.hip, kernels/dense_sensitivity.hip).  Not part of the C ABI: it declares nothing extern and no caller of the library includes it.
+ * (kernels/dense_boundary.hip, kernels/dense_flux.hip, kernels/dense_sensitivity.hip, kernels/dense_cells.hip).  Not part of the C ABI: it declares nothing extern and no caller of the library includes it.
  *
  * The GPU tests hold the HIP build to the host defaults bit for bit, and every build has -ffp-contract=off, so the written order of each
  * floating-point expression here IS the contract: change one and both sides change together.  Whatever reads a vector of the level (the coarse
@@ -86,6 +86,25 @@ HPGMG_BND_FN double bnd_sens_masked(double wn, double kappa, double h, double u_
   const double t = kappa * h;
   return ((wn * (2.0 / (2.0 + t))) * (kappa * u_c - g)) * l_c;
 }
+
+/* Cell-centred conductivities (hpgmg_dense_pack_cell_mean, hpgmg_dense_unpack_cell_sensitivity): the beta of a face between two
+ * cells (box-to-box and the periodic wrap included) is a mean of the two, lo the cell with the smaller index along the axis (the wrap: lo = cell
+ * N - 1, hi = cell 0); a domain wall face of any kind takes its cell's own value, derivative 1.0.  mean: HPGMG_MEAN_HARMONIC (0) or
+ * HPGMG_MEAN_ARITHMETIC (1) of include/hpgmg_operators.h, which a caller has validated.
+ *   bnd_mean:      harmonic (2.0 * (lo * hi)) / (lo + hi);  arithmetic 0.5 * (lo + hi)
+ *   bnd_mean_dlo:  d/dlo: harmonic t = hi / (lo + hi), 2.0 * (t * t);  arithmetic 0.5
+ *   bnd_mean_dhi:  d/dhi = bnd_mean_dlo with the two exchanged
+ * bnd_cell_bits: the status bits of one k entry (1 not finite, 2 finite and not > 0: hpgmg_dense_pack's under CHECK_POSITIVE).  bnd_mean_bits: of a
+ * mean whose two cells both passed: overflow of lo * hi or lo + hi gives 1, underflow to zero 2. */
+HPGMG_BND_FN double bnd_mean(int mean, double lo, double hi) { return mean ? 0.5 * (lo + hi) : (2.0 * (lo * hi)) / (lo + hi); }
+HPGMG_BND_FN double bnd_mean_dlo(int mean, double lo, double hi) {
+  if (mean) return 0.5;
+  const double t = hi / (lo + hi);
+  return 2.0 * (t * t);
+}
+HPGMG_BND_FN double bnd_mean_dhi(int mean, double lo, double hi) { return bnd_mean_dlo(mean, hi, lo); }
+HPGMG_BND_FN int bnd_cell_bits(double v) { return !(v - v == 0.0) ? 1 : !(v > 0.0) ? 2 : 0; }
+HPGMG_BND_FN int bnd_mean_bits(double lo, double hi, double m) { return (bnd_cell_bits(lo) | bnd_cell_bits(hi)) ? 0 : bnd_cell_bits(m); }
 
 /* S(c) of hpgmg_boundary_lift: the four finer entries under each face entry of coarse cell (gi,gj,gk) of an n-cube, faces in order */
 HPGMG_BND_FN double bnd_fine_sum(int n, const double *phi_f, int gi, int gj, int gk) {

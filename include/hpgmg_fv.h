@@ -146,6 +146,18 @@ int  hpgmg_user_flux(hpgmg_user_solver *s, const double *u, const double *g, dou
  * and a live march stay as they were. */
 int  hpgmg_user_sensitivity(hpgmg_user_solver *s, const double *u, const double *lam, const double *g, double *d_alpha, double *d_beta_i, double *d_beta_j,
                             double *d_beta_k, int where);
+/* Cell-centred conductivities: the coefficient as ONE (N,N,N) array kcell -- a conductivity, permeability or density per cell.  The
+ * beta of a face between two cells (box-to-box and the periodic wrap included) is their mean -- mean = HPGMG_MEAN_HARMONIC (0): 2 lo hi / (lo + hi),
+ * HPGMG_MEAN_ARITHMETIC (1): (lo + hi) / 2 -- and a domain wall face of any kind has its cell's own value.
+ * set_cell_coefficients is set_coefficients_robin with those three face arrays, bit for bit, and every rule of it (alpha, kappa, the statuses, what it
+ * ends and invalidates); kcell must be finite and > 0, and a mean that overflows is HPGMG_USER_NOT_FINITE, one that underflows to zero
+ * HPGMG_USER_OUT_OF_RANGE; an unknown mean is HPGMG_USER_BAD_ARGUMENT.
+ * cell_sensitivity is hpgmg_user_sensitivity with the chain rule through the mean: d_alpha as there, and d_k[c] = sum over the six faces of cell c of
+ * G_face dbeta_face/dk_c (1 on a wall), evaluated at the kcell handed in (G reads no coefficient), so that dJ/dk = -d_k.  kcell is validated as
+ * set_cell_coefficients validates it.  Statuses and what is left untouched: hpgmg_user_sensitivity's. */
+int  hpgmg_user_set_cell_coefficients(hpgmg_user_solver *s, const double *alpha, const double *kcell, int mean, const double *kappa, int where);
+int  hpgmg_user_cell_sensitivity(hpgmg_user_solver *s, const double *u, const double *lam, const double *kcell, int mean, const double *g, double *d_alpha,
+                                 double *d_k, int where);
 /* Implicit time stepping:  alpha du/dt = b div(beta grad u) + f  with the walls and data g of the solver, by the theta scheme
  *   alpha (u1 - u0) / dt = theta w1 + (1 - theta) w0,   w = f - L(u; g) = alpha du/dt,   L(u; g) = apply_dirichlet(u, g) - a alpha u,
  * 1/2 <= theta <= 1 (1: backward Euler, 1/2: Crank-Nicolson).  One step is one solve with the operator for a = 1 / (theta dt).  The library keeps the

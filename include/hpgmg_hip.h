@@ -429,6 +429,18 @@ int hpgmg_hip_dense_unpack_flux(const hpgmg_hip_level *L, int id, const double *
 int hpgmg_hip_dense_unpack_sensitivity(const hpgmg_hip_level *L, int u_id, int lam_id, const double *g, double a, double w2, double w, double wn,
                                        double h, int mask, const double *kappa, double *d_alpha, double *d_beta_i, double *d_beta_j,
                                        double *d_beta_k, int *status);
+/* cell-centred conductivities (include/hpgmg_operators.h hpgmg_dense_pack_cell_mean / hpgmg_dense_unpack_cell_sensitivity; kernels/dense_cells.hip;
+ * DESIGN.md §11.10).  kcell: a DEVICE (n, n, n) array; the level is a cube; mean: HPGMG_MEAN_*.  pack_cell_mean: ONE launch over every padded double
+ * of every box writes vectors id_i / id_j / id_k with the bytes hpgmg_hip_dense_pack (mask 0) or hpgmg_hip_dense_pack_walls (wall: the level's
+ * wall-beta array, required under a mask) leave for the three face arrays of means; *status takes hpgmg_dense_pack's bits for kcell's entries and the
+ * means written.  unpack_cell_sensitivity: ONE launch over the interior cells (the caps of hpgmg_hip_dense_unpack_sensitivity, and its arguments)
+ * writes the DEVICE arrays d_alpha (nullptr: not written) and d_k, both the level's cells; validates kcell as the pack does and the g values read.
+ * Both synchronise. */
+int hpgmg_hip_dense_pack_cell_mean(const hpgmg_hip_level *L, int id_i, int id_j, int id_k, const double *kcell, int mean, int mask, double *wall,
+                                   int *status);
+int hpgmg_hip_dense_unpack_cell_sensitivity(const hpgmg_hip_level *L, int u_id, int lam_id, const double *kcell, int mean, const double *g, double a,
+                                            double w2, double w, double wn, double h, int mask, const double *kappa, double *d_alpha, double *d_k,
+                                            int *status);
 /* the two passes of the implicit time march (include/hpgmg_operators.h hpgmg_step_rhs / hpgmg_step_rate; kernels/dense_step.hip), one
  * launch each over the interior cells of every box; num_vectors: the vectors a box of the level holds (the ids and VECTOR_ALPHA are checked against
  * it).  step_rhs: F = F + ((a alpha) u + c w), u_old = u.  step_rate: w = (r + (a alpha) (u - u_old)) - c w, and *max_abs = max |w| (0.0 <= it; a

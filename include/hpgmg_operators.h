@@ -215,6 +215,28 @@ int     hpgmg_dense_unpack_flux(level_type *level, int x_id, const double *g, do
  * with one launch for the four arrays (kernels/dense_sensitivity.hip). */
 int     hpgmg_dense_unpack_sensitivity(level_type *level, int u_id, int lam_id, const double *g, double a, double b, int mask, const double *wall,
                                        const double *kappa, double *d_alpha, double *d_beta_i, double *d_beta_j, double *d_beta_k, int where);
+/* Cell-centred conductivities: the coefficient as ONE dense (N,N,N) array kcell, a value per cell.  The beta of a face between two
+ * cells (box-to-box; the periodic wrap, lo = cell N-1 and hi = cell 0) is bnd_mean(mean, lo, hi) of include/hpgmg_boundary_math.h, lo the cell with the
+ * smaller index -- harmonic (2.0 * (lo * hi)) / (lo + hi), arithmetic 0.5 * (lo + hi) -- and a domain wall face of any kind has its cell's own value.
+ *   pack_cell_mean:          VECTOR_BETA_I / J / K := exactly the bytes, over every padded double of every box, that hpgmg_dense_pack (mask 0) or
+ *                            hpgmg_dense_pack_walls (mask, wall) leave for those three face arrays with layouts FACE_I / J / K: under a mask `wall`
+ *                            takes the masked walls' betas and the vectors 0.0 there.  Status bits: a kcell entry that is not finite NOT_FINITE, a
+ *                            finite one that is not > 0 OUT_OF_RANGE; a mean is checked only when both its cells passed (lo * hi or lo + hi
+ *                            overflows: NOT_FINITE; the mean underflows to zero: OUT_OF_RANGE).  After a non-zero status the vectors are
+ *                            unspecified.  -1, nothing written: more than one rank, a level that is not a cube, a mask on a periodic level or
+ *                            outside 0 .. 63 or without wall, kcell NULL, an unknown where or mean.
+ *   unpack_cell_sensitivity: hpgmg_dense_unpack_sensitivity's d_alpha (may be NULL), and per cell c
+ *                              d_k[c] = ((((G_il D_il + G_ih D_ih) + G_jl D_jl) + G_jh D_jh) + G_kl D_kl) + G_kh D_kh      (left to right)
+ *                            over its six faces (low, high of i, j, k): G that pass' face sensitivity (bnd_sens_*), D the derivative of the face's
+ *                            beta to k_c -- bnd_mean_dhi on a low face, bnd_mean_dlo on a high face, 1.0 on a wall.  G reads no coefficient, so the
+ *                            chain rule is evaluated at the kcell handed in.  kcell is validated as the pack validates it, g as
+ *                            hpgmg_dense_unpack_sensitivity does; the refusals are that hook's, and kcell or d_k NULL or an unknown mean.
+ * Weak host defaults in host/hooks_host.inc (pack: the three face arrays formed with bnd_mean and packed by the existing hooks, which makes it the
+ * definition; unpack: box by box); the HIP plugin overrides them with one launch each (kernels/dense_cells.hip). */
+enum { HPGMG_MEAN_HARMONIC = 0, HPGMG_MEAN_ARITHMETIC = 1 };
+int     hpgmg_dense_pack_cell_mean(level_type *level, const double *kcell, int where, int mean, int mask, double *wall);
+int     hpgmg_dense_unpack_cell_sensitivity(level_type *level, int u_id, int lam_id, const double *kcell, int mean, const double *g, double a, double b,
+                                            int mask, const double *wall, const double *kappa, double *d_alpha, double *d_k, int where);
 /* The two streaming passes of the implicit time march of the user-problem API (hpgmg_user_start / hpgmg_user_step, include/hpgmg_fv.h)
  * over the interior cells of every box of a Helmholtz level (alpha = VECTOR_ALPHA); ghost and padding cells are neither read nor written:
  *   step_rhs:   F = F + ((a * alpha) * u + c * w) ;  u_old = u              (F holds f + T(g) on entry; a = 1 / (theta dt), c = (1 - theta) / theta)
