@@ -44,6 +44,14 @@ class UserInfo(ctypes.Structure):
                 ("vcycles", ctypes.c_int), ("converged", ctypes.c_int)]
 
 
+class UserEigInfo(ctypes.Structure):
+    """hpgmg_user_eig_info of include/hpgmg_fv.h."""
+    _fields_ = [("iterations", ctypes.c_int), ("vcycles", ctypes.c_int), ("converged", ctypes.c_int), ("reserved_", ctypes.c_int),
+                ("residuals", ctypes.c_double * 12), ("mu", ctypes.c_double * 12)]
+
+
+USER_EIGS_MAX_BLOCK, BLOCK_MAX_IN, BLOCK_MAX_OUT = 12, 36, 12      # HPGMG_USER_EIGS_MAX_BLOCK, HPGMG_BLOCK_MAX_IN / _OUT
+
 # hpgmg_dense_pack layouts / checks / where, hpgmg_user_* statuses and methods (include/hpgmg_operators.h, include/hpgmg_fv.h)
 DENSE_CELL, DENSE_FACE_I, DENSE_FACE_J, DENSE_FACE_K = 0, 1, 2, 3
 DENSE_CHECK_FINITE, DENSE_CHECK_POSITIVE, DENSE_CHECK_NONNEGATIVE = 0, 1, 2
@@ -195,6 +203,14 @@ def _declare_driver_api(lib):
         "hpgmg_pcg_update": (c_int, [vp, c_int, c_int, c_int, c_int, c_dbl, P(c_dbl)]),
         "hpgmg_pcg_dot": (c_int, [vp, c_int, c_int, P(c_dbl)]),
         "hpgmg_pcg_dot2": (c_int, [vp, c_int, c_int, c_int, P(c_dbl), P(c_dbl)]),      # method="fpcg" (§11.4): a . b and c . b in one pass
+        # eigenmodes: the call, and the block linear algebra under it
+        "hpgmg_user_eigs": (c_int, [vp, c_int, c_int, c_dbl, c_int, vp, c_int, P(c_dbl), vp, P(UserEigInfo)]),
+        "hpgmg_block_gram": (c_int, [vp, P(c_int), c_int, P(c_int), c_int, c_int, P(c_dbl)]),
+        "hpgmg_block_combine": (c_int, [vp, P(c_int), c_int, P(c_int), c_int, P(c_dbl)]),
+        "hpgmg_block_residual": (c_int, [vp, P(c_int), P(c_int), P(c_int), c_int, c_int, P(c_dbl), P(c_dbl), P(c_dbl)]),
+        "hpgmg_block_gram_host": (c_int, [vp, P(c_int), c_int, P(c_int), c_int, c_int, P(c_dbl)]),
+        "hpgmg_block_combine_host": (c_int, [vp, P(c_int), c_int, P(c_int), c_int, P(c_dbl)]),
+        "hpgmg_block_residual_host": (c_int, [vp, P(c_int), P(c_int), P(c_int), c_int, c_int, P(c_dbl), P(c_dbl), P(c_dbl)]),
         "hpgmg_vector_alloc": (vp, [ctypes.c_size_t]),
         "hpgmg_vector_free": (None, [vp]),
         "hpgmg_vector_copy": (None, [vp, vp, ctypes.c_size_t]),
@@ -236,6 +252,7 @@ def _declare_kernel_api(lib):
         "hpgmg_hip_sum": (c_int, [L, c_int, P(c_dbl)]),
         "hpgmg_hip_gram": (c_int, [L, P(c_int), c_int, P(c_int), c_int, P(c_dbl)]),
         "hpgmg_hip_pcg_dot2": (c_int, [L, c_int, c_int, c_int, P(c_dbl), P(c_dbl)]),
+        "hpgmg_hip_block_tile": (c_int, []),
         "hpgmg_hip_pair_launch_counts": (None, [P(ctypes.c_longlong)]),
     }
     for name, (res, args) in sig.items():

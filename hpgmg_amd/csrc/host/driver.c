@@ -155,6 +155,7 @@ void hpgmg_solver_richardson(hpgmg_solver *s, double out[2]) {
  * layer's files (level.c mg.c solvers.c driver.c config.c: both Makefiles, INTEGRATION.md Route A) builds all of it without naming them. */
 #include "hooks_host.inc"      /* the weak host forms of the dense-array, boundary-value and CG hooks */
 #include "user_solver.inc"     /* hpgmg_user_*: user problems on dense arrays */
+#include "user_eigs.inc"       /* hpgmg_user_eigs: eigenmodes of a user problem (LOBPCG around the V-cycle) */
 
 /* ------------------------------------------------------------------ CLI */
 static int usage(int rank) {

@@ -641,3 +641,106 @@ __attribute__((weak)) int hpgmg_pcg_update(level_type *L, int x_id, int r_id, in
 __attribute__((weak)) int hpgmg_pcg_dot(level_type *L, int a_id, int b_id, double *dot) { return hpgmg_pcg_dot_host(L, a_id, b_id, dot); }
 __attribute__((weak)) int hpgmg_pcg_dot2(level_type *L, int a_id, int c_id, int b_id, double *ab, double *cb) { return hpgmg_pcg_dot2_host(L, a_id, c_id, b_id, ab, cb); }
 
+/* ------------------------------------------------------------------ block linear algebra: portable forms (include/hpgmg_operators.h; DESIGN.md §11.11)
+ * The CG passes' one order for every Gram entry (pcg_leaves / pcg_fold above), the combination and the residuals cell by cell, from downloaded boxes.
+ * Weak like the CG passes: the HIP plugin (host/plugin_block.c) replaces them with kernels/block.hip and comes back to these on a level those do not take. */
+static int block_ids_ok(const level_type *L, const int *ids, int n, int max) {
+  int q;
+  if (!ids || n < 1 || n > max) return 0;
+  for (q = 0; q < n; q++) if (ids[q] < 0 || ids[q] >= L->numVectors) return 0;
+  return 1;
+}
+static int block_ids_distinct(const int *ids, int n) {
+  int p, q;
+  for (p = 0; p < n; p++) for (q = 0; q < p; q++) if (ids[p] == ids[q]) return 0;
+  return 1;
+}
+static double *block_download(const level_type *L, int id) {      /* every box of one vector, whole */
+  const size_t vol = (size_t)L->box_volume;
+  double *v = (double *)malloc((size_t)L->num_my_boxes * vol * sizeof(double));
+  int bx;
+  for (bx = 0; bx < L->num_my_boxes; bx++) hpgmg_vector_download(v + (size_t)bx * vol, L->my_boxes[bx].vectors[id], vol);
+  return v;
+}
+int hpgmg_block_gram_host(level_type *L, const int *a_ids, int na, const int *b_ids, int nb, int w_id, double *G) {
+  const size_t vol = (size_t)L->box_volume, len = (size_t)L->num_my_boxes * vol;
+  int i, j, bx, same = (na == nb);
+  size_t q;
+  if (!G || !block_ids_ok(L, a_ids, na, HPGMG_BLOCK_MAX_IN) || !block_ids_ok(L, b_ids, nb, HPGMG_BLOCK_MAX_IN) || w_id >= L->numVectors) return -1;
+  for (i = 0; same && i < na; i++) same = (a_ids[i] == b_ids[i]);
+  double *w = w_id >= 0 ? block_download(L, w_id) : NULL;
+  for (i = 0; i < na; i++) {
+    double *va = block_download(L, a_ids[i]);
+    if (w) for (q = 0; q < len; q++) va[q] = w[q] * va[q];       /* the leaf term is (w * a) * b */
+    for (j = 0; j < nb; j++) {
+      if (same && j < i) { G[i * nb + j] = G[j * nb + i]; continue; }
+      double *vb = block_download(L, b_ids[j]);
+      pcg_leaves P = pcg_leaves_of(L);
+      for (bx = 0; bx < L->num_my_boxes; bx++) pcg_box_leaves(L, &P, bx, va + (size_t)bx * vol, vb + (size_t)bx * vol);
+      G[i * nb + j] = pcg_fold(&P);
+      free(vb);
+    }
+    free(va);
+  }
+  free(w);
+  return 0;
+}
+int hpgmg_block_combine_host(level_type *L, const int *out_ids, int nout, const int *in_ids, int nin, const double *C) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t vol = (size_t)L->box_volume;
+  int bx, i, j, k, p, q;
+  if (!C || !block_ids_ok(L, out_ids, nout, HPGMG_BLOCK_MAX_OUT) || !block_ids_ok(L, in_ids, nin, HPGMG_BLOCK_MAX_IN) || !block_ids_distinct(out_ids, nout)) return -1;
+  double *in = (double *)malloc((size_t)(nin + nout) * vol * sizeof(double)), *out = in + (size_t)nin * vol;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    const box_type *B = &L->my_boxes[bx];
+    for (p = 0; p < nin; p++) hpgmg_vector_download(in + (size_t)p * vol, B->vectors[in_ids[p]], vol);
+    for (q = 0; q < nout; q++) hpgmg_vector_download(out + (size_t)q * vol, B->vectors[out_ids[q]], vol);      /* a box goes up whole: ghosts and padding keep their content */
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+      for (q = 0; q < nout; q++) {
+        double chain = 0.0;
+        for (p = 0; p < nin; p++) { const double t = C[p * nout + q] * in[(size_t)p * vol + ijk]; chain = chain + t; }
+        out[(size_t)q * vol + ijk] = chain;
+      }
+    }
+    for (q = 0; q < nout; q++) hpgmg_vector_upload(B->vectors[out_ids[q]], out + (size_t)q * vol, vol);
+  }
+  free(in);
+  return 0;
+}
+int hpgmg_block_residual_host(level_type *L, const int *r_ids, const int *ax_ids, const int *x_ids, int n, int w_id, const double *mu, double *rmax,
+                              double *mxmax) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  const size_t vol = (size_t)L->box_volume;
+  int bx, i, j, k, q;
+  if (!mu || !rmax || !mxmax || !block_ids_ok(L, r_ids, n, HPGMG_BLOCK_MAX_OUT) || !block_ids_ok(L, ax_ids, n, HPGMG_BLOCK_MAX_OUT) ||
+      !block_ids_ok(L, x_ids, n, HPGMG_BLOCK_MAX_OUT) || !block_ids_distinct(r_ids, n) || w_id >= L->numVectors) return -1;
+  for (q = 0; q < n; q++) for (i = 0; i < n; i++) if (i != q && (r_ids[q] == ax_ids[i] || r_ids[q] == x_ids[i])) return -1;      /* r_q may alias its own column only */
+  if (w_id >= 0) for (q = 0; q < n; q++) if (r_ids[q] == w_id) return -1;
+  double *v = (double *)malloc(4 * vol * sizeof(double)), *r = v, *ax = v + vol, *x = v + 2 * vol, *w = v + 3 * vol;
+  for (q = 0; q < n; q++) rmax[q] = mxmax[q] = 0.0;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    const box_type *B = &L->my_boxes[bx];
+    if (w_id >= 0) hpgmg_vector_download(w, B->vectors[w_id], vol);
+    for (q = 0; q < n; q++) {
+      hpgmg_vector_download(r, B->vectors[r_ids[q]], vol); hpgmg_vector_download(ax, B->vectors[ax_ids[q]], vol); hpgmg_vector_download(x, B->vectors[x_ids[q]], vol);
+      for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+        const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+        const double mx = w_id >= 0 ? w[ijk] * x[ijk] : x[ijk], t = mu[q] * mx;
+        r[ijk] = ax[ijk] - t;
+        const double fr = fabs(r[ijk]), fm = fabs(mx);
+        if (fr > rmax[q]) rmax[q] = fr;
+        if (fm > mxmax[q]) mxmax[q] = fm;
+      }
+      hpgmg_vector_upload(B->vectors[r_ids[q]], r, vol);
+    }
+  }
+  free(v);
+  return 0;
+}
+__attribute__((weak)) int hpgmg_block_gram(level_type *L, const int *a_ids, int na, const int *b_ids, int nb, int w_id, double *G) { return hpgmg_block_gram_host(L, a_ids, na, b_ids, nb, w_id, G); }
+__attribute__((weak)) int hpgmg_block_combine(level_type *L, const int *out_ids, int nout, const int *in_ids, int nin, const double *C) { return hpgmg_block_combine_host(L, out_ids, nout, in_ids, nin, C); }
+__attribute__((weak)) int hpgmg_block_residual(level_type *L, const int *r_ids, const int *ax_ids, const int *x_ids, int n, int w_id, const double *mu, double *rmax, double *mxmax) {
+  return hpgmg_block_residual_host(L, r_ids, ax_ids, x_ids, n, w_id, mu, rmax, mxmax);
+}
+

@@ -714,6 +714,20 @@ int MGFPCGSolve(mg_type *G, int onLevel, int x_id, int F_id, double a, double b,
   return pcg_solve(G, onLevel, x_id, F_id, a, b, rtol, max_iter, x_is_guess, 1);
 }
 
+/* the V-cycle as pcg_solve calls it, for a driver outside this file (include/hpgmg_mg.h) */
+void MGPreconditionerBegin(mg_type *G, int onLevel, int z_id, int r_id, double a, double b) {
+  seg_reset(G, onLevel + 320, z_id, r_id, a, b);
+  G->MGSolves_performed++;
+}
+void MGPreconditionerApply(mg_type *G, int onLevel, int z_id, int r_id, double a, double b) {
+  level_type *L = G->levels[onLevel];
+  if (!L->active) return;
+  L->vcycles_from_this_level++;
+  zero_vector(L, z_id);
+  MGVCycle(G, z_id, r_id, a, b, onLevel);
+  seg_close();
+}
+
 /* V-cycles FMGSolve may add after its F-cycle until the residual has dropped by rtol: 0, or 20 = the reference built with -DUNLIMIT_FMG_ITERATIONS (mg.c:1239-1247) */
 static int hpgmg_fmg_vcycles = 0;
 void hpgmg_set_fmg_vcycles(int n) { hpgmg_fmg_vcycles = n > 0 ? n : 0; }

@@ -155,6 +155,7 @@ static inline int hp_comm_no_messages(const communicator_type *C) { return C->nu
 static inline int hp_comm_nothing_to_exchange(const communicator_type *C) { return hp_comm_no_messages(C) && !C->num_blocks[1]; }
 HP_INTERNAL int *hp_krylov_pinned(backend_t *B);      /* backend_t.krylov_pinned, allocated (zero) on first use; NULL: no pinned memory */
 HP_INTERNAL int  hp_ghost_free_mode(void);
+HP_INTERNAL backend_t *hp_pcg_backend(level_type *L);      /* the level's backend where the CG passes' kernels take it (plugin_pcg.c), else NULL */
 HP_INTERNAL int  hp_box_rank_at(const level_type *L, int bi, int bj, int bk);
 HP_INTERNAL void hp_ensure_pair_scratch(level_type *L, backend_t *B);
 /* one boundary entry from a block of a box that sits at position bpos (in boxes) and index `box` of the kernels' table; find(ctx, gid) = the

@@ -13,7 +13,7 @@ extern int hpgmg_pcg_dot_host(level_type *, int, int, double *) __attribute__((w
 extern int hpgmg_pcg_dot2_host(level_type *, int, int, int, double *, double *) __attribute__((weak));
 #define PORTABLE(FN, ...) do { if (!FN) hp_no_kernel(#FN " (this level is not one the CG kernels take, and the host layer's portable form is not linked)"); return FN(__VA_ARGS__); } while (0)
 
-static backend_t *pcg_backend(level_type *L) {
+backend_t *hp_pcg_backend(level_type *L) {      /* the levels the CG passes' kernels take (host/plugin_block.c asks too); NULL: the portable forms */
   hpgmg_config c;
   hpgmg_get_config(&c);
   if (c.op != HPGMG_OP_7PT || !c.variable_coeff || !hp_ghost_free_mode() || !L->active || L->num_my_boxes < 1 || L->num_ranks != 1) return NULL;
@@ -26,7 +26,7 @@ static int pcg_ids_ok(const level_type *L, int a, int b, int c, int d) {
 }
 
 int hpgmg_pcg_apply_dot(level_type *L, int Ap_id, int p_id, double a, double b, double *dot) {
-  backend_t *B = pcg_backend(L);
+  backend_t *B = hp_pcg_backend(L);
   double v = 0.0;
   if (!B || Ap_id == p_id || !pcg_ids_ok(L, Ap_id, p_id, 0, 0)) PORTABLE(hpgmg_pcg_apply_dot_host, L, Ap_id, p_id, a, b, dot);
   { TICK(L, apply_op, "apply_op + dot (fused)");
@@ -37,7 +37,7 @@ int hpgmg_pcg_apply_dot(level_type *L, int Ap_id, int p_id, double a, double b, 
 }
 
 int hpgmg_pcg_update(level_type *L, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax) {
-  backend_t *B = pcg_backend(L);
+  backend_t *B = hp_pcg_backend(L);
   double v = 0.0;
   if (!B || x_id == r_id || x_id == p_id || x_id == Ap_id || r_id == p_id || r_id == Ap_id || !pcg_ids_ok(L, x_id, r_id, p_id, Ap_id))
     PORTABLE(hpgmg_pcg_update_host, L, x_id, r_id, p_id, Ap_id, alpha, rmax);
@@ -47,7 +47,7 @@ int hpgmg_pcg_update(level_type *L, int x_id, int r_id, int p_id, int Ap_id, dou
 }
 
 int hpgmg_pcg_dot(level_type *L, int a_id, int b_id, double *dot) {
-  backend_t *B = pcg_backend(L);
+  backend_t *B = hp_pcg_backend(L);
   double v = 0.0;
   if (!B || !pcg_ids_ok(L, a_id, b_id, 0, 0)) PORTABLE(hpgmg_pcg_dot_host, L, a_id, b_id, dot);
   BLAS1(hpgmg_hip_pcg_dot(&B->dev, a_id, b_id, &v));
@@ -56,7 +56,7 @@ int hpgmg_pcg_dot(level_type *L, int a_id, int b_id, double *dot) {
 }
 
 int hpgmg_pcg_dot2(level_type *L, int a_id, int c_id, int b_id, double *ab, double *cb) {
-  backend_t *B = pcg_backend(L);
+  backend_t *B = hp_pcg_backend(L);
   double v = 0.0, w = 0.0;
   if (!B || !pcg_ids_ok(L, a_id, c_id, b_id, 0)) PORTABLE(hpgmg_pcg_dot2_host, L, a_id, c_id, b_id, ab, cb);
   BLAS1(hpgmg_hip_pcg_dot2(&B->dev, a_id, c_id, b_id, &v, &w));

@@ -29,6 +29,7 @@ struct hpgmg_user_solver {
   int march;                   /* 1: a time march is live (hpgmg_user_start; DESIGN.md §11.8): VECTOR_U holds its state u, w_id its rate w = alpha du/dt */
   int uold_id, w_id;           /* the finest level's two vectors of a march (0 until the first hpgmg_user_start creates them) */
   double dt, theta;            /* of the last start / step */
+  int eig_n, eig_ids[6 * HPGMG_USER_EIGS_MAX_BLOCK];      /* the finest level's vectors of hpgmg_user_eigs (host/user_eigs.inc), in the order they were created */
 };
 static int user_live = 0;              /* user solvers alive: the process-wide configuration belongs to them */
 static hpgmg_config user_cfg;

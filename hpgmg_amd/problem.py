@@ -67,6 +67,17 @@ set_coefficients with those face arrays, bit for bit.  cell_sensitivity(u, lam, 
 with the chain rule through the mean, d_k[c] the sum over the six faces of cell c of G_face d beta_face / d k_c, so that dJ/dk = -d_k.
 hpgmg_amd.autograd.solve_cells is the differentiable solve on a cell field.  DESIGN.md §11.10.
 
+Eigenmodes: lam, modes, info = eigs(k, rtol=1e-6, max_iter=60, extra=2) returns the k smallest lambda of  K x = lambda M x  and their modes, K being
+-b div(beta grad .) with the solver's walls and zero data (apply() without its a alpha term), M = diag(alpha) on a Helmholtz solver and M = I on a
+Poisson solver: the decay rates of the march, the modes of a heterogeneous block, the eigenvalue that bounds an explicit step.  It is LOBPCG with a
+block of k + extra <= 12 columns, one V-cycle per unconverged column and iteration.  A Helmholtz solver iterates on A = a M + K with the a in force
+(set_shift's, or the last march's), whose eigenvalues are mu = a + lambda > 0 (info.mu): lam = mu - a loses digits when a >> lambda, and set_shift moves
+a.  modes is (k,N,N,N), mode j normalised to h^3 x^T M x = 1, sign and the basis inside a degenerate cluster unspecified; info.residuals are
+max |A x - mu M x| / (mu max |M x|) of the pairs returned.  Like "pcg" it reports through info.converged instead of raising.  Refused: the singular
+solvers (periodic or six Neumann walls without an a alpha term; create the solver with a > 0 and alpha = 1 and the constant mode comes back as
+lambda ~ 0) and a Helmholtz solver with alpha == 0 somewhere.  eigs leaves the coefficients (and coefficient_version) alone; it ends a march and
+invalidates the stored right-hand side and solution as set_coefficients does.  DESIGN.md §11.11.
+
 NumPy arrays take the host path.  torch tensors on the library's GPU (float64, contiguous) are read and written in place, and results come
 back as tensors on that device.  torch must be imported before this package loads its libraries: both bring a HIP runtime
 (libamdhip64.so.7), and a device pointer is only valid inside the runtime that made it.  The C entry points are hpgmg_user_* of
@@ -106,6 +117,16 @@ class StepInfo(SolveInfo):
     """Of one time step (Solver.step): SolveInfo of the step's solve, whose right-hand side is f + T(g) + a alpha u0 + c w0."""
     rate: float          # max |alpha du/dt| at the new time
     t: float             # time since start()
+
+
+@dataclass
+class EigInfo:
+    """Of Solver.eigs."""
+    iterations: int          # LOBPCG iterations run
+    vcycles: int             # V-cycles run from the finest level: one per unconverged column and iteration
+    residuals: np.ndarray    # (k,): max |A x - mu M x| / (mu max |M x|) of the returned pairs, from A x applied at the end
+    mu: np.ndarray           # (k,): the eigenvalues of the pencil (A, M) iterated on: a + lam on a Helmholtz solver, lam on a Poisson solver
+    converged: bool          # every one of the k residuals is below rtol
 
 
 def hip_runtimes_mapped():
@@ -648,6 +669,51 @@ class Solver:
             raise ValueError("rate: no march is live (start() begins one; set_coefficients, set_rhs and solve end it)")
         self._check(st, "out")
         return out
+
+    # ---- eigenmodes (module docstring)
+    def eigs(self, k, rtol=1e-6, max_iter=60, extra=2, x0=None, out=None):
+        """lam, modes, EigInfo: the k smallest lambda of K x = lambda M x (K = -b div(beta grad .) with the solver's walls and zero data, M = diag(alpha)
+        or I) as a float64 array (k,), ascending, and their modes (k,N,N,N), each normalised to h^3 x^T M x = 1 (sign, and the basis inside a degenerate
+        cluster, unspecified).  LOBPCG with k + extra <= 12 columns and one V-cycle per unconverged column and iteration, until the k residuals
+        max |A x - mu M x| / (mu max |M x|) are below rtol or for max_iter iterations; it does not raise when it stops short (info.converged).
+        A Helmholtz solver iterates on A = a M + K with the a in force: info.mu = a + lam, and lam loses digits when a >> lam (set_shift moves a).
+        x0: a start block (k + extra,N,N,N); None: a deterministic one, so the same call twice gives the same bits.  out: where the modes go -- a NumPy
+        array (the host path) or a GPU float64 tensor written in place, of the same kind as x0; None: a new NumPy array (a tensor when x0 is one).
+        Ends a march and invalidates the stored right-hand side and solution; the coefficients and coefficient_version stay."""
+        for name, v, low in (("k", k, 1), ("extra", extra, 0), ("max_iter", max_iter, 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < low:
+                raise ValueError(f"{name}: {v!r} must be an int >= {low}")
+        k, extra, m = int(k), int(extra), int(k) + int(extra)
+        if m > H.USER_EIGS_MAX_BLOCK:
+            raise ValueError(f"k + extra: {m} columns, at most {H.USER_EIGS_MAX_BLOCK} are iterated on")
+        if m > self.n ** 3:
+            raise ValueError(f"k + extra: {m} columns, the problem has {self.n ** 3} unknowns")
+        if isinstance(rtol, bool) or not isinstance(rtol, (int, float, np.integer, np.floating)) or not rtol > 0.0:
+            raise ValueError(f"rtol: {rtol!r} must be > 0")
+        kind, p0 = None, None
+        if x0 is not None:
+            p0, _, kind = self._arg(x0, (m,) + (self.n,) * 3, "x0")
+        if out is None:
+            if kind == "torch":
+                import torch
+                out = torch.empty((k,) + (self.n,) * 3, dtype=torch.float64, device=x0.device)
+            else:
+                out = np.empty((k,) + (self.n,) * 3, dtype=np.float64)
+        po, where, kind = self._arg(out, (k,) + (self.n,) * 3, "out", kind)
+        self._sync_torch(kind)
+        lam, info = np.empty(k, dtype=np.float64), H.UserEigInfo()
+        st = self.lib.hpgmg_user_eigs(self._ptr, k, extra, float(rtol), int(max_iter), p0, where,
+                                      lam.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), po, ctypes.byref(info))
+        if st == H.USER_UNSUPPORTED:
+            raise ValueError("eigs: this solver is singular (no a alpha term on a periodic box or between six Neumann walls): create it with a > 0 "
+                             "and alpha = 1, and the constant mode comes back as lambda ~ 0")
+        if st == H.USER_OUT_OF_RANGE:
+            raise ValueError("alpha: zero in some cell, so M = diag(alpha) is not positive definite (eigs needs alpha > 0 everywhere)")
+        if st == H.USER_NOT_READY:
+            raise ValueError("eigs: no valid coefficients (an earlier set_coefficients was refused)")
+        self._check(st, "x0" if st == H.USER_NOT_FINITE else "k, extra, rtol, max_iter, x0 or out")
+        self._dt = None                     # a march is over
+        return lam, out, EigInfo(info.iterations, info.vcycles, np.array(info.residuals[:k]), np.array(info.mu[:k]), bool(info.converged))
 
     def wall_flux(self, fluxes):
         """The OUTWARD flux through the six walls as a (6,N,N) array in `boundary`'s layout, from the triple flux() returned: the wall entries

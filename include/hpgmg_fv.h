@@ -181,6 +181,30 @@ int  hpgmg_user_start(hpgmg_user_solver *s, const double *u, const double *f, co
 int  hpgmg_user_step(hpgmg_user_solver *s, const double *f, const double *g, int where, double dt, double theta, double rtol, hpgmg_user_info *info,
                      double *rate);
 int  hpgmg_user_get_rate(hpgmg_user_solver *s, double *out, int where);
+/* Eigenmodes: the k smallest lambda of  K x = lambda M x,  K = -b div(beta grad .) with the solver's walls and homogeneous data (the
+ * operator of hpgmg_user_apply without its a alpha term), M = diag(alpha) on a Helmholtz solver (a != 0) and M = I on a Poisson solver, by LOBPCG with
+ * block size m = k + extra (1 <= k, 0 <= extra, m <= HPGMG_USER_EIGS_MAX_BLOCK, else HPGMG_USER_BAD_ARGUMENT) preconditioned with one V-cycle per active
+ * column and iteration.  A Helmholtz solver iterates on A = a M + K with the shift a in force (set_shift's or a march's): its pencil eigenvalues are
+ * mu = a + lambda > 0, lam[j] = mu_j - a (lambda loses digits when a >> lambda: set_shift moves a) and info->mu[j] = mu_j.
+ * x0: m start vectors, an (m,N,N,N) array in `where` (not finite: HPGMG_USER_NOT_FINITE), or NULL: a deterministic start (products of low-order
+ * polynomials in x, y, z plus a hash of the global cell index): the same call twice gives the same bits.  lam: k doubles on the HOST, ascending.
+ * modes: (k,N,N,N) in `where`, mode j normalised to h^3 x^T M x = 1; its sign, and the basis within a degenerate cluster, are unspecified.
+ * info: iterations, the V-cycles run, residuals[j] = max |A x_j - mu_j M x_j| / (mu_j max |M x_j|) of the returned pairs (true ones: from A x_j applied at
+ * the end), mu, and converged = every residual < rtol.  Stopping short (max_iter, or a Rayleigh-Ritz step that broke down) is not an error: the last block
+ * is returned with converged = 0.
+ * Refused: a singular solver (periodic, or six Neumann / zero-kappa Robin walls, with a = 0 or alpha = 0: HPGMG_USER_UNSUPPORTED -- create the solver with
+ * a > 0 and alpha = 1, the constant mode then comes back as lambda ~ 0); a Helmholtz solver with alpha == 0 in some cell (HPGMG_USER_OUT_OF_RANGE: M must
+ * be positive definite); no valid coefficients (HPGMG_USER_NOT_READY).  A refusal writes nothing to lam, modes or info.
+ * The coefficients stay as they are.  The call ends a live march and invalidates the stored right-hand side and solution, as set_coefficients does: solve
+ * needs a set_rhs first.  The first call gives every level the three vectors of HPGMG_USER_PCG and the finest level 6 m more (a later call with a larger
+ * m the difference). */
+#define HPGMG_USER_EIGS_MAX_BLOCK 12
+typedef struct {
+  int iterations, vcycles, converged, reserved_;
+  double residuals[HPGMG_USER_EIGS_MAX_BLOCK], mu[HPGMG_USER_EIGS_MAX_BLOCK];
+} hpgmg_user_eig_info;
+int  hpgmg_user_eigs(hpgmg_user_solver *s, int k, int extra, double rtol, int max_iter, const double *x0, int where, double *lam, double *modes,
+                     hpgmg_user_eig_info *info);
 
 /* ---- small accessors so a ctypes caller never needs the struct layouts ---- */
 enum { HPGMG_INFO_DIM = 0, HPGMG_INFO_BOX_DIM, HPGMG_INFO_GHOSTS, HPGMG_INFO_JSTRIDE, HPGMG_INFO_KSTRIDE,

@@ -378,6 +378,18 @@ int hpgmg_hip_pcg_dot(const hpgmg_hip_level *L, int a_id, int b_id, double *dot)
 /* *ab = a . b and *cb = c . b (the flexible CG's r . z and Ap . z): pcg_dot's mapping with three streams read once and two chains per lane,
  * ONE fold launch for both trees and one wait for both values; each value has the bits of hpgmg_hip_pcg_dot on its pair. */
 int hpgmg_hip_pcg_dot2(const hpgmg_hip_level *L, int a_id, int c_id, int b_id, double *ab, double *cb);
+/* Block linear algebra of the eigen-solver (include/hpgmg_operators.h hpgmg_block_*; kernels/block.hip), each one pass in the CG passes'
+ * mapping plus, where it ends in scalars, a tiny launch that finishes them and one copy to the host; block_gram and block_residual synchronise; block_combine does not (C goes through one of two pinned staging arrays in stream order).  G_host, C_host,
+ * mu, rmax, mxmax are HOST arrays.  The ids must name vectors of the level (the caller checks their upper bound), the outputs of block_combine and the r ids
+ * of block_residual be distinct.  _supported: a level whose workgroup values for 36 x 36 entries the scratch arithmetic holds.
+ * block_gram: a lane carries a HPGMG_HIP_BLOCK_TILE x HPGMG_HIP_BLOCK_TILE tile of pair chains; identical id lists launch the upper tiles only. */
+#define HPGMG_HIP_BLOCK_TILE 6
+int hpgmg_hip_block_supported(const hpgmg_hip_level *L);
+int hpgmg_hip_block_tile(void);
+int hpgmg_hip_block_gram(const hpgmg_hip_level *L, const int *a_ids, int na, const int *b_ids, int nb, int w_id, double *G_host);
+int hpgmg_hip_block_combine(const hpgmg_hip_level *L, const int *out_ids, int nout, const int *in_ids, int nin, const double *C_host);
+int hpgmg_hip_block_residual(const hpgmg_hip_level *L, const int *r_ids, const int *ax_ids, const int *x_ids, int n, int w_id, const double *mu,
+                             double *rmax, double *mxmax);
 
 /* dense arrays <-> vector id (include/hpgmg_operators.h hpgmg_dense_pack / unpack; kernels/dense_io.hip).  src / dst are DEVICE arrays.
  * pack: a (nk, nj, ni) array, each extent the level's global one or one more (a Dirichlet face array); writes every double of every box

@@ -63,6 +63,11 @@ int  MGPCGSolve(mg_type *all_grids, int onLevel, int x_id, int F_id, double a, d
  * returns r.z and Ap.z, and beta = -(Ap.z / p.Ap) makes the new direction A-orthogonal to the last one explicitly.  A beta of 0.0 is legitimate (p = z);
  * only a non-finite one ends the solve.  Arguments, vectors, return value and hpgmg_last_solve as MGPCGSolve. */
 int  MGFPCGSolve(mg_type *all_grids, int onLevel, int x_id, int F_id, double a, double b, double rtol, int max_iter, int x_is_guess);
+/* The V-cycle as a preconditioner for a driver outside host/mg.c (the eigen-solver of the user-problem API), exactly as the two CG solves
+ * above call it: Begin once per solve (the launch-bound segments get a key of their own), then per application z = 0 and one V-cycle from onLevel on
+ * A z = r, counted in vcycles_from_this_level.  z_id and r_id must be vectors of EVERY level (the cycle restricts and corrects under the same ids). */
+void MGPreconditionerBegin(mg_type *all_grids, int onLevel, int z_id, int r_id, double a, double b);
+void MGPreconditionerApply(mg_type *all_grids, int onLevel, int z_id, int r_id, double a, double b);
 void MGPrintTiming(mg_type *all_grids, int fromLevel);
 void MGResetTimers(mg_type *all_grids);
 void richardson_error(mg_type *all_grids, int levelh, int u_id);

@@ -269,6 +269,29 @@ int     hpgmg_pcg_apply_dot_host(level_type *level, int Ap_id, int p_id, double 
 int     hpgmg_pcg_update_host(level_type *level, int x_id, int r_id, int p_id, int Ap_id, double alpha, double *rmax);
 int     hpgmg_pcg_dot_host(level_type *level, int a_id, int b_id, double *dot);
 int     hpgmg_pcg_dot2_host(level_type *level, int a_id, int c_id, int b_id, double *ab, double *cb);
+/* Block linear algebra on one level for the eigen-solver of the user-problem API (hpgmg_user_eigs, include/hpgmg_fv.h): many inner
+ * products, a linear combination of many vectors and the residuals of a block of Ritz pairs, each in ONE pass over its vectors.  All three touch
+ * interior cells only: no ghost or padding double is read into a result or written.  Return value as the CG passes above (1 = the plugin's kernel ran,
+ * 0 = the portable form, same bits), and -1 = refused (a count out of range, an id that is not a vector of the level, repeated outputs): nothing written.
+ *   block_gram:     G[i * nb + j] = sum over the cells of w * a_i * b_j (w_id < 0: of a_i * b_j), 1 <= na, nb <= HPGMG_BLOCK_MAX_IN.  Every entry is one
+ *                   tree of the CG passes' order above; its leaf term is the product a_i * b_j, weighted (w * a_i) * b_j in that association.  So an
+ *                   unweighted entry has the bits of hpgmg_pcg_dot(a_i, b_j).  When the two id lists are identical, entry (i, j < i) is a copy of (j, i).
+ *   block_combine:  out_j = sum_i C[i * nout + j] * in_i, 1 <= nin <= HPGMG_BLOCK_MAX_IN, 1 <= nout <= HPGMG_BLOCK_MAX_OUT: per cell the chain starts at
+ *                   0.0 and runs i = 0 .. nin - 1, each product formed first.  Outputs may alias inputs (a cell reads all its inputs before it
+ *                   writes); the outputs must be distinct ids.  C is a host array.
+ *   block_residual: r_j = ax_j - mu_j * (w * x_j) (w_id < 0: mu_j * x_j), the product w * x first; rmax[j] = max |r_j| and mxmax[j] = max |w * x_j|
+ *                   (each from 0.0; a NaN is never the maximum, as in norm()), 1 <= n <= HPGMG_BLOCK_MAX_OUT columns in one pass.  The r ids must be
+ *                   distinct; r_j may be ax_j or x_j of its own column. */
+#define HPGMG_BLOCK_MAX_IN 36
+#define HPGMG_BLOCK_MAX_OUT 12
+int     hpgmg_block_gram(level_type *level, const int *a_ids, int na, const int *b_ids, int nb, int w_id, double *G);
+int     hpgmg_block_combine(level_type *level, const int *out_ids, int nout, const int *in_ids, int nin, const double *C);
+int     hpgmg_block_residual(level_type *level, const int *r_ids, const int *ax_ids, const int *x_ids, int n, int w_id, const double *mu, double *rmax,
+                             double *mxmax);
+int     hpgmg_block_gram_host(level_type *level, const int *a_ids, int na, const int *b_ids, int nb, int w_id, double *G);      /* the portable forms themselves (0 or -1) */
+int     hpgmg_block_combine_host(level_type *level, const int *out_ids, int nout, const int *in_ids, int nin, const double *C);
+int     hpgmg_block_residual_host(level_type *level, const int *r_ids, const int *ax_ids, const int *x_ids, int n, int w_id, const double *mu, double *rmax,
+                                  double *mxmax);
 /* Launch-bound stretches of a cycle (everything done on levels of <= 64^3 cells between two
  * bottom solves) are bracketed by the cycle driver as a SEGMENT with a key that repeats every
  * solve, so the HIP plugin can capture it once into a hipGraph and replay it.  Plugins without
