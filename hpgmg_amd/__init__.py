@@ -50,6 +50,11 @@ class UserEigInfo(ctypes.Structure):
                 ("residuals", ctypes.c_double * 12), ("mu", ctypes.c_double * 12)]
 
 
+class UserWaveInfo(ctypes.Structure):
+    """hpgmg_user_wave_info of include/hpgmg_fv.h."""
+    _fields_ = UserInfo._fields_ + [("t", ctypes.c_double), ("kinetic", ctypes.c_double), ("potential", ctypes.c_double)]
+
+
 USER_EIGS_MAX_BLOCK, BLOCK_MAX_IN, BLOCK_MAX_OUT = 12, 36, 12      # HPGMG_USER_EIGS_MAX_BLOCK, HPGMG_BLOCK_MAX_IN / _OUT
 
 # hpgmg_dense_pack layouts / checks / where, hpgmg_user_* statuses and methods (include/hpgmg_operators.h, include/hpgmg_fv.h)
@@ -211,6 +216,17 @@ def _declare_driver_api(lib):
         "hpgmg_block_gram_host": (c_int, [vp, P(c_int), c_int, P(c_int), c_int, c_int, P(c_dbl)]),
         "hpgmg_block_combine_host": (c_int, [vp, P(c_int), c_int, P(c_int), c_int, P(c_dbl)]),
         "hpgmg_block_residual_host": (c_int, [vp, P(c_int), P(c_int), P(c_int), c_int, c_int, P(c_dbl), P(c_dbl), P(c_dbl)]),
+        # the wave equation: the calls, and the three passes under them
+        "hpgmg_user_wave_start": (c_int, [vp, vp, vp, vp, vp, c_int, c_dbl, c_dbl, c_dbl, c_dbl, P(UserWaveInfo)]),
+        "hpgmg_user_wave_step": (c_int, [vp, vp, vp, c_int, c_dbl, c_dbl, P(UserWaveInfo)]),
+        "hpgmg_user_get_velocity": (c_int, [vp, vp, c_int]),
+        "hpgmg_user_get_acceleration": (c_int, [vp, vp, c_int]),
+        "hpgmg_wave_predict": (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl]),
+        "hpgmg_wave_correct": (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, P(c_dbl)]),
+        "hpgmg_wave_init": (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, P(c_dbl)]),
+        "hpgmg_wave_predict_host": (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl]),
+        "hpgmg_wave_correct_host": (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, P(c_dbl)]),
+        "hpgmg_wave_init_host": (c_int, [vp, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, P(c_dbl)]),
         "hpgmg_vector_alloc": (vp, [ctypes.c_size_t]),
         "hpgmg_vector_free": (None, [vp]),
         "hpgmg_vector_copy": (None, [vp, vp, ctypes.c_size_t]),
@@ -253,6 +269,9 @@ def _declare_kernel_api(lib):
         "hpgmg_hip_gram": (c_int, [L, P(c_int), c_int, P(c_int), c_int, P(c_dbl)]),
         "hpgmg_hip_pcg_dot2": (c_int, [L, c_int, c_int, c_int, P(c_dbl), P(c_dbl)]),
         "hpgmg_hip_block_tile": (c_int, []),
+        "hpgmg_hip_wave_predict": (c_int, [L, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl]),
+        "hpgmg_hip_wave_correct": (c_int, [L, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, P(c_dbl)]),
+        "hpgmg_hip_wave_init": (c_int, [L, c_int, c_int, c_int, c_int, c_int, c_int, c_dbl, c_dbl, P(c_dbl)]),
         "hpgmg_hip_pair_launch_counts": (None, [P(ctypes.c_longlong)]),
     }
     for name, (res, args) in sig.items():

@@ -156,6 +156,7 @@ void hpgmg_solver_richardson(hpgmg_solver *s, double out[2]) {
 #include "hooks_host.inc"      /* the weak host forms of the dense-array, boundary-value and CG hooks */
 #include "user_solver.inc"     /* hpgmg_user_*: user problems on dense arrays */
 #include "user_eigs.inc"       /* hpgmg_user_eigs: eigenmodes of a user problem (LOBPCG around the V-cycle) */
+#include "user_wave.inc"       /* hpgmg_user_wave_*: the wave equation on a user problem (Newmark) */
 
 /* ------------------------------------------------------------------ CLI */
 static int usage(int rank) {

@@ -1,6 +1,6 @@
 /*
  * hooks_host.inc -- the portable host forms of the dense-array, boundary-value, time-march and CG hooks (include/hpgmg_operators.h hpgmg_dense_*,
- * hpgmg_boundary_*, hpgmg_step_*, hpgmg_pcg_*): box by box through the plugin's hpgmg_vector_upload / download.  They are weak, so that a plugin with kernels
+ * hpgmg_boundary_*, hpgmg_step_*, hpgmg_pcg_*, hpgmg_block_*, hpgmg_wave_*): box by box through the plugin's hpgmg_vector_upload / download.  They are weak, so that a plugin with kernels
  * for them (the HIP plugin: host/plugin_dense.c, host/plugin_pcg.c; its kernels: kernels/dense_io.hip, dense_boundary.hip, dense_flux.hip, dense_cells.hip, pcg.hip) replaces them while one without (the CPU oracle, whose memory is host memory
  * for either `where`) gets these.  The boundary arithmetic itself is include/hpgmg_boundary_math.h, shared with those kernels.
  * A part of host/driver.c's translation unit, included there.
@@ -11,6 +11,7 @@
 #include "hpgmg_fv.h"
 #include "hpgmg_boundary_math.h"
 #include "hpgmg_step_math.h"
+#include "hpgmg_wave_math.h"
 
 /* ------------------------------------------------------------------ dense arrays <-> boxes (include/hpgmg_operators.h) */
 /* mask, wall: hpgmg_dense_pack_walls (0, NULL: hpgmg_dense_pack) */
@@ -744,3 +745,102 @@ __attribute__((weak)) int hpgmg_block_residual(level_type *L, const int *r_ids, 
   return hpgmg_block_residual_host(L, r_ids, ax_ids, x_ids, n, w_id, mu, rmax, mxmax);
 }
 
+
+/* ------------------------------------------------------------------ the Newmark march: portable forms (include/hpgmg_operators.h; DESIGN.md §11.12)
+ * The cell expressions of include/hpgmg_wave_math.h over the interior cells, box by box through download / upload (a box goes up whole, so a vector that
+ * is only written is downloaded first: its ghost and padding doubles keep their content), and the two sums in the CG passes' one order (pcg_leaves /
+ * pcg_fold above) from per-cell leaf terms.  Weak like the block hooks: the HIP plugin (host/plugin_wave.c) replaces them with kernels/dense_wave.hip and
+ * comes back to these on a level those do not take. */
+static void wave_box_leaves(const level_type *L, pcg_leaves *P, int bx, const double *term) {      /* pcg_box_leaves with the terms already formed */
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride;
+  int i, j, k;
+  size_t s;
+  for (s = 0; s < P->S; s++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+    const int k1 = (int)(s + 1) * HPGMG_PCG_SEGMENT < dim ? (int)(s + 1) * HPGMG_PCG_SEGMENT : dim;
+    double chain = 0.0;
+    for (k = (int)s * HPGMG_PCG_SEGMENT; k < k1; k++) chain = chain + term[(i + g) + (j + g) * jS + (k + g) * kS];
+    P->V[(size_t)(i + dim * j) + P->W * (s + P->S * (size_t)bx)] = chain;
+  }
+}
+int hpgmg_wave_predict_host(level_type *L, int u_id, int uold_id, int v_id, int F_id, int q_id, double dt, double cu, double cv, double a, double sigma) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride, ids[5] = { u_id, uold_id, v_id, F_id, q_id };
+  const size_t vol = (size_t)L->box_volume;
+  int bx, i, j, k;
+  if (wave_ids_refused(ids, 4, 5, L->numVectors, VECTOR_ALPHA)) return -1;
+  double *w = step_boxes(L, 6), *u = w, *uold = w + vol, *v = w + 2 * vol, *F = w + 3 * vol, *q = w + 4 * vol, *al = w + 5 * vol;
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    const box_type *B = &L->my_boxes[bx];
+    hpgmg_vector_download(u, B->vectors[u_id], vol); hpgmg_vector_download(uold, B->vectors[uold_id], vol); hpgmg_vector_download(v, B->vectors[v_id], vol);
+    hpgmg_vector_download(F, B->vectors[F_id], vol); hpgmg_vector_download(q, B->vectors[q_id], vol); hpgmg_vector_download(al, B->vectors[VECTOR_ALPHA], vol);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+      const double ut = wave_ut_cell(u[ijk], v[ijk], q[ijk], dt, cu), vt = wave_vt_cell(v[ijk], q[ijk], cv);
+      F[ijk] = wave_rhs_cell(F[ijk], al[ijk], ut, vt, a, sigma);
+      u[ijk] = ut; uold[ijk] = ut; v[ijk] = vt;
+    }
+    hpgmg_vector_upload(B->vectors[u_id], u, vol); hpgmg_vector_upload(B->vectors[uold_id], uold, vol);
+    hpgmg_vector_upload(B->vectors[v_id], v, vol); hpgmg_vector_upload(B->vectors[F_id], F, vol);
+  }
+  free(w);
+  return 0;
+}
+int hpgmg_wave_correct_host(level_type *L, int q_id, int v_id, int u_id, int uold_id, int F_id, int r_id, double a, double cq, double cg, double sums[2]) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride, ids[6] = { q_id, v_id, u_id, uold_id, F_id, r_id };
+  const size_t vol = (size_t)L->box_volume;
+  int bx, i, j, k;
+  if (!sums || wave_ids_refused(ids, 2, 6, L->numVectors, VECTOR_ALPHA)) return -1;
+  double *w = step_boxes(L, 9), *q = w, *v = w + vol, *u = w + 2 * vol, *uold = w + 3 * vol, *F = w + 4 * vol, *r = w + 5 * vol, *al = w + 6 * vol;
+  double *kin = w + 7 * vol, *pot = w + 8 * vol;
+  pcg_leaves K = pcg_leaves_of(L), U = pcg_leaves_of(L);
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    const box_type *B = &L->my_boxes[bx];
+    hpgmg_vector_download(q, B->vectors[q_id], vol); hpgmg_vector_download(v, B->vectors[v_id], vol); hpgmg_vector_download(u, B->vectors[u_id], vol);
+    hpgmg_vector_download(uold, B->vectors[uold_id], vol); hpgmg_vector_download(F, B->vectors[F_id], vol); hpgmg_vector_download(r, B->vectors[r_id], vol);
+    hpgmg_vector_download(al, B->vectors[VECTOR_ALPHA], vol);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+      q[ijk] = wave_q_cell(u[ijk], uold[ijk], cq);
+      v[ijk] = wave_v_cell(v[ijk], q[ijk], cg);
+      kin[ijk] = wave_kinetic_cell(al[ijk], v[ijk]);
+      pot[ijk] = wave_potential_cell(u[ijk], F[ijk], r[ijk], al[ijk], a);
+    }
+    wave_box_leaves(L, &K, bx, kin); wave_box_leaves(L, &U, bx, pot);
+    hpgmg_vector_upload(B->vectors[q_id], q, vol); hpgmg_vector_upload(B->vectors[v_id], v, vol);
+  }
+  free(w);
+  sums[0] = pcg_fold(&K); sums[1] = pcg_fold(&U);
+  return 0;
+}
+int hpgmg_wave_init_host(level_type *L, int q_id, int r_id, int u_id, int v_id, int F_id, double a, double sigma, double sums[2]) {
+  const int g = L->box_ghosts, dim = L->box_dim, jS = L->box_jStride, kS = L->box_kStride, ids[5] = { q_id, r_id, u_id, v_id, F_id };
+  const size_t vol = (size_t)L->box_volume;
+  int bx, i, j, k;
+  if (!sums || wave_ids_refused(ids, 1, 5, L->numVectors, VECTOR_ALPHA)) return -1;
+  double *w = step_boxes(L, 8), *q = w, *r = w + vol, *u = w + 2 * vol, *v = w + 3 * vol, *F = w + 4 * vol, *al = w + 5 * vol, *kin = w + 6 * vol, *pot = w + 7 * vol;
+  pcg_leaves K = pcg_leaves_of(L), U = pcg_leaves_of(L);
+  for (bx = 0; bx < L->num_my_boxes; bx++) {
+    const box_type *B = &L->my_boxes[bx];
+    hpgmg_vector_download(q, B->vectors[q_id], vol); hpgmg_vector_download(r, B->vectors[r_id], vol); hpgmg_vector_download(u, B->vectors[u_id], vol);
+    hpgmg_vector_download(v, B->vectors[v_id], vol); hpgmg_vector_download(F, B->vectors[F_id], vol); hpgmg_vector_download(al, B->vectors[VECTOR_ALPHA], vol);
+    for (k = 0; k < dim; k++) for (j = 0; j < dim; j++) for (i = 0; i < dim; i++) {
+      const int ijk = (i + g) + (j + g) * jS + (k + g) * kS;
+      q[ijk] = wave_init_cell(r[ijk], al[ijk], u[ijk], v[ijk], a, sigma);
+      kin[ijk] = wave_kinetic_cell(al[ijk], v[ijk]);
+      pot[ijk] = wave_potential_cell(u[ijk], F[ijk], r[ijk], al[ijk], a);
+    }
+    wave_box_leaves(L, &K, bx, kin); wave_box_leaves(L, &U, bx, pot);
+    hpgmg_vector_upload(B->vectors[q_id], q, vol);
+  }
+  free(w);
+  sums[0] = pcg_fold(&K); sums[1] = pcg_fold(&U);
+  return 0;
+}
+__attribute__((weak)) int hpgmg_wave_predict(level_type *L, int u_id, int uold_id, int v_id, int F_id, int q_id, double dt, double cu, double cv, double a, double sigma) {
+  return hpgmg_wave_predict_host(L, u_id, uold_id, v_id, F_id, q_id, dt, cu, cv, a, sigma);
+}
+__attribute__((weak)) int hpgmg_wave_correct(level_type *L, int q_id, int v_id, int u_id, int uold_id, int F_id, int r_id, double a, double cq, double cg, double sums[2]) {
+  return hpgmg_wave_correct_host(L, q_id, v_id, u_id, uold_id, F_id, r_id, a, cq, cg, sums);
+}
+__attribute__((weak)) int hpgmg_wave_init(level_type *L, int q_id, int r_id, int u_id, int v_id, int F_id, double a, double sigma, double sums[2]) {
+  return hpgmg_wave_init_host(L, q_id, r_id, u_id, v_id, F_id, a, sigma, sums);
+}

@@ -26,9 +26,12 @@ struct hpgmg_user_solver {
   int robin_mask;              /* bit f: face f is a Robin wall (a subset of mask) */
   int kappa_positive;          /* some kappa of a Robin face is > 0: six masked walls are then not singular */
   double **kappa;              /* robin_mask != 0: per level, kappa of the Robin walls (a boundary array, 0.0 on the other faces), allocated and freed with wall */
-  int march;                   /* 1: a time march is live (hpgmg_user_start; DESIGN.md §11.8): VECTOR_U holds its state u, w_id its rate w = alpha du/dt */
-  int uold_id, w_id;           /* the finest level's two vectors of a march (0 until the first hpgmg_user_start creates them) */
-  double dt, theta;            /* of the last start / step */
+  int march;                   /* 1: a theta march is live (hpgmg_user_start; DESIGN.md §11.8): VECTOR_U holds its state u, w_id its rate w = alpha du/dt;
+                                  2: a wave march is (hpgmg_user_wave_start, host/user_wave.inc; DESIGN.md §11.12): w_id holds v = du/dt, q_id the acceleration */
+  int uold_id, w_id;           /* the finest level's two vectors of a march (0 until the first hpgmg_user_start / _wave_start creates them) */
+  int q_id;                    /* and the wave march's third (0 until the first hpgmg_user_wave_start) */
+  double dt, theta;            /* of the last start / step (dt: of either march) */
+  double wave_beta, wave_gamma, wave_sigma, wave_t;      /* of the last wave_start; the time since it */
   int eig_n, eig_ids[6 * HPGMG_USER_EIGS_MAX_BLOCK];      /* the finest level's vectors of hpgmg_user_eigs (host/user_eigs.inc), in the order they were created */
 };
 static int user_live = 0;              /* user solvers alive: the process-wide configuration belongs to them */
@@ -585,7 +588,7 @@ int hpgmg_user_step(hpgmg_user_solver *us, const double *f, const double *g, int
   if (!us || !f || !(rtol > 0.0) || (where != HPGMG_WHERE_HOST && where != HPGMG_WHERE_PLUGIN)) return HPGMG_USER_BAD_ARGUMENT;
   hpgmg_solver *s = &us->s;
   level_type *L = &s->level_h;
-  if (!us->march || !us->operator_ok) return HPGMG_USER_NOT_READY;
+  if (us->march != 1 || !us->operator_ok) return HPGMG_USER_NOT_READY;      /* no march, or a wave march */
   if (!(dt > 0.0)) dt = us->dt;          /* <= 0: as before */
   if (!(theta > 0.0)) theta = us->theta;
   if (!user_theta_ok(dt, theta)) return HPGMG_USER_BAD_ARGUMENT;
@@ -626,7 +629,7 @@ int hpgmg_user_step(hpgmg_user_solver *us, const double *f, const double *g, int
 
 int hpgmg_user_get_rate(hpgmg_user_solver *us, double *out, int where) {
   if (!us || !out) return HPGMG_USER_BAD_ARGUMENT;
-  if (!us->march) return HPGMG_USER_NOT_READY;
+  if (us->march != 1) return HPGMG_USER_NOT_READY;
   USER_QUIET(us);
   const int st = hpgmg_dense_unpack(&us->s.level_h, us->w_id, out, where);
   USER_LOUD();

@@ -9,44 +9,12 @@
 // stride-doubling tree over the leaves V[c + W (s + S box)] -- and pcg_fold_kernel folds the workgroups' values (stride 256 upwards) in a second tiny
 // launch (a last-workgroup form needs an agent-scope fence per workgroup: blas1.hip measured that 4x slower).  Lanes past dim^2 carry the tree's 0.0.
 // The stencil reads a face neighbour where it lives (common.hpp: box_nbr) and a Dirichlet face as -x(centre): apply_op's ghost-free rule, same bits.
-#include "reduce.hpp"
+#include "pcg_map.hpp"
 #include "stencil_math.hpp"
 
 namespace hpgmg {
 
-constexpr int kPcgLanes = HPGMG_PCG_COLUMNS, kPcgSeg = HPGMG_PCG_SEGMENT, kFoldLanes = 1024;
-
-struct PcgItem { int item, box, k0, k1, c; bool live; };
-__device__ __forceinline__ bool pcg_item(const hpgmg_hip_level &L, int nseg, int ncb, int per_xcd, int items, PcgItem &it) {
-  const int item = xcd_logical_block((int)blockIdx.x, per_xcd);     // an XCD owns a contiguous run of items: rows shared by neighbouring items meet in its L2
-  if (item >= items) return false;
-  it.item = item;
-  const int cb = item % ncb, s = (item / ncb) % nseg;
-  it.box = item / (ncb * nseg);
-  it.k0 = s * kPcgSeg; it.k1 = (it.k0 + kPcgSeg < L.dim) ? it.k0 + kPcgSeg : L.dim;
-  it.c = cb * kPcgLanes + (int)threadIdx.x;
-  it.live = it.c < L.dim * L.dim;
-  return true;
-}
-
-// the tree below stride 256: V[m] = V[m] + V[m + stride], the value of the workgroup's 256 leaves in lane 0
-__device__ __forceinline__ double pcg_block_sum(double v, double *smem) {
-#pragma unroll
-  for (int stride = 1; stride < 64; stride *= 2) v = v + __shfl_down(v, stride, 64);
-  if (threadIdx.x % 64 == 0) smem[threadIdx.x / 64] = v;
-  __syncthreads();
-  const double lo = smem[0] + smem[1], hi = smem[2] + smem[3];
-  return lo + hi;
-}
-// two such trees at once: one barrier for both (smem: 8 doubles)
-__device__ __forceinline__ void pcg_block_sum2(double &v, double &w, double *smem) {
-#pragma unroll
-  for (int stride = 1; stride < 64; stride *= 2) { v = v + __shfl_down(v, stride, 64); w = w + __shfl_down(w, stride, 64); }
-  if (threadIdx.x % 64 == 0) { smem[threadIdx.x / 64] = v; smem[4 + threadIdx.x / 64] = w; }
-  __syncthreads();
-  const double vlo = smem[0] + smem[1], vhi = smem[2] + smem[3], wlo = smem[4] + smem[5], whi = smem[6] + smem[7];
-  v = vlo + vhi; w = wlo + whi;
-}
+constexpr int kFoldLanes = 1024;
 
 // where lane (i, j) of box `box` reads its neighbour across face `face` when that neighbour lies outside the box: the column (pointer to its plane 0;
 // for the k faces to the cell itself) in the box next door, or -- Dirichlet domain face -- nowhere: the value is -x(centre) (apply_BCs_p1's)
@@ -199,17 +167,8 @@ __global__ __launch_bounds__(kFoldLanes) void pcg_fold2_kernel(double *__restric
   pcg_fold_body<2>(partials, n, chunk, result, seq);
 }
 
-struct PcgGrid { int nseg, ncb, items, per_xcd, grid; };
-static PcgGrid pcg_grid(const hpgmg_hip_level *L) {
-  PcgGrid g;
-  g.nseg = (L->dim + kPcgSeg - 1) / kPcgSeg;
-  g.ncb = (L->dim * L->dim + kPcgLanes - 1) / kPcgLanes;
-  g.items = g.ncb * g.nseg * L->num_boxes;
-  g.grid = grid_for(g.items, &g.per_xcd);
-  return g;
-}
 // fold the scratch's one (out1 == nullptr) or two arrays of `items` values and wait for the sums
-static int pcg_fold(int items, double *out0, double *out1 = nullptr) {
+int pcg_fold(int items, double *out0, double *out1) {
   int chunk = 1;
   while ((long long)chunk * kFoldLanes < items) chunk *= 2;
   Scalar t;
@@ -225,11 +184,6 @@ using namespace hpgmg;
 extern "C" {
 int hpgmg_hip_graph_flush(void);
 
-// what every launch of this file needs of the level: a box side and a number of workgroups the grid arithmetic holds
-static int pcg_geometry_ok(const hpgmg_hip_level *L) {
-  if (L->num_boxes < 1 || L->dim < 1 || L->dim > 1024) return 0;
-  return (long long)((L->dim * L->dim + kPcgLanes - 1) / kPcgLanes) * ((L->dim + kPcgSeg - 1) / kPcgSeg) * L->num_boxes < (1LL << 30) / kXcds;
-}
 int hpgmg_hip_pcg_supported(const hpgmg_hip_level *L, int variant) {
   if (variant != HPGMG_HIP_7PT_VC_HELMHOLTZ && variant != HPGMG_HIP_7PT_VC_POISSON) return 0;
   if (!L->box_nbr || L->ghosts < 1) return 0;

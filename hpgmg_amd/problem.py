@@ -78,6 +78,18 @@ solvers (periodic or six Neumann walls without an a alpha term; create the solve
 lambda ~ 0) and a Helmholtz solver with alpha == 0 somewhere.  eigs leaves the coefficients (and coefficient_version) alone; it ends a march and
 invalidates the stored right-hand side and solution as set_coefficients does.  DESIGN.md §11.11.
 
+The wave equation: wave_start(u, v, f, boundary=g, dt=..., beta=0.25, gamma=0.5, damping=0.0) begins a march of
+alpha d2u/dt2 + damping alpha du/dt = b div(beta grad u) + f  -- acoustics, a membrane, structural vibration, the telegraph equation -- from the state u
+and the velocity v by the implicit Newmark rule (beta, gamma); the default is the average-acceleration rule: second order, unconditionally stable and
+energy conserving.  gamma >= 1/2 and beta >= gamma / 2 are taken (the conditionally stable rules, central differences included, are refused), on a solver
+created with a != 0 and alpha > 0 in every cell.  One step is one solve with a = 1 / (beta dt^2) + damping gamma / (beta dt), which the march sets,
+warm-started from the predictor.  wave_step(f, boundary=g) advances to the next time, f and g being those of that time; dt= changes the step (a
+set_shift and nothing else); beta, gamma and damping stay wave_start's.  u, v and the acceleration stay in the library, on the device, between calls:
+get_solution(), velocity() and acceleration() return them.  WaveInfo adds t, kinetic = h^3/2 sum alpha v^2 and potential = h^3/2 u^T K u (K: eigs' K)
+to SolveInfo's fields, and energy, their sum; the potential energy comes from the step's closing residual and is exact for the u the solve stopped at.
+Only one march is live: step() and rate() refuse on a wave march, wave_step(), velocity() and acceleration() on a theta march; what ends one ends the
+other.  DESIGN.md §11.12.
+
 NumPy arrays take the host path.  torch tensors on the library's GPU (float64, contiguous) are read and written in place, and results come
 back as tensors on that device.  torch must be imported before this package loads its libraries: both bring a HIP runtime
 (libamdhip64.so.7), and a device pointer is only valid inside the runtime that made it.  The C entry points are hpgmg_user_* of
@@ -117,6 +129,19 @@ class StepInfo(SolveInfo):
     """Of one time step (Solver.step): SolveInfo of the step's solve, whose right-hand side is f + T(g) + a alpha u0 + c w0."""
     rate: float          # max |alpha du/dt| at the new time
     t: float             # time since start()
+
+
+@dataclass
+class WaveInfo(SolveInfo):
+    """Of Solver.wave_start / wave_step: SolveInfo of the step's solve (wave_start: no solve ran, vcycles = 0, converged False, residual
+    and norm_f those of A0 u = f + T(g) at the start), and the discrete energies at the new time."""
+    t: float             # time since wave_start()
+    kinetic: float       # h^3/2 sum alpha v^2
+    potential: float     # h^3/2 u^T K u, K = apply() without its a alpha term and with zero data
+
+    @property
+    def energy(self):
+        return self.kinetic + self.potential
 
 
 @dataclass
@@ -183,6 +208,7 @@ class Solver:
         self.robin_faces = tuple(f for f in range(6) if faces is not None and faces[f] == "convective")
         self._ptr = None
         self._dt = self._theta = None       # of the last start() / step()
+        self._wave = None                   # (dt, beta, gamma, damping) of the last wave_start() / wave_step() while that march is live
         self._t = 0.0                       # time since start()
         self.coefficient_version = 0        # counts the calls that may change the operator (set_coefficients, set_shift, a march's new a): autograd.solve
         out = ctypes.c_void_p()
@@ -630,7 +656,7 @@ class Solver:
         if st == H.USER_UNSUPPORTED:
             raise ValueError("alpha: zero everywhere, so there is no du/dt term to march")
         self._check(st, "u, f, boundary, dt or theta")
-        self.a, self._dt, self._theta, self._t = 1.0 / (theta * dt), dt, theta, 0.0
+        self.a, self._dt, self._theta, self._t, self._wave = 1.0 / (theta * dt), dt, theta, 0.0, None
 
     def step(self, f, boundary=None, dt=None, theta=None, rtol=1e-8):
         """One theta step to the next time; f and `boundary` are those of the NEW time.  dt, theta None: as in the call before (a change rebuilds
@@ -669,6 +695,111 @@ class Solver:
             raise ValueError("rate: no march is live (start() begins one; set_coefficients, set_rhs and solve end it)")
         self._check(st, "out")
         return out
+
+    # ---- the wave equation (module docstring)
+    _NO_WAVE = "no wave march is live (wave_start() begins one; set_coefficients, set_rhs, solve, eigs and start end it)"
+
+    @staticmethod
+    def _wave_shift(dt, beta, gamma, damping):
+        """a of one Newmark step, in the library's written order (inf where a divisor underflows to zero, as in C)."""
+        with np.errstate(all="ignore"):
+            return float(np.float64(1.0) / np.float64(beta * (dt * dt)) + np.float64(damping * gamma) / np.float64(beta * dt))
+
+    def _wave_args(self, dt, beta, gamma, damping):
+        if self.a == 0.0:
+            raise ValueError("a: the wave march needs a Helmholtz solver (create it with a != 0 and set alpha; a is then set from dt, beta, gamma and damping)")
+        for name, v in (("dt", dt), ("beta", beta), ("gamma", gamma), ("damping", damping)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+                raise ValueError(f"{name}: {v!r} must be a finite number")
+        if not dt > 0.0:
+            raise ValueError(f"dt: {dt!r} must be > 0")
+        if not damping >= 0.0:
+            raise ValueError(f"damping: {damping!r} must be >= 0")
+        if not gamma >= 0.5:
+            raise ValueError(f"gamma: {gamma!r} must be >= 0.5 (a smaller gamma is unstable)")
+        if not beta >= gamma / 2.0:
+            raise ValueError(f"beta: {beta!r} must be >= gamma / 2 = {gamma / 2.0!r} (smaller values, central differences included, are conditionally stable)")
+        dt, beta, gamma, damping = float(dt), float(beta), float(gamma), float(damping)
+        if not np.isfinite(self._wave_shift(dt, beta, gamma, damping)):
+            raise ValueError(f"dt: {dt!r} gives a shift a = 1 / (beta dt^2) + damping gamma / (beta dt) that is not finite")
+        return dt, beta, gamma, damping
+
+    @staticmethod
+    def _wave_info(info):
+        return WaveInfo(info.norm_of_residual, info.norm_of_f, info.vcycles, bool(info.converged), info.mean_shift, info.t, info.kinetic, info.potential)
+
+    def wave_start(self, u, v, f, boundary=None, dt=None, beta=0.25, gamma=0.5, damping=0.0):
+        """Begins a march of  alpha d2u/dt2 + damping alpha du/dt = b div(beta grad u) + f  at the state u and the velocity v, with the source f and the wall
+        data `boundary` of that time (as set_rhs takes them), by the Newmark rule (beta, gamma): gamma >= 1/2, beta >= gamma / 2.  Sets
+        a = 1 / (beta dt^2) + damping gamma / (beta dt) and the acceleration (f - L(u; boundary)) / alpha - damping v, which needs alpha > 0 in every cell.
+        Returns WaveInfo with t = 0, vcycles = 0 and the energies of the start.  wave_step() advances; get_solution(), velocity() and acceleration() return
+        the state."""
+        if dt is None:
+            raise ValueError("dt: required (the time step, > 0)")
+        dt, beta, gamma, damping = self._wave_args(dt, beta, gamma, damping)
+        pu, where, kind = self._arg(u, (self.n,) * 3, "u")
+        pv = self._arg(v, (self.n,) * 3, "v", kind)[0]
+        pf = self._arg(f, (self.n,) * 3, "f", kind)[0]
+        pg = self._boundary(boundary, kind) if boundary is not None else None
+        self._sync_torch(kind)
+        self.coefficient_version += 1        # the march sets a
+        info = H.UserWaveInfo()
+        st = self.lib.hpgmg_user_wave_start(self._ptr, pu, pv, pf, pg, where, dt, beta, gamma, damping, ctypes.byref(info))
+        if st in (H.USER_OK, H.USER_NOT_FINITE):
+            self._dt = self._wave = None     # past its checks the library has ended whatever march was live
+        if st == H.USER_NOT_FINITE:
+            named = [("u", u, 0.0, False), ("v", v, 0.0, False), ("f", f, 0.0, False)] + ([("boundary", boundary, 0.0, False)] if boundary is not None else [])
+            self._check(st, self._first_bad(named, st))
+        if st == H.USER_OUT_OF_RANGE:
+            raise ValueError("alpha: zero in some cell, so the acceleration (f - L u) / alpha is not defined there (the wave march needs alpha > 0 everywhere)")
+        self._check(st, "u, v, f, boundary, dt, beta, gamma or damping")
+        self.a, self._t, self._wave = self._wave_shift(dt, beta, gamma, damping), 0.0, (dt, beta, gamma, damping)
+        return self._wave_info(info)
+
+    def wave_step(self, f, boundary=None, dt=None, rtol=1e-8):
+        """One Newmark step to the next time; f and `boundary` are those of the NEW time.  dt None: as in the call before (a change rebuilds the operator's
+        diagonals, nothing else).  V-cycles from the predictor run until the residual of the step's equation is below rtol times its right-hand side (20 at
+        most).  Returns WaveInfo: SolveInfo's fields for that solve, t, and the kinetic and potential energy at the new time."""
+        if self._wave is None:
+            raise ValueError(f"wave_step: {self._NO_WAVE}")
+        if not rtol > 0.0:
+            raise ValueError(f"rtol: {rtol!r} must be > 0")
+        dt, beta, gamma, damping = self._wave_args(self._wave[0] if dt is None else dt, *self._wave[1:])
+        pf, where, kind = self._arg(f, (self.n,) * 3, "f")
+        pg = self._boundary(boundary, kind) if boundary is not None else None
+        self._sync_torch(kind)
+        a, info = self._wave_shift(dt, beta, gamma, damping), H.UserWaveInfo()
+        if a != self.a:
+            self.coefficient_version += 1
+        st = self.lib.hpgmg_user_wave_step(self._ptr, pf, pg, where, dt, float(rtol), ctypes.byref(info))
+        if st == H.USER_NOT_FINITE:
+            named = [("f", f, 0.0, False)] + ([("boundary", boundary, 0.0, False)] if boundary is not None else [])
+            self._check(st, self._first_bad(named, st))
+        if st == H.USER_NOT_READY:
+            self._wave = None
+            raise ValueError(f"wave_step: {self._NO_WAVE}")
+        self._check(st, "f, boundary or dt")
+        self.a, self._t, self._wave = a, self._t + dt, (dt, beta, gamma, damping)
+        return self._wave_info(info)
+
+    def _wave_get(self, call, name, out):
+        if out is None:
+            out = np.empty((self.n,) * 3, dtype=np.float64)
+        p, where, kind = self._arg(out, (self.n,) * 3, "out")
+        self._sync_torch(kind)
+        st = call(self._ptr, p, where)
+        if st == H.USER_NOT_READY:
+            raise ValueError(f"{name}: {self._NO_WAVE}")
+        self._check(st, "out")
+        return out
+
+    def velocity(self, out=None):
+        """The velocity v = du/dt of the wave march's state into `out` (NumPy array or tensor), or a new NumPy array."""
+        return self._wave_get(self.lib.hpgmg_user_get_velocity, "velocity", out)
+
+    def acceleration(self, out=None):
+        """The acceleration d2u/dt2 of the wave march's state into `out` (NumPy array or tensor), or a new NumPy array."""
+        return self._wave_get(self.lib.hpgmg_user_get_acceleration, "acceleration", out)
 
     # ---- eigenmodes (module docstring; DESIGN.md §11.11)
     def eigs(self, k, rtol=1e-6, max_iter=60, extra=2, x0=None, out=None):
@@ -712,7 +843,7 @@ class Solver:
         if st == H.USER_NOT_READY:
             raise ValueError("eigs: no valid coefficients (an earlier set_coefficients was refused)")
         self._check(st, "x0" if st == H.USER_NOT_FINITE else "k, extra, rtol, max_iter, x0 or out")
-        self._dt = None                     # a march is over
+        self._dt = self._wave = None        # a march is over
         return lam, out, EigInfo(info.iterations, info.vcycles, np.array(info.residuals[:k]), np.array(info.mu[:k]), bool(info.converged))
 
     def wall_flux(self, fluxes):

@@ -205,6 +205,33 @@ typedef struct {
 } hpgmg_user_eig_info;
 int  hpgmg_user_eigs(hpgmg_user_solver *s, int k, int extra, double rtol, int max_iter, const double *x0, int where, double *lam, double *modes,
                      hpgmg_user_eig_info *info);
+/* The wave equation:  alpha d2u/dt2 + sigma alpha du/dt = b div(beta grad u) + f  with the walls and data g of the solver, by the
+ * implicit Newmark rule (beta, gamma), gamma >= 1/2 and beta >= gamma / 2: the unconditionally stable rules (1/4, 1/2 is the average-acceleration
+ * rule: second order, energy conserving).  One step is one solve with the operator for a = 1 / (beta dt^2) + sigma gamma / (beta dt), warm-started from
+ * the predictor.  The library keeps u, v = du/dt and the acceleration q = d2u/dt2 on the device between calls; only f (and g) come in per step.
+ * wave_start: begins a march at (u, v) with the source f and data g of that time (g NULL as set_rhs allows it), sets a and
+ *   q = (f - L(u; g)) / alpha - sigma v.  dt <= 0 or not finite, sigma < 0 or not finite, gamma < 1/2, beta < gamma / 2, a not finite, a Poisson solver:
+ *   HPGMG_USER_BAD_ARGUMENT; alpha == 0 in some cell: HPGMG_USER_OUT_OF_RANGE; g on a periodic box: HPGMG_USER_UNSUPPORTED; u, v, f or g not finite:
+ *   HPGMG_USER_NOT_FINITE.  It shares hpgmg_user_start's two vectors and adds one more to the finest level at the first call.  It ends whatever march was
+ *   live, also when it is refused after its first pack.  info: t = 0, vcycles = 0, norm_of_f = |f + T(g)|, norm_of_residual = |f + T(g) - A0 u|.
+ * wave_step: one step to the next time, f and g being those of the NEW time; dt <= 0: as in the call before (a change sets the shift and nothing else;
+ *   beta, gamma and sigma are wave_start's).  V-cycles from the predictor run until |F - A0 u| < rtol |F| (20 at most), F the step's right-hand side.
+ *   f or g not finite: HPGMG_USER_NOT_FINITE, and u, v, q and the march are as before the call.
+ * info: hpgmg_user_info's fields of the step's solve, t the time since wave_start, kinetic = h^3/2 sum alpha v^2 and potential = h^3/2 u^T K u
+ *   (K = apply without its a alpha term and with zero data), the latter from the solve's closing residual: exact for the u the solve stopped at.
+ * get_velocity, get_acceleration: v, q into an (N,N,N) array; get_solution returns u.
+ * Only one march is live: hpgmg_user_step / _get_rate answer HPGMG_USER_NOT_READY on a wave march, the wave calls on a theta march or none.  Whatever
+ * ends a theta march ends a wave march; after a step the solver holds no right-hand side of the caller's. */
+typedef struct {
+  double norm_of_residual, norm_of_f, mean_shift;
+  int    vcycles, converged;
+  double t, kinetic, potential;
+} hpgmg_user_wave_info;
+int  hpgmg_user_wave_start(hpgmg_user_solver *s, const double *u, const double *v, const double *f, const double *g, int where, double dt, double beta,
+                           double gamma, double damping, hpgmg_user_wave_info *info);
+int  hpgmg_user_wave_step(hpgmg_user_solver *s, const double *f, const double *g, int where, double dt, double rtol, hpgmg_user_wave_info *info);
+int  hpgmg_user_get_velocity(hpgmg_user_solver *s, double *out, int where);
+int  hpgmg_user_get_acceleration(hpgmg_user_solver *s, double *out, int where);
 
 /* ---- small accessors so a ctypes caller never needs the struct layouts ---- */
 enum { HPGMG_INFO_DIM = 0, HPGMG_INFO_BOX_DIM, HPGMG_INFO_GHOSTS, HPGMG_INFO_JSTRIDE, HPGMG_INFO_KSTRIDE,

@@ -459,6 +459,15 @@ int hpgmg_hip_dense_unpack_cell_sensitivity(const hpgmg_hip_level *L, int u_id, 
  * NaN is skipped), folded by a second tiny launch and waited for. */
 int hpgmg_hip_step_rhs(const hpgmg_hip_level *L, int num_vectors, int F_id, int u_id, int uold_id, int w_id, double a, double c);
 int hpgmg_hip_step_rate(const hpgmg_hip_level *L, int num_vectors, int w_id, int r_id, int u_id, int uold_id, double a, double c, double *max_abs);
+/* the three passes of the Newmark march (include/hpgmg_operators.h hpgmg_wave_predict / _correct / _init; kernels/dense_wave.hip), one
+ * launch each in the CG passes' mapping over the interior cells of every box; num_vectors as above.  wave_correct and wave_init end in a second tiny
+ * launch that folds their two sums (sums[0] the kinetic, sums[1] the potential one: HOST doubles) and wait for them.  A level the mapping does not hold,
+ * an id outside the level or a written vector named twice is refused with an error recorded and nothing launched (sums then 0.0). */
+int hpgmg_hip_wave_predict(const hpgmg_hip_level *L, int num_vectors, int u_id, int uold_id, int v_id, int F_id, int q_id, double dt, double cu, double cv,
+                           double a, double sigma);
+int hpgmg_hip_wave_correct(const hpgmg_hip_level *L, int num_vectors, int q_id, int v_id, int u_id, int uold_id, int F_id, int r_id, double a, double cq,
+                           double cg, double sums[2]);
+int hpgmg_hip_wave_init(const hpgmg_hip_level *L, int num_vectors, int q_id, int r_id, int u_id, int v_id, int F_id, double a, double sigma, double sums[2]);
 
 /* ---- operators/rebuild.c:47-208 black-box rebuild: accumulate one colouring (x = 0/1 pattern, ghosts
  *      already exchanged / BCs applied) into Aii and sum|Aij|, then turn them into Dinv, L1inv, lambda_max ---- */

@@ -292,6 +292,25 @@ int     hpgmg_block_gram_host(level_type *level, const int *a_ids, int na, const
 int     hpgmg_block_combine_host(level_type *level, const int *out_ids, int nout, const int *in_ids, int nin, const double *C);
 int     hpgmg_block_residual_host(level_type *level, const int *r_ids, const int *ax_ids, const int *x_ids, int n, int w_id, const double *mu, double *rmax,
                                   double *mxmax);
+/* The three streaming passes of the Newmark march of the user-problem API (hpgmg_user_wave_start / hpgmg_user_wave_step, include/hpgmg_fv.h; DESIGN.md
+ * §11.12) over the interior cells of every box of a Helmholtz level (alpha = VECTOR_ALPHA); ghost and padding doubles are neither read nor written:
+ *   wave_predict:  ut = (u + dt * v) + cu * q ;  vt = v + cv * q ;  F = F + alpha * (a * ut - sigma * vt) ;  then u = ut, uold = ut, v = vt
+ *                  (F holds f + T(g) on entry; cu = dt^2 (1/2 - beta), cv = dt (1 - gamma)).  5 reads, 4 writes.
+ *   wave_correct:  q = (u - uold) * cq ;  v = v + cg * q  (cq = 1 / (beta dt^2), cg = gamma dt; r is the residual F - A0 u of the step's solve).
+ *                  6 reads, 2 writes.
+ *   wave_init:     q = ((r + (a * alpha) * u) / alpha) - sigma * v  (r = F - A0 u).  5 reads, 1 write.
+ * in exactly that written order (include/hpgmg_wave_math.h, which the host defaults and the kernels both compile).  wave_correct and wave_init also
+ * return sums[0] = sum over the cells of (alpha * v) * v (the new v) and sums[1] = sum of u * ((F - r) - (a * alpha) * u), each ONE tree of the CG
+ * passes' order above: sums[0] has the bits of hpgmg_block_gram([v], [v], VECTOR_ALPHA).  A NaN or Inf propagates into the sums.
+ * Return value as the block hooks: 1 = the plugin's kernel ran, 0 = the portable form (host/hooks_host.inc, the CPU oracle), same bits, and -1 =
+ * refused (an id that is not a vector of the level, a level without alpha, a vector that is written -- u, uold, v, F of wave_predict, q and v of
+ * wave_correct, q of wave_init -- named twice or equal to VECTOR_ALPHA): nothing written. */
+int     hpgmg_wave_predict(level_type *level, int u_id, int uold_id, int v_id, int F_id, int q_id, double dt, double cu, double cv, double a, double sigma);
+int     hpgmg_wave_correct(level_type *level, int q_id, int v_id, int u_id, int uold_id, int F_id, int r_id, double a, double cq, double cg, double sums[2]);
+int     hpgmg_wave_init(level_type *level, int q_id, int r_id, int u_id, int v_id, int F_id, double a, double sigma, double sums[2]);
+int     hpgmg_wave_predict_host(level_type *level, int u_id, int uold_id, int v_id, int F_id, int q_id, double dt, double cu, double cv, double a, double sigma);      /* the portable forms themselves (0 or -1) */
+int     hpgmg_wave_correct_host(level_type *level, int q_id, int v_id, int u_id, int uold_id, int F_id, int r_id, double a, double cq, double cg, double sums[2]);
+int     hpgmg_wave_init_host(level_type *level, int q_id, int r_id, int u_id, int v_id, int F_id, double a, double sigma, double sums[2]);
 /* Launch-bound stretches of a cycle (everything done on levels of <= 64^3 cells between two
  * bottom solves) are bracketed by the cycle driver as a SEGMENT with a key that repeats every
  * solve, so the HIP plugin can capture it once into a hipGraph and replay it.  Plugins without

@@ -10,6 +10,11 @@ without torch).  These three are timed alike, with the host clock between device
 the two passes of kernels/dense_step.hip alone (hook calls in a row between an event pair: step_rate's figure includes its fold launch and the
 host's wait for the value) as ms and as 48 B per cell per second; set_shift.
 
+The wave march, device arrays only, timed like the time march: one wave_step() of the average-acceleration rule; the same update
+without a march from the same start -- torch forms the predictor and the right-hand side, solve(rhs, u0=predictor) into u, torch forms the acceleration
+and the velocity (skipped without torch); the three passes of kernels/dense_wave.hip alone per hook call, against 72 / 64 / 48 B per cell
+(wave_correct's and wave_init's figures include their fold launch and the host's wait for the two sums).
+
     python tools/user_problem_timing.py [--n 256] [--repeats 5]
 """
 import argparse
@@ -83,6 +88,7 @@ def main():
             res[f"unpack_one_field_{where}_ms"] = timed(lambda: lib.hpgmg_dense_unpack(L, H.VECTOR_U, U, w))
         res["fmg_residual"] = "%1.15e" % info.norm_of_residual
         march_timing(args, lib, K, s, res, timed, d_f, d_u, f, alpha)
+        wave_timing(args, lib, K, s, res, timed, d_f, d_u, f, alpha)
     for p in dev:
         K.hpgmg_hip_free(p)
     K.hpgmg_hip_event_destroy(e0)
@@ -148,6 +154,80 @@ def march_timing(args, lib, K, s, res, timed, d_f, d_u, f, alpha):
         cycles.append(i.vcycles)
     res["torch_route_ms"] = statistics.median(out[1:])
     res["torch_route_vcycles"] = cycles[1:]
+
+
+def wave_timing(args, lib, K, s, res, timed, d_f, d_u, f, alpha):
+    """The wave march on the same solver, after march_timing (module docstring): d_u holds the start state and, as a second array, the start velocity."""
+    n, S, W = s.n, s._ptr, H.WHERE_PLUGIN
+    dt, rtol, beta, gamma, sigma = 1e-3, 1e-6, 0.25, 0.5, 0.0
+    L = lib.hpgmg_solver_level(lib.hpgmg_user_solver_of(S), 0)
+    info = H.UserWaveInfo()
+    assert K.hpgmg_hip_memcpy_h2d(d_u, f.ctypes.data, f.nbytes) == 0
+    res["wave_rtol"], res["wave_dt"] = rtol, dt
+    assert lib.hpgmg_user_wave_start(S, d_u, d_u, d_f, None, W, dt, beta, gamma, sigma, ctypes.byref(info)) == H.USER_OK
+    q0 = np.empty((n, n, n))
+    assert lib.hpgmg_user_get_acceleration(S, q0.ctypes.data, H.WHERE_HOST) == H.USER_OK
+    out, cycles, energy = [], [], []
+    for _ in range(args.repeats + 1):                                                   # the first is the warm-up
+        K.hpgmg_hip_sync()
+        t0 = time.perf_counter()
+        assert lib.hpgmg_user_wave_step(S, d_f, None, W, 0.0, rtol, ctypes.byref(info)) == H.USER_OK
+        K.hpgmg_hip_sync()
+        out.append((time.perf_counter() - t0) * 1e3)
+        cycles.append(info.vcycles)
+        energy.append(info.kinetic + info.potential)
+    res["wave_step_ms"] = statistics.median(out[1:])
+    res["wave_step_vcycles"] = cycles[1:]
+    res["wave_step_energy"] = energy[1:]
+    # the three passes alone, on the march's own vectors (their values do not matter to the time)
+    nv = (ctypes.c_int * H.INFO_COUNT)()
+    lib.hpgmg_level_info(L, nv)
+    uold_id, v_id, q_id, calls = nv[H.INFO_NUM_VECTORS] - 3, nv[H.INFO_NUM_VECTORS] - 2, nv[H.INFO_NUM_VECTORS] - 1, 20
+    a, cq, cg = s._wave_shift(dt, beta, gamma, sigma), 1.0 / (beta * dt * dt), gamma * dt
+    sums = (ctypes.c_double * 2)()
+    took = {}
+
+    def predict_calls():
+        for _ in range(calls):
+            took["wave_predict"] = lib.hpgmg_wave_predict(L, H.VECTOR_U, uold_id, v_id, H.VECTOR_F, q_id, dt, 0.0, 0.0, a, sigma)
+        K.hpgmg_hip_sync()
+
+    def correct_calls():
+        for _ in range(calls):
+            took["wave_correct"] = lib.hpgmg_wave_correct(L, q_id, v_id, H.VECTOR_U, uold_id, H.VECTOR_F, H.VECTOR_TEMP, a, cq, cg, sums)
+
+    def init_calls():
+        for _ in range(calls):
+            took["wave_init"] = lib.hpgmg_wave_init(L, q_id, H.VECTOR_TEMP, H.VECTOR_U, v_id, H.VECTOR_F, a, sigma, sums)
+    for name, fn, nbytes in (("wave_predict", predict_calls, 72.0), ("wave_correct", correct_calls, 64.0), ("wave_init", init_calls, 48.0)):
+        fn()
+        ms = timed(fn) / calls
+        assert took[name] == 1, (name, took)                                          # the kernel ran, not the portable form
+        res[f"{name}_call_ms"] = ms
+        res[f"{name}_TB_per_s"] = nbytes * n ** 3 / (ms * 1e-3) / 1e12
+    if torch is None:
+        res["wave_torch_route_ms"] = None
+        return
+    dev = torch.device("cuda", torch.cuda.current_device())
+    t_alpha, t_f = torch.from_numpy(alpha).to(dev), torch.from_numpy(f).to(dev)
+    t_u, t_v, t_q = torch.from_numpy(f).to(dev), torch.from_numpy(f).to(dev), torch.from_numpy(q0).to(dev)
+    s.set_shift(a)
+    cu, cv = dt * dt * (0.5 - beta), dt * (1.0 - gamma)
+    out, cycles = [], []
+    for _ in range(args.repeats + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ut = t_u + dt * t_v + cu * t_q
+        vt = t_v + cv * t_q
+        rhs = t_f + t_alpha * (a * ut - sigma * vt)
+        _, i = s.solve(rhs, rtol=rtol, u0=ut, out=t_u)
+        t_q = (t_u - ut) * cq
+        t_v = vt + cg * t_q
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+        cycles.append(i.vcycles)
+    res["wave_torch_route_ms"] = statistics.median(out[1:])
+    res["wave_torch_route_vcycles"] = cycles[1:]
 
 
 if __name__ == "__main__":
